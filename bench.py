@@ -10,14 +10,21 @@ A step = one render_grafx pass over one resident batch.  The batch axis shards o
 (weak scaling: 256 graphs per GPU, no data-path collective for the forward render).
 Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the JSON line.  `--full` adds
+everything else the line used to carry: the live per-kernel roofline of the timed steps, the `sustained` repetition,
+the training step, the `secondary` workloads and the CPU baseline (each of them can still be dropped with its `--no-*`
+flag).  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; a larger output is
+sampled with a fixed seed, at most 48 MiB in all), so that two builds can be compared output for output: the inputs
+are seeded and identical from run to run.
+
 `--gpus N` without a launcher (no RANK in the environment) makes this process a pure launcher: it starts
 N children — one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1 — BEFORE
 anything here touches the GPU, relays rank 0's JSON line and exits non-zero if any rank failed.
 
 Other workloads (`--config`): cfg2 = BASELINE configs[1] (ParametricEqualizer, 1024 x 1 x 480000),
-cfg3 = configs[2] (STFTMaskedNoiseReverb, 512 x 2 x 240000); each prints the same kind of line with its own
-roofline.  `--dry --backend gloo` is the CPU plumbing check of the multi-rank path (pass-through processors,
-no audio arithmetic; used by tests/test_bench_launch.py) — its numbers mean nothing and the line says so.
+cfg3 = configs[2] (STFTMaskedNoiseReverb, 512 x 2 x 240000); each prints the same kind of line (with --full: with its
+own roofline and CPU baseline).  `--dry --backend gloo` is the CPU plumbing check of the multi-rank path (pass-through
+processors, no audio arithmetic; used by tests/test_bench_launch.py) — its numbers mean nothing and the line says so.
 """
 import argparse
 import json
@@ -54,12 +61,19 @@ def parse_args(argv=None):
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only with --dry)")
     ap.add_argument("--dry", action="store_true",
                     help="CPU plumbing check: pass-through processors on CPU tensors (launch, sharding, barriers, JSON)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step measurement")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 6 s repetition of the headline step (`sustained`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the per-kernel roofline of the timed steps, the "
+                         "`sustained` leg, the training step, the `secondary` workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; a seeded "
+                         "sample when larger than 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-train", action="store_true", help="(with --full) skip the secondary training-step measurement")
+    ap.add_argument("--no-sustained", action="store_true",
+                    help="(with --full) skip the >= 6 s repetition of the headline step (`sustained`)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the cfg2 / cfg3 measurements (BASELINE configs[1] / configs[2]) that the default single-GPU "
-                         "run appends to the line as `secondary`, with their compat (upstream default tap counts) twins")
+                    help="(with --full) skip the cfg2 / cfg3 measurements (BASELINE configs[1] / configs[2]) that the "
+                         "single-GPU run appends to the line as `secondary`, with their compat (upstream default tap counts) twins")
     ap.add_argument("--reference-default-lengths", action="store_true",
                     help="use the reference's default (even) filter lengths 4000/16384/60000: every convolve() then takes "
                          "the odd-P aliasing compatibility path (DESIGN.md section 2); not the headline configuration")
@@ -70,7 +84,7 @@ def parse_args(argv=None):
     ap.add_argument("--capture", action="store_true",
                     help="replay the render as one captured HIP graph (grafx_amd.render.CapturedRender): the serving "
                          "path for small batches, where the eager loop is host-bound")
-    ap.add_argument("--train", action="store_true", help="(kept for compatibility: the training step is timed by default)")
+    ap.add_argument("--train", action="store_true", help="(kept for compatibility: --full times the training step)")
     ap.add_argument("--train-batch", type=int, default=256, help="graphs per GPU in the training step (configs[4]: 256)")
     ap.add_argument("--train-steps", type=int, default=3)
     return ap.parse_args(argv)
@@ -423,6 +437,51 @@ def partitioned_conv_unit_rooflines(prof, steps, rows, L, N):
     return out or None
 
 
+DUMP_BYTES = 48 * 2**20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array of ``arrays`` ({name: tensor whose last axis is time}) as ``outdir/<name>.npy`` in
+    float32.  An array larger than its share of ``budget`` is sampled with a fixed seed: every row keeps one contiguous
+    window of W samples at a drawn offset (W as large as the share allows, at least 256; when even that is too much, a
+    drawn subset of the rows keeps its windows).  The sample depends on the shape alone, so runs with the same arguments
+    write the same elements.  -> {name: (shape written, "all" | description of the sample)}"""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        rows = t.reshape(-1, t.shape[-1])
+        R, L = rows.shape
+        if R * L * 4 <= share:
+            sample, how = rows.reshape(t.shape), "all"
+        else:
+            rng = np.random.default_rng(0)
+            W = min(L, max(256, share // (4 * R)))
+            k = min(R, share // (4 * W))
+            sel = np.arange(R) if k == R else np.sort(rng.choice(R, size=k, replace=False))
+            off = rng.integers(0, L - W + 1, size=k)
+            idx = torch.as_tensor(off[:, None] + np.arange(W)[None, :], device=rows.device)
+            sample = torch.gather(rows[torch.as_tensor(sel, device=rows.device)], 1, idx)
+            if k == R:
+                sample = sample.reshape(*t.shape[:-1], W)
+            how = (f"{k} of the {R} rows of the {tuple(t.shape)} output (last axis: time), each a window of {W} samples "
+                   f"at an offset drawn with numpy default_rng(0)")
+        arr = sample.float().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+        written[name] = (list(arr.shape), how)
+    return written
+
+
+def _report_dump(written, world):
+    for name, (shape, how) in written.items():
+        print(f"[bench] --dump-outputs: {name}.npy {shape} float32: {how}"
+              + (f" (rank 0's shard of {world})" if world > 1 else ""), file=sys.stderr, flush=True)
+
+
 class GpuSampler:
     """Shader clock and board power from the amdgpu hwmon files (readable without privileges), sampled by a thread every
     50 ms while a loop runs.  The box lists every card of the node (other tenants' included): the card is the one whose
@@ -568,8 +627,8 @@ def _timed_region(args, torch, dist, dev, step, sync, fence, profile):
     for _ in range(args.warmup):
         y = step()
     fence()
-    # the dominant kernel is timed live, inside the timed region, with a pair of stream events around every launch
-    # (recorded on the stream the kernel runs on; no synchronisation, ~120 event records per step)
+    # with --full the dominant kernel is timed live, inside the timed region, with a pair of stream events around every
+    # launch (recorded on the stream the kernel runs on; no synchronisation, ~120 event records per step)
     import contextlib
 
     with (ops.profiling() if profile else contextlib.nullcontext()) as prof:
@@ -641,12 +700,14 @@ def bench_console(args, torch, dist, dev, world, rank, sync, fence):
             captured.append(CapturedRender(procs, x, params, rd_dev))
 
     y, elapsed, per_rank, prof = _timed_region(args, torch, dist, dev, step, sync, fence,
-                                               profile=not (args.capture or args.dry))
+                                               profile=args.full and not (args.capture or args.dry))
     assert torch.isfinite(y).all(), "render produced non-finite samples"
+    if args.dump_outputs and rank == 0:
+        _report_dump(dump_outputs(args.dump_outputs, {"output": y}), world)
     roof = roofline_from_profile(prof, args.steps, elapsed, B, L) if prof else None
 
     sustained = None
-    if world == 1 and not (args.dry or args.no_sustained):
+    if args.full and world == 1 and not (args.dry or args.no_sustained):
         y = None             # (checked above) release the timed region's buffer: the loop below keeps two of its own alive
         try:
             sustained = sustained_leg(torch, step, sync, elapsed / args.steps * 1e3)
@@ -654,7 +715,7 @@ def bench_console(args, torch, dist, dev, world, rank, sync, fence):
             sustained = {"error": f"{type(e).__name__}: {e}"}
 
     train = None
-    if not (args.no_train or args.capture):
+    if args.full and not (args.no_train or args.capture):
         y = None
         try:
             train = train_leg(args, torch, dist, dev, world, procs, params, x, rd_dev, L, sync, fence)
@@ -662,8 +723,8 @@ def bench_console(args, torch, dist, dev, world, rank, sync, fence):
             train = {"error": f"{type(e).__name__}: {e}"}
 
     secondary = None
-    if world == 1 and not (args.no_secondary or args.dry or args.capture or args.reference_default_lengths
-                           or args.reference_default_args):
+    if args.full and world == 1 and not (args.no_secondary or args.dry or args.capture or args.reference_default_lengths
+                                         or args.reference_default_args):
         x = None  # (the closure `step` is done with it) release the 8.6 GB batch before the other workloads allocate
         try:
             secondary = secondary_leg(torch, dev, sync)
@@ -685,6 +746,7 @@ def bench_console(args, torch, dist, dev, world, rank, sync, fence):
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "f32",
+        "full": args.full,
         "data": "synthetic (randn signals, randn*0.1 parameters, random-phase noise IRs)",
         "config": {"workload": "BASELINE configs[3]: 32-channel mixing console, 111 nodes / 142 edges, "
                                "ParametricEqualizer(6) + Compressor(iir) + STFTMaskedNoiseReverb + bus sums",
@@ -729,7 +791,7 @@ def bench_console(args, torch, dist, dev, world, rank, sync, fence):
         out["training"] = train
     if secondary is not None:
         out["secondary"] = secondary
-    if world == 1 and not args.no_cpu_baseline and not args.dry:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.dry:
         out["cpu_baseline"] = cpu_baseline_console(G, render_data, params_cpu, L)
     # the last key of the line (a reader that keeps only the tail of the output still sees every leg's number)
     summary = {"headline_ms": round(ms_per_step, 3), "headline_roofline_frac": None if roof is None else round(roof["frac"], 4)}
@@ -974,8 +1036,10 @@ def bench_processor(args, torch, dist, dev, world, rank, sync, fence):
     step, R, C, L, what = processor_case(args.config, torch, dev, rank, args.batch, args.length)
     step()
     sync()
-    y, elapsed, per_rank, prof = _timed_region(args, torch, dist, dev, step, sync, fence, profile=True)
+    y, elapsed, per_rank, prof = _timed_region(args, torch, dist, dev, step, sync, fence, profile=args.full)
     assert torch.isfinite(y).all(), "processor produced non-finite samples"
+    if args.dump_outputs and rank == 0:
+        _report_dump(dump_outputs(args.dump_outputs, {"output": y}), world)
     roof = roofline_from_profile(prof, args.steps, elapsed, R, L) if prof else None
     if rank != 0:
         return None
@@ -984,7 +1048,8 @@ def bench_processor(args, torch, dist, dev, world, rank, sync, fence):
         "metric": "channel-samples/sec through one processor call (all GPUs)",
         "value": world * R * C * L * args.steps / elapsed, "unit": "channel-samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic (randn signals and parameters)",
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": args.full,
+        "data": "synthetic (randn signals and parameters)",
         "config": {"workload": what, "rows_per_gpu": R, "channels": C, "audio_len": L,
                    "parallelism": f"row-shard x{world}"},
         "world_size": world if dist is None else dist.get_world_size(),
@@ -992,7 +1057,7 @@ def bench_processor(args, torch, dist, dev, world, rank, sync, fence):
         "roofline": roof,
         "call_roofline": call_roofline(R, C, L, ms_per_step),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_proc(args.config, L)
     return out
 
@@ -1002,6 +1067,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, argv))
     run_rank(args)

@@ -20,7 +20,7 @@ def _run(*flags, env_extra=None, timeout=300):
 
 def test_bench_gpus_2_launches_two_ranks():
     res = _run("--gpus", "2", "--dry", "--backend", "gloo", "--batch", "2", "--length", "4096", "--steps", "2",
-               "--warmup", "1")
+               "--warmup", "1", "--full")
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout  # ONE JSON line, from rank 0
@@ -45,7 +45,7 @@ def test_bench_gpus_8_dry_run_is_eight_ranks_eight_shards_one_gradient():
     """The node the driver's SCALE run wants (8 ranks) has never been available: everything but RCCL itself is exercised
     here -- eight processes, eight different shards of the batch, identical gradients after the flat all-reduce."""
     res = _run("--gpus", "8", "--dry", "--backend", "gloo", "--batch", "1", "--length", "2048", "--steps", "1",
-               "--warmup", "0", timeout=600)
+               "--warmup", "0", "--full", timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout
@@ -90,3 +90,69 @@ def test_bench_under_torch_distributed_run():
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 2 and out["world_size"] == 2
+
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """A plain run leaves out the training leg, the one leg besides the headline that a dry run carries (the sustained,
+    secondary and CPU-baseline legs are off in a dry run anyway; test_timed_region_... checks the step count and the
+    profiling switch); `--dump-outputs DIR` writes the last timed step's output as float32 .npy, the same values on
+    every run with the same arguments."""
+    import numpy as np
+
+    got = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        res = _run("--dry", "--backend", "gloo", "--batch", "2", "--length", "4096", "--steps", "3", "--warmup", "1",
+                   "--dump-outputs", str(d))
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["full"] is False
+        assert not {"training", "secondary", "sustained", "cpu_baseline"} & set(out), sorted(out)
+        assert [f.name for f in d.glob("*.npy")] == ["output.npy"]
+        got.append(np.load(d / "output.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape[0] == 2 and got[0].shape[-2:] == (2, 4096)
+    assert np.isfinite(got[0]).all() and np.array_equal(got[0], got[1])
+
+
+def test_dump_outputs_samples_a_large_output_within_the_bound(tmp_path):
+    """An output larger than the bound is written as a seeded sample: one window per row, the same on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    y = torch.randn(16, 2, 65536)                                   # 8 MiB against a 1 MiB bound
+    budget = 2**20
+    w1 = bench.dump_outputs(str(tmp_path / "a"), {"output": y}, budget=budget)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), {"output": y}, budget=budget)
+    assert w1 == w2 and w1["output"][1] != "all"
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert a.dtype == np.float32 and a.nbytes <= budget and np.array_equal(a, b)
+    W = a.shape[-1]
+    rows = y.reshape(-1, 65536).numpy()
+    for r, win in zip(rows, a.reshape(-1, W)):                     # every row kept: each sample is a window of its row
+        starts = [o for o in range(65536 - W + 1) if r[o] == win[0]]
+        assert any(np.array_equal(r[o:o + W], win) for o in starts)
+
+
+def test_timed_region_runs_warmup_then_exactly_steps_and_profiles_only_with_full():
+    """`--steps K --warmup W`: W calls before the fence that opens the timed region, exactly K inside it; the per-launch
+    events of the live roofline are recorded only when the caller asks for them (bench.py passes --full)."""
+    import torch
+
+    import bench
+
+    for full in (False, True):
+        args = bench.parse_args(["--steps", "7", "--warmup", "2"] + (["--full"] if full else []))
+        calls, fences = [], []
+
+        def step():
+            calls.append(1)
+            return torch.zeros(1)
+
+        y, elapsed, per_rank, prof = bench._timed_region(args, torch, None, torch.device("cpu"), step, lambda: None,
+                                                         lambda: fences.append(len(calls)), profile=args.full)
+        assert fences == [2, 9], fences          # 2 warm-up calls, then 7 timed ones between the two fences
+        assert elapsed > 0 and per_rank == [elapsed]
+        assert (prof is not None) == full

@@ -13,7 +13,7 @@ for set in "TCC_HIT_sum TCC_MISS_sum" "TCC_REQ_sum TCC_READ_sum" "TCC_EA_RDREQ_s
            "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum" "TCC_BUSY_sum TCC_TAG_STALL_sum" \
            "TCP_GATE_EN1_sum TCP_READ_TAGCONFLICT_STALL_CYCLES_sum" "TA_BUFFER_READ_WAVEFRONTS_sum TA_BUFFER_COALESCED_READ_CYCLES_sum"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/p$i -- python3 $R/bench.py --config cfg3 --steps 2 --warmup 1 --no-cpu-baseline ${CFG3_EXTRA} > $OUT/p$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/p$i -- python3 $R/bench.py --full --config cfg3 --steps 2 --warmup 1 --no-cpu-baseline ${CFG3_EXTRA} > $OUT/p$i.log 2>&1
 done
 python3 - > $OUT/summary.txt <<PY
 import csv, glob, collections, re
