@@ -704,10 +704,13 @@ int gfx_noise_shaping_ir_f32(const float* noise, int64_t noise_stride, const flo
         return GFX_EINVAL;
     if ((log_fade_in == nullptr) != (z_fade_in_gain == nullptr) || noise_stride < ir_len || R * C > 0x7fffffffLL)
         return GFX_EINVAL;
+    if (C > 65535) return GFX_EINVAL;
     const int64_t rows = R * C;
-    for (int64_t done = 0; done < rows; done += 65535) {  // grid.y limit
-        const int64_t n = rows - done < 65535 ? rows - done : 65535;
-        if (done % C != 0) return GFX_EINVAL;  // unreachable for C in {1,2,3,5,...}; keeps the channel phase
+    // grid.y limit; every launch starts on a channel boundary (the kernel takes the channel as its row index mod C) --
+    // 65535 itself is odd, so whole rows of C channels per launch
+    const int64_t step = 65535 / C * C;
+    for (int64_t done = 0; done < rows; done += step) {
+        const int64_t n = rows - done < step ? rows - done : step;
         hipLaunchKernelGGL(noise_shaping_ir_kernel, dim3((unsigned)((ir_len + 255) / 256), (unsigned)n), dim3(256), 0,
                            (hipStream_t)stream, noise, noise_stride, log_decay + done * K, log_gain + done * K,
                            log_fade_in ? log_fade_in + done * K : nullptr,

@@ -185,6 +185,7 @@ def fftconv_can_tee(Cin, Cf, L, Lout, off, N):
 
 
 GFX_EINVAL = -1                                  # include/grafx_amd.h
+GRID_YZ_MAX = 65535                              # workgroups along the second / third dimension of one launch
 SCHEDULES = {"auto": 0, "tile": 1, "pipe": 2}   # GFX_SCHED_* of include/grafx_amd.h
 # What `schedule="auto"` means to fftconv(): "auto" (the library decides: the persistent hand-scheduled kernel for large
 # launches it covers) or "pipe" (prefer that kernel at every size it covers -- tests and latency experiments).
@@ -362,6 +363,7 @@ def odd_alias_supported(P):
 # P = 8 388 607 and every adjoint take).
 ALIAS_PAIRS = os.environ.get("GRAFX_ALIAS_PAIRS", "1") != "0"
 ALIAS_ROWS_PER_CHUNK = int(os.environ.get("GRAFX_ALIAS_ROWS", "1024"))   # rows of one launch chain (and ALIAS_WS_CAP bytes at most)
+ALIAS_ONE_ROW_MAX = 16383    # rows one call of gfx_odd_alias_f32 / _rows_f32 / _adjoint_f32 accepts (csrc/czt.hip: czt_alias)
 
 
 def _alias_fns(precise, pairs=False):
@@ -425,6 +427,8 @@ def _alias_chunks(rows, P, rows_per_chunk, device, precise, pairs=False):
         free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
         cap = min(cap, max(free // 4, 1))
     unit = 2 if pairs else 1            # chunks of whole pairs: row 2r stays with row 2r + 1
+    if not pairs:                       # the one-transform-per-row entries take ALIAS_ONE_ROW_MAX rows per call
+        rows_per_chunk = min(rows_per_chunk, ALIAS_ONE_ROW_MAX)
     chunk = max(unit, min(rows, rows_per_chunk, unit * (cap // ws_bytes(unit, P))) // unit * unit)
     if chunk >= rows:
         chunk = rows
@@ -1250,12 +1254,17 @@ def gather_sum(buf, src_idx, seg_ptr, out):
     if (out.shape[0], out.shape[2], out.shape[3]) != (B, C, L) or seg_ptr.numel() != J + 1:
         raise ValueError(f"gather_sum: output {tuple(out.shape)} / {seg_ptr.numel() - 1} segments do not match the "
                          f"buffer {tuple(buf.shape)}")
+    if J * C > GRID_YZ_MAX:
+        raise ValueError(f"gather_sum: {J} destinations x {C} channels ride on one grid dimension, at most {GRID_YZ_MAX}")
     with _timed("gather_sum_kernel", 4 * B * C * L * (src_idx.numel() + J)):
-        check(
-            lib().gfx_gather_sum_f32(_ptr(buf), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(src_idx), _ptr(seg_ptr),
-                                     _ptr(out), out.stride(0), out.stride(1), out.stride(2), B, J, C, L, _stream()),
-            "gfx_gather_sum_f32",
-        )
+        for b0 in range(0, B, GRID_YZ_MAX):     # the batch rides on a grid dimension: slices keep the views' strides
+            bs, os_ = buf[b0 : b0 + GRID_YZ_MAX], out[b0 : b0 + GRID_YZ_MAX]
+            check(
+                lib().gfx_gather_sum_f32(_ptr(bs), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(src_idx), _ptr(seg_ptr),
+                                         _ptr(os_), out.stride(0), out.stride(1), out.stride(2), bs.shape[0], J, C, L,
+                                         _stream()),
+                "gfx_gather_sum_f32",
+            )
     return out
 
 
@@ -1268,7 +1277,15 @@ def gather_sum_fanout(buf, unique_src, dest_mask, out):
     if (out.shape[0], out.shape[2], out.shape[3]) != (B, C, L) or dest_mask.numel() != unique_src.numel():
         raise ValueError(f"gather_sum_fanout: output {tuple(out.shape)} does not match the buffer {tuple(buf.shape)}")
     with _timed("gather_sum_kernel", 4 * B * C * L * (unique_src.numel() + J)):
-        code = lib().gfx_gather_sum_fanout_f32(_ptr(buf), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(unique_src),
-                                               _ptr(dest_mask), unique_src.numel(), _ptr(out), out.stride(0),
-                                               out.stride(1), out.stride(2), B, J, C, L, _stream())
-    return code == 0
+        # the batch rides on a grid dimension; what the kernel refuses (alignment, J, C) it refuses for every slice alike,
+        # so a refusal can only come from the first one, before anything is written
+        for b0 in range(0, B, GRID_YZ_MAX):
+            bs, os_ = buf[b0 : b0 + GRID_YZ_MAX], out[b0 : b0 + GRID_YZ_MAX]
+            code = lib().gfx_gather_sum_fanout_f32(_ptr(bs), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(unique_src),
+                                                   _ptr(dest_mask), unique_src.numel(), _ptr(os_), out.stride(0),
+                                                   out.stride(1), out.stride(2), bs.shape[0], J, C, L, _stream())
+            if code != 0:
+                if b0 == 0:
+                    return False
+                check(code, "gfx_gather_sum_fanout_f32")
+    return True
