@@ -1,5 +1,5 @@
 // The gain computer of the dynamics processors (Compressor / NoiseGate knees, reference dynamics.py:444-489, 676-721) and
-// the hardware log / exp forms the forward kernels use -- shared by dynamics.hip and ballistics.hip.
+// the hardware log / exp forms the forward kernels use -- shared by the dynamics files (through dyn_common.hpp) and ballistics.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void gather_sum_fanout_kernel(const float* __r
 }
 
 // StereoGain (stereo.py:25-48: y[r,c,n] = x[r,cx,n] exp(log_gain[r,c])) with the routing sum that follows fused in -- the
-// gain / pan stage in front of a bus, the elementwise twin of dyn_oneshot_mix_kernel (dynamics.hip: same schedule words,
+// gain / pan stage in front of a bus, the elementwise twin of dyn_oneshot_mix_kernel (dynamics.hip, see MixArgs there: same schedule words,
 // same extras, same increasing summation order, bit-identical sums).  One thread per 16-byte column of a graph: it walks
 // the `inner` rows, scales, stores the row and adds it to the accumulators of the destinations the row feeds.
 struct GainMixArgs {

@@ -792,31 +792,27 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     gp = torch.empty((R, 3), dtype=torch.float32, device=x.device)
     da = torch.empty(R, dtype=torch.float32, device=x.device) if pole else None
     pin = _Pin()
-    if u1 is not None:
+    # three paths: the kept scan (with or without the tiles' workspace), the rescan inside the tiles, the plain two passes
+    kept = u1 is not None
+    if kept:
         _require_gpu(u1)
         _expect(u1, (R, L), "dynamics_bwd: u1")
-        ws = None
-        if (DYN_SCHEDULE if schedule is None else schedule) == "oneshot":   # one-shot tiles for the short-memory rows
-            ws = torch.empty(lib().gfx_dynamics_bwd_ws_bytes(R, L), dtype=torch.uint8, device=x.device)
-        check(lib().gfx_dynamics_bwd_u1_ws_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)),
-                                               pin(_rowvec(log_ratio, R)), pin(_rowvec(log_knee, R)),
-                                               pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee], int(gate), _ptr(gx),
-                                               rowmap(gx)[0], _ptr(gp), pin(u1), _ptr(da), _ptr(ws),
-                                               0 if ws is None else ws.numel(), _stream()), "gfx_dynamics_bwd_u1_ws_f32")
-        return gx, gp, da
-    u1 = torch.empty((R, L), dtype=torch.float32, device=x.device)
-    if DYN_BWD_RESCAN if rescan is None else rescan:
-        ws = torch.empty(lib().gfx_dynamics_bwd_ws_bytes(R, L), dtype=torch.uint8, device=x.device)
-        check(lib().gfx_dynamics_bwd_rescan_ws_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)),
-                                                   pin(_rowvec(log_ratio, R)), pin(_rowvec(log_knee, R)),
-                                                   pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee], int(gate),
-                                                   _ptr(gx), rowmap(gx)[0], _ptr(gp), _ptr(u1), _ptr(da), _ptr(ws), ws.numel(),
-                                                   _stream()), "gfx_dynamics_bwd_rescan_ws_f32")
-        return gx, gp, da
-    check(lib().gfx_dynamics_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)),
-                                     pin(_rowvec(log_ratio, R)), pin(_rowvec(log_knee, R)), pin(_rowvec(z_alpha, R)),
-                                     R, C, L, iir_len, KNEES[knee], int(gate), _ptr(gx), rowmap(gx)[0], _ptr(gp), None,
-                                     _ptr(u1), _ptr(da), _stream()), "gfx_dynamics_bwd_f32")
+        need_ws = (DYN_SCHEDULE if schedule is None else schedule) == "oneshot"   # one-shot tiles for the short-memory rows
+    else:
+        u1 = torch.empty((R, L), dtype=torch.float32, device=x.device)
+        need_ws = rescan = bool(DYN_BWD_RESCAN if rescan is None else rescan)   # (the rescan entry always takes a workspace)
+    ws = torch.empty(lib().gfx_dynamics_bwd_ws_bytes(R, L), dtype=torch.uint8, device=x.device) if need_ws else None
+    args = (_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)), pin(_rowvec(log_ratio, R)),
+            pin(_rowvec(log_knee, R)), pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee], int(gate), _ptr(gx),
+            rowmap(gx)[0], _ptr(gp))
+    if kept:
+        check(lib().gfx_dynamics_bwd_u1_ws_f32(*args, pin(u1), _ptr(da), _ptr(ws), 0 if ws is None else ws.numel(),
+                                               _stream()), "gfx_dynamics_bwd_u1_ws_f32")
+    elif rescan:
+        check(lib().gfx_dynamics_bwd_rescan_ws_f32(*args, _ptr(u1), _ptr(da), _ptr(ws), ws.numel(), _stream()),
+              "gfx_dynamics_bwd_rescan_ws_f32")
+    else:
+        check(lib().gfx_dynamics_bwd_f32(*args, None, _ptr(u1), _ptr(da), _stream()), "gfx_dynamics_bwd_f32")
     return gx, gp, da
 
 

@@ -1,4 +1,4 @@
-"""The compressor's smoother with a LONG memory on the tile grid (csrc/dynamics.hip, "look-back" tiles, round 5).
+"""The compressor's smoother with a LONG memory on the tile grid (csrc/dynamics.hip, the forward; "look-back" tiles, round 5).
 
 Round 4's dependency-free tiles took a row only if its smoother forgot within 256 samples (a <= 0.898); every slower
 pole went to one workgroup per row, and in a fused routing sum those rows were written and read back.  Now a tile whose

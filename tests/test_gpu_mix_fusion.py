@@ -136,7 +136,6 @@ def test_console_render_with_and_without_the_fused_mix(train):
     x = torch.randn(B, 8, 2, L, device=dev)
     params = {t: {k: v.detach().to(dev) for k, v in d.items()} for t, d in create_empty_parameters(procs, G, std=0.1).items()}
     outs, seen = {}, {}
-    real = ops.lib().gfx_dynamics_fused_mix_f32
     for flag in (True, False):
         ops.MIX_FUSION = flag
         try:

@@ -1,4 +1,4 @@
-"""Time of the ballistics recursion (csrc/ballistics.hip) at the console's sizes:
+"""Time of the ballistics recursion (csrc/ballistics.hip) and of its adjoint (csrc/ballistics_bwd.hpp) at the console's sizes:
    python tools/ballistics_bench.py [--rows 9216 1024 256] [--length 131072] [--iters 5] [--old-lib grafx_amd/lib/r4base.so]
 -> ms per call and GB/s over the algorithmic bytes (read every input sample once, write every output sample once), for
    * z ~ randn * 0.1 (bench.py's parameter scale: coefficients ~ 0.5, rows cut into verified chunks),
