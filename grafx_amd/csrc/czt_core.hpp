@@ -12,25 +12,9 @@
 
 namespace gfx {
 
-// the workspace streams through every pass once: non-temporal accesses keep it from evicting what IS reused (the chirp
-// spectrum, the twiddle tables).  -DGFX_CZT_NT=0 for A/B.
-#ifndef GFX_CZT_EARLY_SPEC_F64
-#define GFX_CZT_EARLY_SPEC_F64 0
-#endif
-#ifndef GFX_CZT_EARLY_SPEC
-#define GFX_CZT_EARLY_SPEC 1
-#endif
-#ifndef GFX_CZT_NT
-#define GFX_CZT_NT 1
-#endif
-#if GFX_CZT_NT
-#define GFX_CZT_LOAD(p) __builtin_nontemporal_load(p)
-#define GFX_CZT_STORE(v, p) __builtin_nontemporal_store(v, p)
-#else
-#define GFX_CZT_LOAD(p) (*(p))
-#define GFX_CZT_STORE(v, p) (*(p) = (v))
-#endif
-
+// the workspace streams through every pass once: non-temporal accesses (__builtin_nontemporal_*, or these aux bits on a
+// descriptor access) keep it from evicting what IS reused (the chirp spectrum, the twiddle tables)
+constexpr int CZT_NT = 2;
 
 constexpr int CZT_MAXC = 32;
 // tiles per (sub-)transform: every size up to 32 with prime factors up to 7 (czt_geom picks the smallest that covers P)
@@ -43,14 +27,12 @@ template <typename T> struct Prec;
 template <> struct Prec<float> {
     using cxt = cx;
     using T2 = float2;
-    using Tw = TileTw;
     static constexpr int lds_bytes = TILE_LDS_BYTES;
     static __device__ __forceinline__ T2 make(float x, float y) { return make_float2(x, y); }
 };
 template <> struct Prec<double> {
     using cxt = cxd;
     using T2 = double2;
-    using Tw = TileTwD;
     static constexpr int lds_bytes = TILE_LDS_BYTES_F64;
     static __device__ __forceinline__ T2 make(double x, double y) { return make_double2(x, y); }
 };
@@ -140,11 +122,11 @@ template <int AUX> __device__ __forceinline__ void tile_st(__amdgpu_buffer_rsrc_
 // the workspace's points in the column passes (T2 in memory, the tile's complex type in registers)
 template <typename T>
 __device__ __forceinline__ typename Prec<T>::cxt buf_load(const typename Prec<T>::T2* p) {
-    return GFX_CZT_LOAD(reinterpret_cast<const typename Prec<T>::cxt*>(p));
+    return __builtin_nontemporal_load(reinterpret_cast<const typename Prec<T>::cxt*>(p));
 }
 template <typename T>
 __device__ __forceinline__ void buf_store(typename Prec<T>::T2* p, typename Prec<T>::cxt v) {
-    GFX_CZT_STORE(v, reinterpret_cast<typename Prec<T>::cxt*>(p));
+    __builtin_nontemporal_store(v, reinterpret_cast<typename Prec<T>::cxt*>(p));
 }
 
 // A column pass's view of one transform's points: point (k1, n2) = b[k1 * 8192 + n2].  float: through a descriptor (lane
@@ -152,21 +134,20 @@ __device__ __forceinline__ void buf_store(typename Prec<T>::T2* p, typename Prec
 // point, in kernels that are bound by vector-memory issue and the vector ALU; double: global accesses (measured equal).
 template <typename T> struct ColBuf {
     using cx = typename Prec<T>::cxt;
-    static constexpr int NT = GFX_CZT_NT ? 2 : 0;
     typename Prec<T>::T2* b;
     __amdgpu_buffer_rsrc_t r;
     __device__ __forceinline__ ColBuf(const typename Prec<T>::T2* base, int64_t points)
         : b(const_cast<typename Prec<T>::T2*>(base)), r(tile_rsrc(base, (uint32_t)(points * (int64_t)sizeof(typename Prec<T>::T2)))) {}
     __device__ __forceinline__ cx ld(int k1, int n2) const {
         if constexpr (sizeof(T) == 4)
-            return __builtin_bit_cast(cx, __builtin_amdgcn_raw_buffer_load_b64(r, 8u * (uint32_t)n2, (uint32_t)k1 * (TILE_M * 8u), NT));
+            return __builtin_bit_cast(cx, __builtin_amdgcn_raw_buffer_load_b64(r, 8u * (uint32_t)n2, (uint32_t)k1 * (TILE_M * 8u), CZT_NT));
         else
             return buf_load<T>(&b[(int64_t)k1 * TILE_M + n2]);
     }
     __device__ __forceinline__ void st(int k1, int n2, cx v) const {
         if constexpr (sizeof(T) == 4) {
             using u2 = unsigned __attribute__((ext_vector_type(2)));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, 8u * (uint32_t)n2, (uint32_t)k1 * (TILE_M * 8u), NT);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, 8u * (uint32_t)n2, (uint32_t)k1 * (TILE_M * 8u), CZT_NT);
         } else {
             buf_store<T>(&b[(int64_t)k1 * TILE_M + n2], v);
         }
@@ -295,50 +276,53 @@ __global__ __launch_bounds__(256) void czt_cols_fwd_kernel(const float* __restri
 
 // One tile per (row, k1): forward, times the chirp spectrum, inverse -- in place.  PLAN: forward only, spectrum stored
 // in thread layout.
+// float: the twiddles live through the tile, the spectrum is loaded up front and the tile goes through a descriptor (10.1
+// -> 9.3 ms per 4096 rows).  double: the split tile (fft_tile_f64.hpp: exchanges in two rounds, twiddles fetched per pass),
+// the spectrum eight values at a time and global accesses to the tile (measured 1 % better than the descriptor form).
 template <typename T, bool PLAN>
-__global__ __launch_bounds__(TILE_T, (sizeof(T) == 4 || GFX_F64_SPLIT) ? 2 : 1) void czt_rows_kernel(
+__global__ __launch_bounds__(TILE_T, 2) void czt_rows_kernel(
     typename Prec<T>::T2* __restrict__ buf, const typename Prec<T>::T2* __restrict__ spec,
     typename Prec<T>::T2* __restrict__ spec_out, int C, const typename Prec<T>::T2* __restrict__ twtab) {
     using cx = typename Prec<T>::cxt;
+    constexpr bool F32 = sizeof(T) == 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     cx* lds = reinterpret_cast<cx*>(lds_raw);
     const int t = threadIdx.x;
     const int64_t tile = blockIdx.x;                    // row * C + k1
     const int k1 = (int)(tile % C);                       // C here = tiles per signal row = S * C
     constexpr uint32_t TILE_BYTES = TILE_M * sizeof(cx);
-    constexpr int NT = GFX_CZT_NT ? 2 : 0;
     const __amdgpu_buffer_rsrc_t rb = tile_rsrc(reinterpret_cast<cx*>(buf) + tile * TILE_M, TILE_BYTES);
-    constexpr bool SPLIT = sizeof(T) == 8 && GFX_F64_SPLIT;     // (fft_tile_f64.hpp: exchanges in two rounds, twiddles per pass)
-    typename Prec<T>::Tw tw;
-    if constexpr (!SPLIT) tile_twiddles(tw, twtab, t);
+    TileTw tw;
+    if constexpr (F32) tile_twiddles(tw, twtab, t);
     cx v[32], w[2][16];
-    // (descriptor accesses in float: 10.1 -> 9.3 ms per 4096 rows; in double the global form measured 1 % better)
     cx* b = reinterpret_cast<cx*>(buf) + tile * TILE_M;
 #pragma unroll
     for (int a = 0; a < 32; ++a) {
-        if constexpr (sizeof(T) == 4) v[a] = tile_ld<NT>(rb, t, a, (cx*)nullptr);
-        else v[a] = GFX_CZT_LOAD(&b[t + 256 * a]);
+        if constexpr (F32) v[a] = tile_ld<CZT_NT>(rb, t, a, (cx*)nullptr);
+        else v[a] = __builtin_nontemporal_load(&b[t + 256 * a]);
     }
     // float: the spectrum's loads go out with the tile's, up front, as in fftconv1_kernel -- left to itself the compiler
     // issues each one right before its product and waits for it, 32 L2 round trips in the middle of the tile (in double the
     // 128 registers are not there)
-    constexpr bool EARLY = !PLAN && (sizeof(T) == 4 || GFX_CZT_EARLY_SPEC_F64) && GFX_CZT_EARLY_SPEC;
-    cx sreg[EARLY ? 32 : 1];
+    cx sreg[32];
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(reinterpret_cast<const cx*>(spec) + (PLAN ? 0 : (int64_t)k1 * TILE_M), TILE_BYTES);
-    if constexpr (EARLY) {
+    if constexpr (F32 && !PLAN) {
 #pragma unroll
         for (int q = 0; q < 32; ++q) sreg[q] = tile_ld<0>(rs, t, q, (cx*)nullptr);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (SPLIT) tile_forward(v, w, twtab, lds, t);
-    else tile_forward(v, w, tw, lds, t);
+    if constexpr (F32) tile_forward(v, w, tw, lds, t);
+    else tile_forward(v, w, twtab, lds, t);
     if (PLAN) {
         cx* o = reinterpret_cast<cx*>(spec_out) + (int64_t)k1 * TILE_M;
 #pragma unroll
         for (int q = 0; q < 32; ++q) o[q * TILE_T + t] = w[q >> 4][q & 15];
         return;
     }
-    if constexpr (SPLIT) {
+    if constexpr (F32) {
+#pragma unroll
+        for (int q = 0; q < 32; ++q) w[q >> 4][q & 15] = cmul(w[q >> 4][q & 15], sreg[q]);
+    } else {
         // eight spectrum values at a time, fenced: left to itself the scheduler requests all 32 (128 registers) on top of the
         // 128 of the tile, and at two workgroups per CU there are 256 in all
 #pragma unroll
@@ -351,18 +335,14 @@ __global__ __launch_bounds__(TILE_T, (sizeof(T) == 4 || GFX_F64_SPLIT) ? 2 : 1) 
             for (int q = 0; q < 8; ++q) w[(8 * g + q) >> 4][(8 * g + q) & 15] = cmul(w[(8 * g + q) >> 4][(8 * g + q) & 15], sp[q]);
         }
         __builtin_amdgcn_sched_barrier(0);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 32; ++q)
-            w[q >> 4][q & 15] = cmul(w[q >> 4][q & 15], EARLY ? sreg[EARLY ? q : 0] : tile_ld<0>(rs, t, q, (cx*)nullptr));
     }
     __syncthreads();
-    if constexpr (SPLIT) tile_inverse(w, v, twtab, lds, t);
-    else tile_inverse(w, v, tw, lds, t);
+    if constexpr (F32) tile_inverse(w, v, tw, lds, t);
+    else tile_inverse(w, v, twtab, lds, t);
 #pragma unroll
     for (int a = 0; a < 32; ++a) {
-        if constexpr (sizeof(T) == 4) tile_st<NT>(rb, t, a, v[brev(a, 5)]);
-        else GFX_CZT_STORE(v[brev(a, 5)], &b[t + 256 * a]);
+        if constexpr (F32) tile_st<CZT_NT>(rb, t, a, v[brev(a, 5)]);
+        else __builtin_nontemporal_store(v[brev(a, 5)], &b[t + 256 * a]);
     }
 }
 

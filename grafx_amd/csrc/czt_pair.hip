@@ -31,11 +31,7 @@
 namespace gfx {
 
 constexpr int CZT_PAIR_MAXC = 63;
-#ifdef GFX_PAIR_DEV_SIZES
-#define GFX_CZT_PAIR_SIZES(X) X(2) X(3) X(35) X(36) X(48)
-#else
 #define GFX_CZT_PAIR_SIZES(X) GFX_CZT_SIZES(X) X(35) X(36) X(40) X(42) X(45) X(48) X(49) X(50) X(54) X(56) X(60) X(63)
-#endif
 
 // the middle pass keeps two columns of C points in registers when fused with the next column pass: above 48 tiles (36 in
 // double precision) that no longer fits two waves per SIMD and it goes in two passes instead (one more sweep over the buffer)
@@ -801,8 +797,7 @@ static int czt_pair_alias(const float* z, float* y, int64_t ldy, int64_t lo, int
         g.rmax = rmax ? rmax + 2 * p0 : nullptr;
         if (g.levels > 0) {
             if constexpr (sizeof(T) == 4) {
-                static const bool fused = [] { const char* e = getenv("GRAFX_CZT_FUSED_LEVEL"); return !(e && e[0] == '0'); }();
-                if (g.levels == 1 && fused) {
+                if (g.levels == 1) {   // one outer level in float: the fused chain
                     int rc = GFX_EINVAL;
 #define GFX_PL(CC) case CC: rc = pair_chain_one_level<T, CC>(g, zc, yc, ldy, lo, len, n, cP, cQ, mid, spec, buf, tw, st); break;
                     switch (g.C) { GFX_CZT_SIZES(GFX_PL) default: break; }

@@ -11,18 +11,12 @@
 #include "../../include/grafx_amd.h"
 #include "dyn_gain.hpp"
 
-#ifdef GFX_NT_OFF
-#define GFX_NT_STORE(...) gfx_plain_store(__VA_ARGS__)
-template <typename T> __device__ __forceinline__ void gfx_plain_store(T v, T* p) { *p = v; }
-#else
-#define GFX_NT_STORE(...) __builtin_nontemporal_store(__VA_ARGS__)
-#endif
-
 namespace gfx {
 
 constexpr int DT = 256;            // threads per workgroup
 constexpr int DE = 4;              // samples per thread per tile
 constexpr int DTILE = DT * DE;     // 1024 samples per tile
+constexpr int OS_HMAX = 256;       // taps of history a one-shot tile may re-read (tile: 1024 samples)
 // per-parameter-row pole table (dyn_pole_table_kernel), floats per row:
 //   a^(4 l) l < 64 | a_step[6] | a_wave | a_N | ap[0..4] | a | 1 - a | trunc | one-shot | H | look-back | M | a^(512 i) i < 64
 constexpr int DP_TAB = 148;
@@ -121,7 +115,7 @@ __device__ __forceinline__ void load4(const float* __restrict__ row, int64_t n, 
 __device__ __forceinline__ void store4(float* __restrict__ row, int64_t n, int64_t L, bool vec, const float (&v)[DE]) {
     if (vec && n + DE <= L) {
         using f4 = float __attribute__((ext_vector_type(4)));
-        GFX_NT_STORE(f4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4*>(row + n));  // streamed output
+        __builtin_nontemporal_store(f4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4*>(row + n));  // streamed output
     } else {
 #pragma unroll
         for (int i = 0; i < DE; ++i)
@@ -145,7 +139,7 @@ template <bool AL>
 __device__ __forceinline__ void st4(float* __restrict__ row, int64_t n, int64_t L, bool vec, const float (&v)[DE]) {
     if (AL) {
         using f4 = float __attribute__((ext_vector_type(4)));
-        if (n < L) GFX_NT_STORE(f4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4*>(row + n));
+        if (n < L) __builtin_nontemporal_store(f4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4*>(row + n));
     } else {
         store4(row, n, L, vec, v);
     }

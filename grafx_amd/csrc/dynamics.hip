@@ -120,10 +120,7 @@ __device__ __forceinline__ void dyn_stream(const DynArgs& a, const OnePole& p, c
     }
 }
 
-#ifndef GFX_DYN_WAVES
-#define GFX_DYN_WAVES 1
-#endif
-__global__ __launch_bounds__(DT, GFX_DYN_WAVES) void dyn_fused_kernel(const float* __restrict__ x, float* __restrict__ y,
+__global__ __launch_bounds__(DT, 1) void dyn_fused_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                        const float* __restrict__ log_threshold,
                                                        const float* __restrict__ log_ratio,
                                                        const float* __restrict__ log_knee,
@@ -169,12 +166,8 @@ __global__ __launch_bounds__(DT, GFX_DYN_WAVES) void dyn_fused_kernel(const floa
 // with H the number of taps above 1e-12.  A tile re-reads those H samples (lane l takes taps 4l .. 4l+3 as one
 // predicated 16-byte load per channel) and reduces them with six shuffles: no LDS, no barrier.
 // Which rows qualify is decided ON THE DEVICE from the pole table (no host synchronisation): a row is taken here when its
-// truncation term is dead (a^N <= 1e-12) and H <= DYN_OS_HMAX; every other row leaves this grid at once and is produced
+// truncation term is dead (a^N <= 1e-12) and H <= OS_HMAX; every other row leaves this grid at once and is produced
 // by dyn_fused_kernel, launched over the same rows with the complementary test.
-#ifndef GFX_DYN_OS_HMAX
-#define GFX_DYN_OS_HMAX 256   // taps of history a one-shot tile may re-read (tile: 1024 samples)
-#endif
-
 // `any_lb` (nullable): set to 1 when some row takes the look-back tiles -- only then do the tile grids draw tickets
 // (see LbArgs); without it no row is given to the look-back (the backward pass, callers without the larger workspace).
 __global__ void dyn_pole_table_kernel(const float* __restrict__ z_alpha, float* __restrict__ tab, int64_t rows, int64_t N,
@@ -203,7 +196,7 @@ __global__ void dyn_pole_table_kernel(const float* __restrict__ z_alpha, float* 
         // history (up to 64 tiles of 512 samples) the tiles get their entry state from their predecessors' aggregates
         const double h = ceil(-27.631021115928547 / la);
         const bool dead = h <= (double)N;
-        const bool os = dead && h <= (double)GFX_DYN_OS_HMAX;
+        const bool os = dead && h <= (double)OS_HMAX;
         const double m = ceil(h / 512.0);
         const bool lb = any_lb != nullptr && dead && !os && m <= 64.0;
         t[DP_ONESHOT] = os ? 1.0f : 0.0f;
@@ -224,7 +217,7 @@ struct OsIn {
     float xa[OS_SUB][DE], xb[OS_SUB][DE], ha[DE], hb[DE];
 };
 
-// LOOK-BACK tiles (round 5): a smoother memory longer than the history a tile may re-read (H > GFX_DYN_OS_HMAX samples,
+// LOOK-BACK tiles (round 5): a smoother memory longer than the history a tile may re-read (H > OS_HMAX samples,
 // up to 64 tiles) does not send the row to the row kernel any more.  The scan is linear, so the state entering tile j is
 //     u[s - 1] = sum_{i >= 1} a^(512 (i - 1)) A[j - i],      A[t] = the state tile t leaves from a ZERO entry state,
 // and A[t] depends on tile t's own samples only: every tile publishes its aggregate as soon as its local scans are done
@@ -524,13 +517,10 @@ struct MixArgs {
 // (and the element-wise tail paths of load4 / store4) inlined it is 6 k instructions, more than the instruction cache holds
 // -- 5.0 ms for 8192 rows where this form takes 3.3-3.5.  Requesting rows ahead of the one being scanned was measured too
 // (register rings of 2-4 rows): slower at every depth, the registers cost more waves than the loads in flight gain
-// (EXPERIMENTS.md).
-#ifndef GFX_DEFER_WAVES
-#define GFX_DEFER_WAVES 1     // waves per SIMD the deferred walk is compiled for: left to the compiler (155 VGPRs, three waves,
-                              // 4.19 ms for the 8192-row stage at a = 0.9975); 4 forces 128 VGPRs and 84 bytes of scratch: 4.31 ms
-#endif
+// (EXPERIMENTS.md).  The waves per SIMD are left to the compiler: the deferred walk takes 155 VGPRs, three waves, 4.19 ms for
+// the 8192-row stage at a = 0.9975; forced to four waves it is 128 VGPRs and 84 bytes of scratch, 4.31 ms.
 template <int NA, bool STEREO, int KIND, bool GATE, bool DEFER>
-__global__ __launch_bounds__(DT, (DEFER && NA <= 2) ? GFX_DEFER_WAVES : 1) void dyn_oneshot_mix_kernel(const float* __restrict__ x, float* __restrict__ y,
+__global__ __launch_bounds__(DT, 1) void dyn_oneshot_mix_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                              const float* __restrict__ log_threshold,
                                                              const float* __restrict__ log_ratio,
                                                              const float* __restrict__ log_knee,

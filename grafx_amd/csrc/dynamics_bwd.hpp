@@ -4,10 +4,6 @@
 #pragma once
 #include "dyn_common.hpp"
 
-#ifndef GFX_DYN_BWD_FAST
-#define GFX_DYN_BWD_FAST true     // hardware log / exp / reciprocal in the backward tiles (false: the library functions)
-#endif
-
 namespace gfx {
 
 // ---- backward of the gain computer (training path of Compressor / NoiseGate) --------------------------------
@@ -148,7 +144,8 @@ __global__ __launch_bounds__(DT) void dyn_bwd_u1_kernel(const float* __restrict_
 // dL/d(smoothed energy) at four (reversed-walk) positions from the samples, output gradients and scan values there;
 // also returns the gain and, when `acc` is given, adds the parameter-gradient terms.
 // (A: float in the tiles -- eight terms per thread and launch, the sums continue in double --, double in the row kernel, where
-// a thread adds hundreds of terms of both signs)
+// a thread adds hundreds of terms of both signs; FAST: hardware log / exp / reciprocal in the tiles, the library functions in
+// the row kernel)
 template <bool FAST = false, typename A = float>
 __device__ __forceinline__ void dyn_denv4(const DynArgs& a, const Knee& q, const float (&xa)[DE], const float (&xb)[DE],
                                           const float (&ga)[DE], const float (&gb)[DE], const float (&lin)[DE],
@@ -476,7 +473,7 @@ __global__ __launch_bounds__(DT, 3) void dyn_bwd_oneshot_kernel(const float* __r
     float d[OS_SUB][DE], gn[OS_SUB][DE], loc[OS_SUB][DE], excl[OS_SUB], total[OS_SUB];
 #pragma unroll
     for (int k = 0; k < OS_SUB; ++k) {
-        dyn_denv4<GFX_DYN_BWD_FAST>(a, q, xa[k], xb[k], ga[k], gb[k], uu[k], d[k], gn[k], acc);
+        dyn_denv4<true>(a, q, xa[k], xb[k], ga[k], gb[k], uu[k], d[k], gn[k], acc);
         float run = 0.0f;
 #pragma unroll
         for (int i = 0; i < DE; ++i) {
@@ -496,7 +493,7 @@ __global__ __launch_bounds__(DT, 3) void dyn_bwd_oneshot_kernel(const float* __r
     float carry = 0.0f;
     if (s != 0 && H > 0) {                       // uniform
         float hd[DE], hgn[DE];
-        dyn_denv4<GFX_DYN_BWD_FAST>(a, q, hxa, hxb, hga, hgb, hu, hd, hgn, (float*)nullptr);   // (lanes without a live tap hold zeros: denv = 0)
+        dyn_denv4<true>(a, q, hxa, hxb, hga, hgb, hu, hd, hgn, (float*)nullptr);   // (lanes without a live tap hold zeros: denv = 0)
         float w = 0.0f;                          // Horner, farthest walk position first
 #pragma unroll
         for (int i = 0; i < DE; ++i) w = fmaf(a1, w, hd[i]);

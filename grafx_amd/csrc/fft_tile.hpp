@@ -123,15 +123,49 @@ __device__ __forceinline__ cx tw32_sub(cx a, cx b, int idx32) {
     return tw32<INV>(a - b, idx32);
 }
 
+// ---- the same in double precision (fft_tile_f64.hpp): plain v_fma_f64 arithmetic ------------------------------
+using cxd = double __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ cxd to_cx(double2 a) { return cxd{a.x, a.y}; }
+__device__ __forceinline__ cxd cadd(cxd a, cxd b) { return a + b; }
+__device__ __forceinline__ cxd cmul(cxd a, cxd w) { return cxd{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
+__device__ __forceinline__ cxd cmulc(cxd a, cxd w) { return cxd{a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y}; }
+__device__ __forceinline__ cxd mul_neg_i(cxd a) { return cxd{a.y, -a.x}; }
+__device__ __forceinline__ cxd mul_pos_i(cxd a) { return cxd{-a.y, a.x}; }
+
+__device__ constexpr double kCos32d[16] = {
+    1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708,
+    0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785,
+    0.0, -0.19509032201612826785, -0.38268343236508977173, -0.55557023301960222474,
+    -0.70710678118654752440, -0.83146961230254523708, -0.92387953251128675613, -0.98078528040323044913};
+__device__ constexpr double kSin32d[16] = {
+    0.0, 0.19509032201612826785, 0.38268343236508977173, 0.55557023301960222474,
+    0.70710678118654752440, 0.83146961230254523708, 0.92387953251128675613, 0.98078528040323044913,
+    1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708,
+    0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785};
+
+template <bool INV>
+__device__ __forceinline__ cxd tw32(cxd d, int idx32) {
+    if (idx32 == 0) return d;
+    if (idx32 == 16) return -d;
+    if (idx32 == 8) return INV ? mul_pos_i(d) : mul_neg_i(d);
+    if (idx32 == 24) return INV ? mul_neg_i(d) : mul_pos_i(d);
+    const double sg = idx32 >= 16 ? -1.0 : 1.0;
+    const double c = sg * kCos32d[idx32 & 15], s = sg * (INV ? kSin32d[idx32 & 15] : -kSin32d[idx32 & 15]);
+    return cxd{d.x * c - d.y * s, d.y * c + d.x * s};
+}
+template <bool INV>
+__device__ __forceinline__ cxd tw32_sub(cxd a, cxd b, int idx32) { return tw32<INV>(a - b, idx32); }
+
 constexpr __host__ __device__ int brev(int v, int bits) {
     int r = 0;
     for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1) << (bits - 1 - i);
     return r;
 }
 
-// In-register radix-2 DIF DFT of N (16 or 32) points; result for frequency k is at v[brev(k)].
-template <int N, bool INV>
-__device__ __forceinline__ void dif(cx (&v)[N]) {
+// In-register radix-2 DIF DFT of N points (V: cx or cxd); result for frequency k is at v[brev(k)].
+template <int N, bool INV, typename V>
+__device__ __forceinline__ void dif(V (&v)[N]) {
 #pragma unroll
     for (int len = N; len >= 2; len >>= 1) {
         const int half = len >> 1;
@@ -139,7 +173,7 @@ __device__ __forceinline__ void dif(cx (&v)[N]) {
         for (int base = 0; base < N; base += len) {
 #pragma unroll
             for (int j = 0; j < half; ++j) {
-                const cx a = v[base + j], b = v[base + j + half];
+                const V a = v[base + j], b = v[base + j + half];
                 v[base + j] = cadd(a, b);
                 v[base + j + half] = tw32_sub<INV>(a, b, j * (32 / len));
             }
@@ -149,23 +183,25 @@ __device__ __forceinline__ void dif(cx (&v)[N]) {
 
 // Per-thread twiddles, kept two-level to save VGPRs: W^(t*k1) = lo[k1 & 3] * hi[k1 >> 2]
 // (one extra complex multiply per use, one extra rounding ~6e-8).
-struct TileTw {
-    cx lo1[4], hi1[8];  // W_8192^(t*i), W_8192^(t*4i)
-    cx lo2[4], hi2[4];  // W_256^(d*i),  W_256^(d*4i), d = t & 15
+template <typename V> struct TileTwT {   // V: cx or cxd
+    V lo1[4], hi1[8];  // W_8192^(t*i), W_8192^(t*4i)
+    V lo2[4], hi2[4];  // W_256^(d*i),  W_256^(d*4i), d = t & 15
 
-    __device__ __forceinline__ cx fwd1(cx e, int k1) const { return apply<false>(e, lo1[k1 & 3], hi1[k1 >> 2], k1 & 3, k1 >> 2); }
-    __device__ __forceinline__ cx inv1(cx e, int k1) const { return apply<true>(e, lo1[k1 & 3], hi1[k1 >> 2], k1 & 3, k1 >> 2); }
-    __device__ __forceinline__ cx fwd2(cx e, int k2) const { return apply<false>(e, lo2[k2 & 3], hi2[k2 >> 2], k2 & 3, k2 >> 2); }
-    __device__ __forceinline__ cx inv2(cx e, int k2) const { return apply<true>(e, lo2[k2 & 3], hi2[k2 >> 2], k2 & 3, k2 >> 2); }
-    __device__ __forceinline__ cx base() const { return lo1[1]; }  // W_8192^t
+    __device__ __forceinline__ V fwd1(V e, int k1) const { return apply<false>(e, lo1[k1 & 3], hi1[k1 >> 2], k1 & 3, k1 >> 2); }
+    __device__ __forceinline__ V inv1(V e, int k1) const { return apply<true>(e, lo1[k1 & 3], hi1[k1 >> 2], k1 & 3, k1 >> 2); }
+    __device__ __forceinline__ V fwd2(V e, int k2) const { return apply<false>(e, lo2[k2 & 3], hi2[k2 >> 2], k2 & 3, k2 >> 2); }
+    __device__ __forceinline__ V inv2(V e, int k2) const { return apply<true>(e, lo2[k2 & 3], hi2[k2 >> 2], k2 & 3, k2 >> 2); }
+    __device__ __forceinline__ V base() const { return lo1[1]; }  // W_8192^t
 
     template <bool CONJ>
-    static __device__ __forceinline__ cx apply(cx e, cx lo, cx hi, int il, int ih) {
+    static __device__ __forceinline__ V apply(V e, V lo, V hi, int il, int ih) {
         if (il == 0 && ih == 0) return e;
-        const cx w = il == 0 ? hi : (ih == 0 ? lo : cmul(lo, hi));
+        const V w = il == 0 ? hi : (ih == 0 ? lo : cmul(lo, hi));
         return CONJ ? cmulc(e, w) : cmul(e, w);
     }
 };
+using TileTw = TileTwT<cx>;
+using TileTwD = TileTwT<cxd>;
 
 __device__ __forceinline__ float2 unit_root(int num, float inv_half_den) {
     // exp(-2*pi*i*num/den), 2/den = inv_half_den (a power of two, so the argument is exact)

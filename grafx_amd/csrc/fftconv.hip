@@ -108,12 +108,10 @@ __device__ __forceinline__ f4v buf_load_f4(rsrc_t r, uint32_t voff, uint32_t sof
 // outputs are streamed: written once, read by a later stage long after they left the 4 MB L2s.  The
 // non-temporal hint keeps them from evicting the window overlaps and filter spectra the tiles re-read
 // (tee kernel at 8192 rows: 7.3 -> 6.5 ms).
-#ifndef GFX_STORE_AUX
-#define GFX_STORE_AUX 2  // nt
-#endif
+constexpr int STORE_AUX_NT = 2;   // the buffer store's aux bits: non-temporal
 __device__ __forceinline__ void buf_store_f2(rsrc_t r, uint32_t voff, uint32_t soff, cx e) {
     using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, e), r, voff, soff, GFX_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, e), r, voff, soff, STORE_AUX_NT);
 }
 constexpr uint32_t OOB = 0xffffffffu;  // lane offset that the range check always rejects
 
@@ -468,9 +466,6 @@ __device__ __forceinline__ void macinv_pair_half(const f4v* __restrict__ Z, cons
     // two tiles uses (turn 0: tile i + 1 only, turn nparts: tile i only)
     const int64_t s0 = a.off - a.O + (tile + 1) * a.hop;                  // start of the window of turn 0
     int k_lo = two ? 0 : 1, k_hi = a.nparts;
-#ifdef GFX_PAIR_NOLOOP
-    k_hi = -1;   // timing experiment: the walk skipped, the rest of the kernel as it is
-#endif
     if (s0 >= a.L) k_lo = max(k_lo, (int)((s0 - a.L) / a.hop) + 1);       // first k with s0 - k hop < L
     if (s0 + TILE_F <= (int64_t)k_hi * a.hop) k_hi = (int)((s0 + TILE_F - 1) / a.hop);   // last k with s0 - k hop + TILE_F > 0
 
@@ -795,6 +790,18 @@ static inline void pipe_magic(uint32_t d, uint32_t& m, uint32_t& sh) {
     m = q > 0xffffffffu ? 0xffffffffu : (uint32_t)q;
 }
 
+// the kernel argument blocks are dwords: a pointer's halves, and a row map's strides in bytes (outer: 64 bits)
+static inline uint32_t ptr_lo(const void* p) { return (uint32_t)reinterpret_cast<uint64_t>(p); }
+static inline uint32_t ptr_hi(const void* p) { return (uint32_t)(reinterpret_cast<uint64_t>(p) >> 32); }
+static inline bool pipe_strides_fit(const gfx_rowmap_t& mp) {
+    return mp.stride_inner >= 0 && mp.stride_ch >= 0 && mp.stride_outer >= 0 && mp.stride_inner * 4 < (int64_t(1) << 32) &&
+           mp.stride_ch * 4 < (int64_t(1) << 32);
+}
+static inline void pipe_strides(const gfx_rowmap_t& mp, uint32_t& olo, uint32_t& ohi, uint32_t& in, uint32_t& ch) {
+    const uint64_t o = (uint64_t)mp.stride_outer * 4;
+    olo = (uint32_t)o; ohi = (uint32_t)(o >> 32); in = (uint32_t)(mp.stride_inner * 4); ch = (uint32_t)(mp.stride_ch * 4);
+}
+
 // What the persistent kernels cover: one partition, no output offset, even row lengths (stores are whole sample pairs),
 // the same batch-major row grouping on every tensor, byte strides inside 32 bits, and an overlap the build has a variant
 // for.  Everything else runs on fftconv1_kernel.
@@ -802,11 +809,7 @@ static int pipe_variant(const ConvArgs& a, const ConvGeom& g, bool tee, int64_t 
     if (g.nparts != 1 || a.off != 0 || (a.Lout & 1) || (tee && ((a.L & 1) || a.Lout != a.L)) || N > TILE_M + 1) return -1;
     if (a.L * 4 >= (int64_t(1) << 30) || a.Lout * 4 >= (int64_t(1) << 30)) return -1;
     if (a.xmap.inner != a.ymap.inner || (tee && a.cmap.inner != a.xmap.inner)) return -1;
-    auto fits = [](const gfx_rowmap_t& mp) {
-        return mp.stride_inner >= 0 && mp.stride_ch >= 0 && mp.stride_outer >= 0 && mp.stride_inner * 4 < (int64_t(1) << 32) &&
-               mp.stride_ch * 4 < (int64_t(1) << 32);
-    };
-    if (!fits(a.xmap) || !fits(a.ymap) || (tee && !fits(a.cmap))) return -1;
+    if (!pipe_strides_fit(a.xmap) || !pipe_strides_fit(a.ymap) || (tee && !pipe_strides_fit(a.cmap))) return -1;
     for (size_t i = 0; i < sizeof(kPipeVariants) / sizeof(kPipeVariants[0]); ++i)
         if (kPipeVariants[i].tee == tee && (int64_t)kPipeVariants[i].a_lo * 512 == a.O) return (int)i;
     return -1;
@@ -824,10 +827,8 @@ static int launch_pipe(PipeModule* pm, int variant, const float* x, const void* 
         k.rm_rec = (uint32_t)(rowmax_words * 4);
         k.rm_flags = 0x00020000u;
     }
-    auto lo = [](const void* p) { return (uint32_t)reinterpret_cast<uint64_t>(p); };
-    auto hi = [](const void* p) { return (uint32_t)(reinterpret_cast<uint64_t>(p) >> 32); };
-    k.x_lo = lo(x); k.x_hi = hi(x); k.h_lo = lo(Hs); k.h_hi = hi(Hs); k.y_lo = lo(y); k.y_hi = hi(y);
-    k.c_lo = lo(xcopy); k.c_hi = hi(xcopy); k.tw_lo = lo(tw); k.tw_hi = hi(tw);
+    k.x_lo = ptr_lo(x); k.x_hi = ptr_hi(x); k.h_lo = ptr_lo(Hs); k.h_hi = ptr_hi(Hs); k.y_lo = ptr_lo(y); k.y_hi = ptr_hi(y);
+    k.c_lo = ptr_lo(xcopy); k.c_hi = ptr_hi(xcopy); k.tw_lo = ptr_lo(tw); k.tw_hi = ptr_hi(tw);
     k.L_bytes = (uint32_t)(a.L * 4); k.Lout_bytes = (uint32_t)(a.Lout * 4);
     k.V_bytes = (uint32_t)(a.V * 4); k.O_bytes = (uint32_t)(a.O * 4);
     k.ntiles = (uint32_t)a.ntiles; k.nblocks = (uint32_t)a.nblocks;
@@ -841,26 +842,13 @@ static int launch_pipe(PipeModule* pm, int variant, const float* x, const void* 
     const unsigned grid = (unsigned)(2 * pm->cus) & ~7u;     // two resident workgroups per CU
     k.per_xcd = (uint32_t)((a.nblocks + grid - 1) / grid);   // tiles per workgroup: consecutive runs (the overlap is carried in registers)
     k.wgs_per_xcd = grid / 8;
-    auto strides = [](const gfx_rowmap_t& mp, uint32_t& olo, uint32_t& ohi, uint32_t& in, uint32_t& ch) {
-        const uint64_t o = (uint64_t)mp.stride_outer * 4;
-        olo = (uint32_t)o; ohi = (uint32_t)(o >> 32); in = (uint32_t)(mp.stride_inner * 4); ch = (uint32_t)(mp.stride_ch * 4);
-    };
-    strides(a.xmap, k.xs_outer_lo, k.xs_outer_hi, k.xs_inner, k.xs_ch);
-    strides(a.ymap, k.ys_outer_lo, k.ys_outer_hi, k.ys_inner, k.ys_ch);
-    if (xcopy) strides(a.cmap, k.cs_outer_lo, k.cs_outer_hi, k.cs_inner, k.cs_ch);
+    pipe_strides(a.xmap, k.xs_outer_lo, k.xs_outer_hi, k.xs_inner, k.xs_ch);
+    pipe_strides(a.ymap, k.ys_outer_lo, k.ys_outer_hi, k.ys_inner, k.ys_ch);
+    if (xcopy) pipe_strides(a.cmap, k.cs_outer_lo, k.cs_outer_hi, k.cs_inner, k.cs_ch);
     size_t size = sizeof(k);
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    // GRAFX_PIPE_THREADS: block size for an experimental code object loaded through GRAFX_PIPE_HSACO (timing experiments
-    // with other tile shapes, tools/experiments/r4_tile16); the shipped kernels are 256-thread tiles
-    // -- honoured ONLY together with GRAFX_PIPE_HSACO: the embedded code object never runs with another block size
-    static const unsigned threads = [] {
-        const char* alt = getenv("GRAFX_PIPE_HSACO");
-        const char* e = getenv("GRAFX_PIPE_THREADS");
-        const int n = (alt && *alt && e) ? atoi(e) : 0;
-        return n == 512 ? 512u : (unsigned)TILE_T;
-    }();
-    return hipModuleLaunchKernel(pm->fn[variant], grid, 1, 1, threads, 1, 1, 0, st, nullptr, config) == hipSuccess ? GFX_OK
-                                                                                                               : GFX_ELAUNCH;
+    return hipModuleLaunchKernel(pm->fn[variant], grid, 1, 1, TILE_T, 1, 1, 0, st, nullptr, config) == hipSuccess ? GFX_OK
+                                                                                                              : GFX_ELAUNCH;
 }
 
 // The hand-scheduled form of corr1_kernel (csrc/asm/gen_corr_pipe.py) covers off = 0 with the same row grouping on x and
@@ -868,21 +856,15 @@ static int launch_pipe(PipeModule* pm, int variant, const float* x, const void* 
 static bool corr_pipe_ok(const CorrArgs& a) {
     if (a.off != 0 || a.N > TILE_M + 1 || a.xmap.inner != a.gmap.inner) return false;
     if (a.L * 4 >= (int64_t(1) << 30) || a.Lg * 4 >= (int64_t(1) << 30)) return false;
-    auto fits = [](const gfx_rowmap_t& mp) {
-        return mp.stride_inner >= 0 && mp.stride_ch >= 0 && mp.stride_outer >= 0 && mp.stride_inner * 4 < (int64_t(1) << 32) &&
-               mp.stride_ch * 4 < (int64_t(1) << 32);
-    };
-    return fits(a.xmap) && fits(a.gmap);
+    return pipe_strides_fit(a.xmap) && pipe_strides_fit(a.gmap);
 }
 
 static int launch_corr_pipe(PipeModule* pm, const float* x, const float* g, float* gh, const CorrArgs& a, const float2* tw,
                             hipStream_t st) {
     CorrKernArgs k;
     memset(&k, 0, sizeof(k));
-    auto lo = [](const void* p) { return (uint32_t)reinterpret_cast<uint64_t>(p); };
-    auto hi = [](const void* p) { return (uint32_t)(reinterpret_cast<uint64_t>(p) >> 32); };
-    k.x_lo = lo(x); k.x_hi = hi(x); k.g_lo = lo(g); k.g_hi = hi(g); k.o_lo = lo(gh); k.o_hi = hi(gh);
-    k.tw_lo = lo(tw); k.tw_hi = hi(tw);
+    k.x_lo = ptr_lo(x); k.x_hi = ptr_hi(x); k.g_lo = ptr_lo(g); k.g_hi = ptr_hi(g); k.o_lo = ptr_lo(gh); k.o_hi = ptr_hi(gh);
+    k.tw_lo = ptr_lo(tw); k.tw_hi = ptr_hi(tw);
     k.L_bytes = (uint32_t)(a.L * 4); k.Lg_bytes = (uint32_t)(a.Lg * 4); k.V_bytes = (uint32_t)(a.V * 4);
     k.N_even_bytes = (uint32_t)((a.N & ~int64_t(1)) * 4);
     k.ntiles = (uint32_t)a.ntiles; k.nblocks = (uint32_t)a.nblocks;
@@ -901,22 +883,15 @@ static int launch_corr_pipe(PipeModule* pm, const float* x, const float* g, floa
     memcpy(&k.scale, &sc, 4);
     const unsigned grid = pad8(a.nblocks);
     k.pad0 = grid / 8;
-    auto strides = [](const gfx_rowmap_t& mp, uint32_t& olo, uint32_t& ohi, uint32_t& in, uint32_t& ch) {
-        const uint64_t o = (uint64_t)mp.stride_outer * 4;
-        olo = (uint32_t)o; ohi = (uint32_t)(o >> 32); in = (uint32_t)(mp.stride_inner * 4); ch = (uint32_t)(mp.stride_ch * 4);
-    };
-    strides(a.xmap, k.xs_outer_lo, k.xs_outer_hi, k.xs_inner, k.xs_ch);
-    strides(a.gmap, k.gs_outer_lo, k.gs_outer_hi, k.gs_inner, k.gs_ch);
+    pipe_strides(a.xmap, k.xs_outer_lo, k.xs_outer_hi, k.xs_inner, k.xs_ch);
+    pipe_strides(a.gmap, k.gs_outer_lo, k.gs_outer_hi, k.gs_inner, k.gs_ch);
     size_t size = sizeof(k);
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     return hipModuleLaunchKernel(pm->corr, grid, 1, 1, TILE_T, 1, 1, 0, st, nullptr, config) == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
-// Whether GFX_SCHED_AUTO may pick the persistent kernel for large launches (decided by measurement)
-#ifndef GFX_PIPE_AUTO
-#define GFX_PIPE_AUTO 1
-#endif
-// GFX_SCHED_AUTO: which of the two kernels a launch gets.  GRAFX_FFTCONV_SCHED=tile|pipe overrides (A/B measurements).
+// GFX_SCHED_AUTO: which of the two kernels a launch gets (the persistent kernel for large launches: decided by measurement,
+// DESIGN.md section 4.2).  GRAFX_FFTCONV_SCHED=tile|pipe overrides (A/B measurements).
 static int auto_schedule() {
     static int cached = -1;
     if (cached < 0) {
@@ -1128,7 +1103,7 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
         if (auto_schedule() == GFX_SCHED_PIPE) schedule = GFX_SCHED_TILE;   // the override only steers what can be steered
         else return GFX_EINVAL;
     }
-    if (schedule == GFX_SCHED_PIPE || (schedule == GFX_SCHED_AUTO && pv >= 0 && GFX_PIPE_AUTO && a.nblocks >= 16 * pm->cus))
+    if (schedule == GFX_SCHED_PIPE || (schedule == GFX_SCHED_AUTO && pv >= 0 && a.nblocks >= 16 * pm->cus))
     {
         // (the shipped code object is generated without the rowmax knob: this kernel takes even output lengths only, and the
         // one consumer of the maxima -- the odd-length aliasing -- has an odd one)

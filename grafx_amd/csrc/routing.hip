@@ -14,13 +14,6 @@
 
 #include "../../include/grafx_amd.h"
 
-#ifdef GFX_NT_OFF
-#define GFX_NT_STORE(...) gfx_plain_store(__VA_ARGS__)
-template <typename T> __device__ __forceinline__ void gfx_plain_store(T v, T* p) { *p = v; }
-#else
-#define GFX_NT_STORE(...) __builtin_nontemporal_store(__VA_ARGS__)
-#endif
-
 #ifndef GFX_GATHER_UNROLL
 #define GFX_GATHER_UNROLL 1
 #endif
@@ -30,7 +23,7 @@ namespace gfx {
 // streamed outputs: non-temporal, so they do not push the rows still being read out of L2
 __device__ __forceinline__ void nt_store(float4* p, float4 v) {
     using f4 = float __attribute__((ext_vector_type(4)));
-    GFX_NT_STORE(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
+    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
 }
 
 __global__ __launch_bounds__(256) void gather_sum_kernel(const float* __restrict__ buf, int64_t buf_sb, int64_t buf_sv,

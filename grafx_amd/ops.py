@@ -191,8 +191,8 @@ SCHEDULES = {"auto": 0, "tile": 1, "pipe": 2}   # GFX_SCHED_* of include/grafx_a
 # launches it covers) or "pipe" (prefer that kernel at every size it covers -- tests and latency experiments).
 FFTCONV_SCHEDULE = "auto"
 # the full-length convolution in front of the odd-length aliasing leaves the rows' maxima for its pair scaling (round 6;
-# GRAFX_ROWMAX_BYPRODUCT=0: the aliasing takes them in a pass of its own over z, as for every other producer of z)
-ROWMAX_BYPRODUCT = os.environ.get("GRAFX_ROWMAX_BYPRODUCT", "1") != "0"
+# False: the aliasing takes them in a pass of its own over z, as for every other producer of z)
+ROWMAX_BYPRODUCT = True
 
 
 @_on_device
@@ -653,9 +653,9 @@ MIX_FUSION = True          # dynamics stages take the routing sum that follows t
 DYN_SCHEDULE = "oneshot"
 # the compressor backward without a kept scan rebuilds it inside its tiles (gfx_dynamics_bwd_rescan_ws_f32); False: a pass
 # over every row writes it out first (gfx_dynamics_bwd_f32, rounds 2-5)
-DYN_BWD_RESCAN = os.environ.get("GRAFX_DYN_BWD_RESCAN", "1") != "0"
-# rows with a long smoother memory stay on the tile grid (gfx_dynamics_ws_bytes_ex); False / GRAFX_DYN_LOOKBACK=0: round 4
-DYN_LOOKBACK = os.environ.get("GRAFX_DYN_LOOKBACK", "1") != "0"
+DYN_BWD_RESCAN = True
+# rows with a long smoother memory stay on the tile grid (gfx_dynamics_ws_bytes_ex); False: round 4
+DYN_LOOKBACK = True
 
 
 def mix_schedule(dest_sources, n):

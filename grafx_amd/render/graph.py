@@ -9,7 +9,6 @@ upstream; the processors are the HIP-backed modules of ``grafx_amd.processors``
 (or any ``nn.Module`` with the same interface, e.g. the CPU oracle in tests).
 """
 import contextlib
-import os
 import warnings
 
 import torch
@@ -28,8 +27,8 @@ from .core import (
 # Training forward: keep the dynamics stages' smoother scan (R x L floats per stage) for their backward.  Rounds 2-5 kept it
 # (the alternative was a pass of its own over every row); since round 6 the backward tiles rebuild the scan from the
 # samples they read anyway (gfx_dynamics_bwd_rescan_ws_f32), which takes 4 bytes per sample out of the forward AND the
-# backward kernel and 4.8 GB at 256 graphs out of the step's peak: off by default (GRAFX_KEEP_SCAN=1: round 5's path).
-KEEP_SMOOTHER_SCAN = os.environ.get("GRAFX_KEEP_SCAN", "0") == "1"
+# backward kernel and 4.8 GB at 256 graphs out of the step's peak: off by default (True: round 5's path).
+KEEP_SMOOTHER_SCAN = False
 # Where the parameter-only work of the later stages (filter design, the reverb's impulse response and spectra) runs:
 #   "under_first"   on a side stream underneath the first processor stage's signal kernel (the convolution of the first
 #                   equaliser stage in a console: compute-bound, the side kernels take CUs from it);

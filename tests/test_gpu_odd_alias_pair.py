@@ -240,8 +240,7 @@ def test_a_call_of_many_rows_gives_the_bits_of_calls_of_two(P, rows, precise):
 @pytest.mark.parametrize("P", [258049, 299999, 483999])
 def test_fused_outer_level_equals_the_separate_passes(P, monkeypatch):
     """One outer radix-4 level: czt_pair_lv_* (outer pass + column pass in one kernel, five sweeps) against the chain of
-    separate passes (nine sweeps; GRAFX_CZT_FUSED_LEVEL=0 is read once per process, so the separate chain is reached through
-    the one-row form here, which has no fused kernels): the same transform, another factorisation of the twiddles."""
+    separate passes (nine sweeps; the separate chain is reached through the one-row form here, which has no fused kernels): the same transform, another factorisation of the twiddles."""
     from grafx_amd import ops
 
     torch.manual_seed(P)
