@@ -695,3 +695,74 @@ class BiquadCascadeFn(torch.autograd.Function):
         gx = g.sum(1, keepdim=True) if x.shape[1] == 1 and Cout > 1 else g
         return (gx if ctx.needs_input_grad[0] else None, gB if ctx.needs_input_grad[1] else None,
                 gA if ctx.needs_input_grad[2] else None)
+
+
+class BiquadCascadeStateFn(torch.autograd.Function):
+    """(y, zf) = the cascade of BiquadCascadeFn started from the state zi (gfx_biquad_cascade_state_f32): zi, zf (R, Cout, K, 2),
+    per section (w[-1], w[-2]) in and (w[L-1], w[L-2]) out of the a0-normalised direct form II
+        w[n] = u[n] - a1 w[n-1] - a2 w[n-2],    y[n] = b0 w[n] + b1 w[n-1] + b2 w[n-2],    b = B / a0, a = A / a0.
+
+    Backward, per section from the last to the first, given g = dL/dy and (q1, q2) = dL/dzf of that section.  With a state
+    coming in, y is no longer (B / A) u, so BiquadCascadeFn's y-based formula for dA does not hold: everything is derived
+    from w, which the native kernel recomputes from the saved section input (unit numerator, the section's zi):
+        r[m]   = sum_d b_d g[m + d]  (+ q1 at m = L-1, + q2 at m = L-2)        m = -2 .. L-1: what reads w[m] directly
+        lam[m] = r[m] - a1 lam[m+1] - a2 lam[m+2]                               m = L-1 .. 0: the same all-pole recursion run
+                                                                                backwards in time, from silence (native kernel)
+        dzi    = (r[-1] - a1 lam[0] - a2 lam[1],  r[-2] - a2 lam[0])            its two values past sample 0 (w[-2] feeds w[0] only)
+        db_d   =  sum_n g[n] w[n-d]  (d = 0, 1, 2),    da_d = -sum_n lam[n] w[n-d]  (d = 1, 2)
+        dB_d   = db_d / a0,   dA_d = da_d / a0 (d = 1, 2),   dA_0 = -(sum_d b_d db_d + sum_d a_d da_d) / a0
+    and lam is dL/du, the g of the section before.  Channel broadcasts (1 <-> C) reduce as in BiquadCascadeFn."""
+
+    @staticmethod
+    def forward(ctx, x, Bs, As, zi):
+        K = Bs.shape[2]
+        us, zfs = [x.contiguous()], []
+        for i in range(K):
+            u, z = ops.biquad_cascade(us[-1], Bs[:, :, i : i + 1].contiguous(), As[:, :, i : i + 1].contiguous(),
+                                      zi=zi[:, :, i : i + 1].contiguous(), return_state=True)
+            us.append(u)
+            zfs.append(z)
+        ctx.save_for_backward(Bs, As, zi, *us[:-1])
+        return us[-1], torch.cat(zfs, 2)
+
+    @staticmethod
+    def backward(ctx, gy, gzf):
+        Bs, As, zi, *us = ctx.saved_tensors
+        R, Cf, K, _ = Bs.shape
+        Cout, L = zi.shape[1], us[0].shape[-1]
+        g = (torch.zeros((R, Cout, L), dtype=Bs.dtype, device=Bs.device) if gy is None else gy).contiguous()
+        gzf = torch.zeros_like(zi) if gzf is None else gzf
+        gB, gA, gzi = torch.zeros_like(Bs), torch.zeros_like(As), torch.zeros_like(zi)
+        unit = torch.zeros((R, Cf, 1, 3), dtype=Bs.dtype, device=Bs.device)
+        unit[..., 0] = 1.0
+
+        def to_filter_channels(t):     # (R, Cout) -> (R, Cf)
+            return t.sum(1, keepdim=True) if (Cf == 1 and Cout > 1) else t
+
+        for i in reversed(range(K)):
+            a0 = As[:, :, i, 0:1]                                   # (R, Cf, 1): broadcasts over channels and time
+            b, a = Bs[:, :, i] / a0, As[:, :, i] / a0               # (R, Cf, 3), a[..., 0] = 1
+            An = a.unsqueeze(2).contiguous()
+            zi_i = zi[:, :, i : i + 1].contiguous()
+            w = ops.biquad_cascade(us[i], unit, An, zi=zi_i, return_state=True)[0]
+            w_ext = torch.cat([zi_i[:, :, 0, 1:2], zi_i[:, :, 0, 0:1], w], -1)      # w[-2], w[-1], w[0] .. w[L-1]
+            r = torch.zeros((R, Cout, L + 2), dtype=g.dtype, device=g.device)          # r[m] at index m + 2
+            r[..., 2:] += b[..., 0:1] * g
+            r[..., 1 : L + 1] += b[..., 1:2] * g
+            r[..., :L] += b[..., 2:3] * g
+            r[..., L + 1] += gzf[:, :, i, 0]
+            r[..., L] += gzf[:, :, i, 1]
+            lam = ops.biquad_cascade(r[..., 2:].flip(-1).contiguous(), unit, An).flip(-1)
+            lam1 = lam[..., 1] if L > 1 else torch.zeros_like(lam[..., 0])
+            gzi[:, :, i, 0] = r[..., 1] - a[..., 1] * lam[..., 0] - a[..., 2] * lam1
+            gzi[:, :, i, 1] = r[..., 0] - a[..., 2] * lam[..., 0]
+            db = torch.stack([to_filter_channels((g * w_ext[..., 2 - d : L + 2 - d]).sum(-1)) for d in range(3)], -1)
+            da = torch.stack([-to_filter_channels((lam * w_ext[..., 2 - d : L + 2 - d]).sum(-1)) for d in (1, 2)], -1)
+            gB[:, :, i] = db / a0
+            gA[:, :, i, 1:] = da / a0
+            gA[:, :, i, 0] = -((b * db).sum(-1) + (a[..., 1:] * da).sum(-1)) / a0[..., 0]
+            g = lam
+        x = us[0]
+        gx = g.sum(1, keepdim=True) if x.shape[1] == 1 and Cout > 1 else g
+        need = ctx.needs_input_grad
+        return (gx if need[0] else None, gB if need[1] else None, gA if need[2] else None, gzi if need[3] else None)

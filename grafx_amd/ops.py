@@ -1102,8 +1102,13 @@ def stereo_gain(x, log_gain, out=None, mix=None):
 
 
 @_on_device
-def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None):
-    """Exact time-domain cascade of the K biquads in Bs/As (R,Cf,K,3) over x (R,C,L) or a (B,n,C,L) view."""
+def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None, zi=None, return_state=False):
+    """Exact time-domain cascade of the K biquads in Bs/As (R,Cf,K,3) over x (R,C,L) or a (B,n,C,L) view.
+
+    ``zi``: the filter state entering sample 0, contiguous float32 (R, Cout, K, 2) with Cout = max(C, Cf): per row-channel
+    and section (w[-1], w[-2]) of the a0-normalised direct-form-II recursion (None: silence).  With ``zi`` or
+    ``return_state`` the result is ``(y, zf)``, zf = (w[L-1], w[L-2]) in the same layout (a new tensor): feed it to the next
+    block's call and the blocks' outputs are the one-call output of the whole signal."""
     _require_gpu(x, Bs, As, out)
     xmap, R, Cin, L = rowmap(x)
     Rb, Cf, K, three = Bs.shape
@@ -1114,10 +1119,23 @@ def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None):
         out = torch.empty((R, Cout, L), dtype=torch.float32, device=x.device)
     ymap = rowmap(out)[0]
     Bs, As = Bs.contiguous(), As.contiguous()
-    with _timed("biquad_cascade_kernel", 4 * R * (Cin + Cout) * L):
-        check(lib().gfx_biquad_cascade_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), R, Cin, Cf, K, L,
-                                           int(ssm_quirk), _stream()), "gfx_biquad_cascade_f32")
-    return out
+    if zi is None and not return_state:
+        with _timed("biquad_cascade_kernel", 4 * R * (Cin + Cout) * L):
+            check(lib().gfx_biquad_cascade_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), R, Cin, Cf, K, L,
+                                               int(ssm_quirk), _stream()), "gfx_biquad_cascade_f32")
+        return out
+    if zi is not None:
+        if not isinstance(zi, torch.Tensor) or not zi.is_cuda or zi.dtype != torch.float32:
+            raise ValueError(f"biquad_cascade: zi must be a float32 tensor on the GPU, got "
+                             f"{getattr(zi, 'dtype', type(zi).__name__)} on {getattr(zi, 'device', 'the host')}")
+        _expect(zi, (R, Cout, K, 2), "biquad_cascade: zi")
+        if not zi.is_contiguous():
+            raise ValueError("biquad_cascade: zi must be contiguous")
+    zf = torch.empty((R, Cout, K, 2), dtype=torch.float32, device=x.device)
+    with _timed("biquad_cascade_state_kernel", 4 * R * (Cin + Cout) * L + 16 * R * Cout * K):
+        check(lib().gfx_biquad_cascade_state_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), _ptr(zi), _ptr(zf),
+                                                 R, Cin, Cf, K, L, int(ssm_quirk), _stream()), "gfx_biquad_cascade_state_f32")
+    return out, zf
 
 
 @_on_device

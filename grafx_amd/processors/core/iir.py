@@ -32,7 +32,8 @@ class IIRFilter(nn.Module):
             self._plans = {}
         elif backend in ("lfilter", "ssm"):
             # upstream: torchaudio.functional.lfilter per section / a state-space form on torchlpc (iir.py:154-261).
-            # Here both are the exact recursive cascade as one parallel-scan HIP kernel (gfx_biquad_cascade_f32).
+            # Here both are the exact recursive cascade as one parallel-scan HIP kernel (gfx_biquad_cascade_f32; with the
+            # filter state carried across calls: gfx_biquad_cascade_state_f32).
             # (first-order sections ride on it with a zero third coefficient; upstream's "ssm" asserts order 2, iir.py:226)
             if order not in (1, 2) or (order == 1 and backend == "ssm"):
                 raise NotImplementedError("the HIP recursive kernel runs first- and second-order sections (order 1 or 2; "
@@ -84,25 +85,65 @@ class IIRFilter(nn.Module):
         """Sampled response of every section: sum_d B_d D_d / sum_d A_d D_d (``eps`` is accepted and unused upstream)."""
         return (Bs.unsqueeze(-1) * delays).sum(-2) / (As.unsqueeze(-1) * delays).sum(-2)
 
-    def _process_recursive(self, input_signal, Bs, As, out=None):
-        if Bs.shape[-1] == 2 and As.shape[-1] == 2:     # first-order sections: b2 = a2 = 0 (differentiable: a zero pad)
+    def _process_recursive(self, input_signal, Bs, As, out=None, state=None, return_state=False):
+        first_order = Bs.shape[-1] == 2 and As.shape[-1] == 2
+        if first_order:     # first-order sections: b2 = a2 = 0 (differentiable: a zero pad)
             Bs, As = torch.nn.functional.pad(Bs, (0, 1)), torch.nn.functional.pad(As, (0, 1))
-        if needs_grad(input_signal, Bs, As):
-            x3 = input_signal.reshape(-1, *input_signal.shape[-2:]) if input_signal.ndim == 4 else input_signal
-            if self.backend == "ssm" and Bs.shape[2] > 1:
+        stateful = state is not None or return_state
+        lead = input_signal.shape[:2] if input_signal.ndim == 4 else None     # a (B, n, C, L) view: rows are B * n
+        if state is not None and lead is not None and state.ndim == 5:
+            state = state.reshape(-1, *state.shape[2:])
+        if needs_grad(input_signal, Bs, As, state):
+            x3 = input_signal.reshape(-1, *input_signal.shape[-2:]) if lead is not None else input_signal
+            if stateful:
+                y, zf = self._stateful_differentiable(x3, Bs, As, state)
+            elif self.backend == "ssm" and Bs.shape[2] > 1:
                 y = self._ssm_quirk_differentiable(x3, Bs, As)
             else:
                 y = diff.BiquadCascadeFn.apply(x3, Bs, As)   # native recursion both ways (autograd.BiquadCascadeFn)
-            if input_signal.ndim == 4:
-                y = y.view(*input_signal.shape[:2], *y.shape[1:])
-            if out is None:
-                return y
-            out.copy_(y.view(out.shape))
-            return out
-        if self.backend == "ssm":
-            assert Bs.shape[-1] == As.shape[-1] == 3, "The filter order must be 2."
-        # "ssm" with K > 1: upstream drives every section's recursion with the original input (iir.py:226-246)
-        return ops.biquad_cascade(input_signal, Bs, As, ssm_quirk=self.backend == "ssm", out=out)
+            if lead is not None:
+                y = y.view(*lead, *y.shape[1:])
+            if out is not None:
+                out.copy_(y.view(out.shape))
+                y = out
+        else:
+            if self.backend == "ssm":
+                assert Bs.shape[-1] == As.shape[-1] == 3, "The filter order must be 2."
+            # "ssm" with K > 1: upstream drives every section's recursion with the original input (iir.py:226-246)
+            if not stateful:
+                return ops.biquad_cascade(input_signal, Bs, As, ssm_quirk=self.backend == "ssm", out=out)
+            y, zf = ops.biquad_cascade(input_signal, Bs, As, ssm_quirk=self.backend == "ssm", out=out, zi=state,
+                                       return_state=True)
+        if not return_state:
+            return y
+        if first_order:     # a first-order section has one state value: w[n-2] is read by nothing (a2 = b2 = 0)
+            zf = zf * zf.new_tensor([1.0, 0.0])
+        return y, (zf.view(*lead, *zf.shape[1:]) if lead is not None else zf)
+
+    def _stateful_differentiable(self, x, Bs, As, state):
+        """(y, zf) with gradients (autograd.BiquadCascadeStateFn); "ssm" with K > 1 as in _ssm_quirk_differentiable below,
+        every section's recursion (and so its state) driven by the original input."""
+        R, Cout, K = x.shape[0], max(x.shape[1], Bs.shape[1]), Bs.shape[2]
+        if state is None:
+            state = torch.zeros((R, Cout, K, 2), dtype=x.dtype, device=x.device)
+        elif tuple(state.shape) != (R, Cout, K, 2) or state.dtype != torch.float32:
+            raise ValueError(f"state: expected a float32 tensor of shape {(R, Cout, K, 2)}, got {state.dtype} "
+                             f"{tuple(state.shape)}")
+        if self.backend != "ssm" or K == 1:
+            return diff.BiquadCascadeStateFn.apply(x, Bs, As, state)
+        a0 = As[..., :1]
+        Bn, a12 = Bs / a0, As[..., 1:] / a0
+        b0 = Bn[..., :1]
+        b12 = Bn[..., 1:] - b0 * a12
+        one, zero = torch.ones_like(b0[:, :, 0]), torch.zeros_like(b0[:, :, 0])
+        y, zfs = x, []
+        for k in range(K):
+            Bk = torch.cat([zero, b12[:, :, k]], -1).unsqueeze(2)
+            Ak = torch.cat([one, a12[:, :, k]], -1).unsqueeze(2)
+            d, zf = diff.BiquadCascadeStateFn.apply(x, Bk, Ak, state[:, :, k : k + 1])
+            y = b0[:, :, k] * y + d
+            zfs.append(zf)
+        return y, torch.cat(zfs, 2)
 
     @staticmethod
     def _ssm_quirk_differentiable(x, Bs, As):
@@ -124,9 +165,18 @@ class IIRFilter(nn.Module):
             y = b0[:, :, k] * y + diff.BiquadCascadeFn.apply(x, Bk, Ak)
         return y
 
-    def forward(self, input_signal, Bs, As, out=None, tee=None, shared_rows=None, final=False):
+    def forward(self, input_signal, Bs, As, out=None, tee=None, shared_rows=None, final=False, state=None,
+                return_state=False):
         """``shared_rows``: Bs/As hold that many rows, shared by the batch (signal row r uses r % shared_rows).
-        ``final``: the caller returns this output as its own up to linear operations (autograd.TAPE_ONLY)."""
+        ``final``: the caller returns this output as its own up to linear operations (autograd.TAPE_ONLY).
+        ``state`` / ``return_state`` (recursive backends): block-wise processing of a long signal.  ``state`` is the filter
+        state entering this block, float32 (R, Cout, K, 2) -- (B, n, Cout, K, 2) for a (B, n, C, L) input -- with
+        (w[n-1], w[n-2]) of every section's a0-normalised direct form II (first-order sections: a zero second entry); None
+        is silence.  With ``return_state`` the result is ``(y, state)``, the state after the block's last sample: pass it
+        to the next block's call and the blocks' outputs are the one-call output, gradients included."""
+        if self.backend == "fsm" and (state is not None or return_state):
+            raise ValueError("IIRFilter(backend='fsm'): the frequency-sampled FIR carries no recursive state; use the "
+                             "recursive backends (backend='lfilter' or 'ssm') for block-wise processing")
         if shared_rows is not None and self.backend != "fsm":
             rows = input_signal.shape[0] * input_signal.shape[1] if input_signal.ndim == 4 else input_signal.shape[0]
             Bs, As = Bs.repeat(rows // shared_rows, 1, 1, 1), As.repeat(rows // shared_rows, 1, 1, 1)  # no row sharing
@@ -134,7 +184,7 @@ class IIRFilter(nn.Module):
         if self.backend != "fsm":
             if tee is not None:
                 tee.copy_(input_signal)
-            return self._process_recursive(input_signal, Bs, As, out=out)
+            return self._process_recursive(input_signal, Bs, As, out=out, state=state, return_state=return_state)
         if tee is not None and needs_grad(input_signal, Bs, As):
             tee.copy_(input_signal)
             tee = None

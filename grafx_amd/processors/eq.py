@@ -27,15 +27,20 @@ class ParametricEqualizer(BufferIO, nn.Module):
     accepts_shared_params = True  # render_into(..., _shared_rows=n): parameters hold n rows shared by the batch
     accepts_strided_rows = True   # forward() also takes a strided (B, n, C, L) view and then returns (B, n, C, L)
 
-    def forward(self, input_signals, w0, q_inv, log_gain, _out=None, _tee=None, _shared_rows=None):
+    def forward(self, input_signals, w0, q_inv, log_gain, _out=None, _tee=None, _shared_rows=None, state=None,
+                return_state=False):
+        """``state`` / ``return_state``: block-wise processing on a recursive backend (IIRFilter.forward); the state belongs
+        to the filtered channels, i.e. to mid and side when ``processor_channel="midside"``."""
         self._check_bands()
         if needs_grad(input_signals, w0, q_inv, log_gain):
             Bs, As = diff.PeqCoeffsFn.apply(w0, q_inv, log_gain, self.use_shelving_filters)
         else:
             Bs, As = ops.peq_coeffs(w0, q_inv, log_gain, self.use_shelving_filters)
+        block = {} if state is None and not return_state else {"state": state, "return_state": return_state}
         if self.processor_channel == "midside":
-            return ms_to_lr(self.biquad(lr_to_ms(input_signals), Bs, As, shared_rows=_shared_rows, final=True))
-        return self.biquad(input_signals, Bs, As, out=_out, tee=_tee, shared_rows=_shared_rows, final=True)
+            y = self.biquad(lr_to_ms(input_signals), Bs, As, shared_rows=_shared_rows, final=True, **block)
+            return (ms_to_lr(y[0]), y[1]) if return_state else ms_to_lr(y)
+        return self.biquad(input_signals, Bs, As, out=_out, tee=_tee, shared_rows=_shared_rows, final=True, **block)
 
     def get_biquad_coefficients_with_shelving_filters(self, cos_w0, alpha, A):
         """Band 0 a low shelf, band K-1 a high shelf, peaking filters in between (eq.py:300-314), from the common

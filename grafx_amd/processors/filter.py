@@ -71,12 +71,14 @@ class BiquadFilter(BufferIO, nn.Module):
         self.normalized = normalized
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, Bs, A1_pre, A2_pre, A0=None, _out=None):
+    def forward(self, input_signals, Bs, A1_pre, A2_pre, A0=None, _out=None, state=None, return_state=False):
+        """``state`` / ``return_state``: block-wise processing on a recursive backend (IIRFilter.forward)."""
         A0 = A0 if self.normalized else None
-        if needs_grad(input_signals, Bs, A1_pre, A2_pre, A0):
-            return self.biquad(input_signals, *diff.biquad_coefficients(Bs, A1_pre, A2_pre, A0), out=_out, final=True)
+        block = {} if state is None and not return_state else {"state": state, "return_state": return_state}
+        if needs_grad(input_signals, Bs, A1_pre, A2_pre, A0, state):
+            return self.biquad(input_signals, *diff.biquad_coefficients(Bs, A1_pre, A2_pre, A0), out=_out, final=True, **block)
         Bs, As = ops.biquad_coeffs(Bs, A1_pre, A2_pre, A0)
-        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), out=_out)
+        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), out=_out, **block)
 
     def render_into(self, x4, out4, **params):
         return self.forward(x4, _out=out4, **params)

@@ -590,6 +590,15 @@ int gfx_gather_sum_fanout_f32(const float* buf, int64_t buf_sb, int64_t buf_sv, 
 int gfx_biquad_cascade_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* Bs,
                            const float* As, int64_t R, int64_t C_in, int64_t C_f, int64_t K, int64_t L, int ssm_quirk,
                            void* stream);
+/* The same cascade with the filter state carried across calls, for block-wise processing of a long signal.
+ * zi, zf: (R, C_out, K, 2) contiguous, C_out = max(C_in, C_f): per row-channel and section (w[n-1], w[n-2]) of the
+ * a0-normalised direct-form-II recursion above -- zi the state entering sample 0, zf = (w[L-1], w[L-2]), the state
+ * after the LAST sample (not after the kernel's zero-padded last tile).  Either may be NULL (zero state in / state not
+ * stored), and zi == zf updates the state in place.  Under ssm_quirk the state is still every section's own w.
+ * With zi = zf = NULL the output is that of gfx_biquad_cascade_f32. */
+int gfx_biquad_cascade_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* Bs,
+                                 const float* As, const float* zi, float* zf, int64_t R, int64_t C_in, int64_t C_f,
+                                 int64_t K, int64_t L, int ssm_quirk, void* stream);
 
 /* ---- noise-shaping reverb impulse response ------------------------------------------------
  * replaces the envelope synthesis of FilteredNoiseShapingReverb.forward (reverb.py:343-366):
