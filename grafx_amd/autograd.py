@@ -616,6 +616,30 @@ class BallisticsFn(torch.autograd.Function):
         return gx, gz.reshape(z_alpha.shape)
 
 
+class BallisticsStateFn(torch.autograd.Function):
+    """(y, zf) = the recursion of BallisticsFn started from y[-1] = zi (R,) instead of 1, zf = y[:, L-1]
+    (gfx_ballistics_state_f32 / gfx_ballistics_bwd_state_f32).  Differentiable in x, z_alpha and zi; either output's cotangent
+    may be missing.  A cotangent of zf is one of y[:, L-1]; dL/dzi is the adjoint carry that leaves sample 0."""
+
+    @staticmethod
+    def forward(ctx, x, z_alpha, zi):
+        x, z_alpha, zi = x.contiguous(), z_alpha.contiguous(), zi.contiguous()
+        y, zf = ops.ballistics(x, z_alpha, zi=zi, return_state=True)
+        ctx.save_for_backward(x, z_alpha, zi, y)
+        ctx.set_materialize_grads(False)
+        return y, zf
+
+    @staticmethod
+    def backward(ctx, g, gzf):
+        x, z_alpha, zi, y = ctx.saved_tensors
+        g = torch.zeros_like(y) if g is None else g
+        if gzf is not None:
+            g = g.clone()
+            g[:, -1] += gzf
+        gx, gz, gzi = ops.ballistics_bwd(x, y, g, z_alpha, zi=zi)
+        return gx, gz.reshape(z_alpha.shape), gzi
+
+
 def log_gain(G, T, log_ratio, log_knee, knee, gate):
     """dynamics.py:444-489 (compressor), 676-721 (gate)."""
     R = 1 + torch.exp(log_ratio)

@@ -6,6 +6,9 @@
 //
 //     y[-1] = 1;   c[n] = at if x[n] < y[n-1] else rt;   y[n] = (1 - c[n]) y[n-1] + c[n] x[n]
 //
+// The *_state entries start a row from y[-1] = zi[row] instead and leave y[L-1] in zf[row]: a signal processed in blocks,
+// each entering with the state the block before left, is the one-call recursion in the same bits.
+//
 // The coefficient depends on the state, so this is not an associative scan.  What the recursion does have
 // is CONTRACTION: every step maps the state through a non-decreasing piecewise-linear function of slope 1 - at or
 // 1 - rt < 1, so two trajectories over the same input approach each other by that factor per sample and, in float32,
@@ -17,7 +20,7 @@
 //           recursion -- the same two products and one sum per step, rounded separately, as the reference's CPU loop --
 //           and keeps the state it ENTERS its chunk with.  After the chunk the lanes compare, bit for bit, that entry
 //           state with the state the lane to the left LEFT its chunk with (one DPP shift).  Chunk 0 starts from
-//           y[-1] = 1, so by induction a row whose comparisons all hold is exactly the sequential recursion; a row
+//           y[-1] (1, or the row's zi), so by induction a row whose comparisons all hold is exactly the sequential recursion; a row
 //           with a mismatch, or whose slower coefficient needs a longer warm-up than a chunk, is flagged.
 //   pass 1  flagged rows are walked whole, one lane per row (16 / 32 / 64 rows per wave).
 //
@@ -62,6 +65,10 @@ struct BlArgs {
     const float *log_threshold, *log_ratio, *log_knee;
     int knee, gate;
     unsigned prows;
+    // state across calls: zi (R) is y[-1] of every SIGNAL row (nullptr: 1), zf (R) receives y[L-1] (nullptr: not wanted).
+    // Every launch of a call reads zi again for the rows it walks from their first sample: the two must not share memory.
+    const float* zi;
+    float* zf;
 };
 
 __device__ __forceinline__ int64_t row_off(const gfx_rowmap_t& m, int64_t r, int c) {
@@ -216,6 +223,7 @@ __global__ __launch_bounds__(64) void ballistics_walk_kernel(BlArgs a) {
     for (int u = 0; u < PF; ++u)
         if (u < ntile) request(u, nx[u], nz[u]);
     float s = 1.0f;            // zi = 1 (envelope.py:98); chunks > 0 replace it by the first sample they see
+    if (a.zi && valid && chunk == 0) s = a.zi[row];
     float entry = 1.0f;
     float* mine = &tile[(lane < RPW ? lane : 0) * PITCH];   // (lanes >= RPW only copy)
     // one tile: the register set that holds it -> LDS (and re-requested for the tile PF ahead), walk, store
@@ -323,6 +331,9 @@ __global__ __launch_bounds__(64) void ballistics_walk_kernel(BlArgs a) {
         for (int u = 0; u < PF; ++u)
             if (ti0 + u < ntile) do_tile(ti0 + u, nx[u], nz[u]);
     }
+    // the lane that walked the row's last sample holds y[L-1].  A row that pass 0 flags below is walked again by a later
+    // launch of the same call, which writes again; a row this launch did not walk is not written by it.
+    if (a.zf && alive && cend == a.L) a.zf[row] = s;
     if (a.pass == 0) {
         // lane k entered its chunk with the state its warm-up reached; the row's true state there is what lane k - 1
         // left its chunk with, PROVIDED lane k - 1 was right itself -- chunk 0 is (it starts from zi), so a row without a
@@ -357,15 +368,17 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // u: SRC 0 rows / SRC 1 signal.  Without a workspace (the flags of the two-pass form) every row is walked whole.
 template <int SRC, int DST = 0>
 static int ballistics_run(const float* u, gfx_rowmap_t xmap, int C, const float* z, int is_coef, float* y, int64_t R, int64_t L,
-                   void* ws, size_t ws_bytes, hipStream_t st, const BlArgs* gain = nullptr) {
+                   void* ws, size_t ws_bytes, hipStream_t st, const BlArgs* gain = nullptr, const float* zi = nullptr,
+                   float* zf = nullptr) {
     if (!u || !z || !y || R <= 0 || L <= 0 || R > 0x3fffffffLL || L > 0x7fffff00LL) return GFX_EINVAL;
+    if (zi && zf && zi < zf + R && zf < zi + R) return GFX_EINVAL;   // (later launches re-read zi after earlier ones wrote zf)
     if (SRC == 1 && ((C != 1 && C != 2) || xmap.inner <= 0)) return GFX_EINVAL;
     if (ws && ws_bytes < gfx_ballistics_ws_bytes(R)) return GFX_ENOSPC;
     BlArgs a;
     if (gain) a = *gain;    // DST 1: ymap and the gain computer's parameters
     else { a.ymap = xmap; a.log_threshold = a.log_ratio = a.log_knee = nullptr; a.knee = a.gate = 0; a.prows = 1; }
     a.u = u; a.xmap = xmap; a.C = C; a.y = y; a.z = z; a.is_coef = is_coef; a.flag = reinterpret_cast<unsigned*>(ws);
-    a.R = R; a.L = L;
+    a.R = R; a.L = L; a.zi = zi; a.zf = zf;
     a.vec = (L % 4 == 0) && aligned16(u) && aligned16(y);
     if (SRC == 1) a.vec = a.vec && xmap.stride_outer % 4 == 0 && xmap.stride_inner % 4 == 0 && xmap.stride_ch % 4 == 0;
     if (DST == 1) a.vec = a.vec && a.ymap.stride_outer % 4 == 0 && a.ymap.stride_inner % 4 == 0 && a.ymap.stride_ch % 4 == 0;
@@ -423,24 +436,43 @@ int gfx_ballistics_f32(const float* u, const float* z_alpha, float* y, int64_t R
 
 int gfx_ballistics_ws_f32(const float* u, const float* z_alpha, int is_coef, float* y, int64_t R, int64_t L, void* ws,
                           size_t ws_bytes, void* stream) {
+    return gfx_ballistics_state_f32(u, z_alpha, is_coef, nullptr, nullptr, y, R, L, ws, ws_bytes, stream);
+}
+
+int gfx_ballistics_state_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
+                             int64_t L, void* ws, size_t ws_bytes, void* stream) {
     gfx_rowmap_t none = {1, 0, 0, 0};
-    return ballistics_run<0>(u, none, 1, z_alpha, is_coef, y, R, L, ws, ws_bytes, (hipStream_t)stream);
+    return ballistics_run<0>(u, none, 1, z_alpha, is_coef, y, R, L, ws, ws_bytes, (hipStream_t)stream, nullptr, zi, zf);
 }
 
 int gfx_dynamics_ballistics_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
                                 const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
                                 int64_t R, int64_t C, int64_t L, int knee, int gate, void* ws, size_t ws_bytes, void* stream) {
+    return gfx_dynamics_ballistics_state_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L,
+                                             knee, gate, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int gfx_dynamics_ballistics_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
+                                      const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
+                                      int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
+                                      size_t ws_bytes, void* stream) {
     if (!log_threshold || !log_ratio || knee < 0 || knee > 2 || (knee != 0 && !log_knee)) return GFX_EINVAL;
     if (param_rows < 1 || param_rows > R || xmap.inner <= 0 || ymap.inner <= 0) return GFX_EINVAL;
     BlArgs g;
     g.ymap = ymap; g.log_threshold = log_threshold; g.log_ratio = log_ratio; g.log_knee = log_knee;
     g.knee = knee; g.gate = gate; g.prows = (unsigned)param_rows;
-    return ballistics_run<1, 1>(x, xmap, (int)C, z_alpha, 0, y, R, L, ws, ws_bytes, (hipStream_t)stream, &g);
+    return ballistics_run<1, 1>(x, xmap, (int)C, z_alpha, 0, y, R, L, ws, ws_bytes, (hipStream_t)stream, &g, zi, zf);
 }
 
 int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef, float* env,
                               int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
-    return ballistics_run<1>(x, xmap, (int)C, z_alpha, is_coef, env, R, L, ws, ws_bytes, (hipStream_t)stream);
+    return gfx_ballistics_energy_state_f32(x, xmap, C, z_alpha, is_coef, nullptr, nullptr, env, R, L, ws, ws_bytes, stream);
+}
+
+int gfx_ballistics_energy_state_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
+                                    const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
+                                    void* stream) {
+    return ballistics_run<1>(x, xmap, (int)C, z_alpha, is_coef, env, R, L, ws, ws_bytes, (hipStream_t)stream, nullptr, zi, zf);
 }
 
 }  // extern "C"

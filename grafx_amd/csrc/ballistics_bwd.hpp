@@ -22,6 +22,9 @@ constexpr int BROWS = 64;   // (columns per tile: a template parameter of the ke
 // instead: chunk aggregates, a chain over the chunks, then the walk with the true carries.  Per-chunk sums of the two coefficient gradients go to `part` (chunks x R x 2) and are
 // added in chunk order by ballistics_bwd_finish_kernel: the same bits from run to run.  part == nullptr: one chunk, gz
 // written directly (gfx_ballistics_bwd_f32).
+// With a state (gfx_ballistics_bwd_state_f32) y[-1] = zi[row] instead of 1 -- the comparison at n = 0 is x[0] < zi and the
+// coefficient-gradient term there lambda[0] (x[0] - zi) -- and the carry that LEAVES sample 0, (1 - c[0]) lambda[0], is
+// dL/dzi: written to gzi by whichever workgroup walks sample 0 with the true carry.
 constexpr float BWD_CMIN = 0.0103f;   // (1 - 0.0103)^2048 = 6e-10
 constexpr int64_t BWD_WARM = 2048;
 
@@ -30,7 +33,9 @@ __global__ __launch_bounds__(64) void ballistics_bwd_kernel(const float* __restr
                                                             const float* __restrict__ g,
                                                             const float* __restrict__ z_alpha, float* __restrict__ gx,
                                                             float* __restrict__ gz, int64_t R, int64_t L, int64_t chunk,
-                                                            float* __restrict__ part, float* __restrict__ agg = nullptr) {
+                                                            float* __restrict__ part, float* __restrict__ agg = nullptr,
+                                                            const float* __restrict__ zi = nullptr,
+                                                            float* __restrict__ gzi = nullptr) {
     constexpr int BCOLS = BC, BPAD = BC + 4, LPR = BC / 4, RPP = 64 / LPR;   // lanes per row, rows per cooperative pass
     __shared__ __attribute__((aligned(16))) float tx[BROWS * BPAD], ty[BROWS * BPAD], tg[BROWS * BPAD];
     const int lane = threadIdx.x;
@@ -42,6 +47,7 @@ __global__ __launch_bounds__(64) void ballistics_bwd_kernel(const float* __restr
         rt = sigmoidf(z_alpha[2 * my + 1]);
     }
     float carry = 0.0f, sa = 0.0f, sr = 0.0f, prod = 1.0f;
+    const float y_first = (zi && my < R) ? zi[my] : 1.0f;   // y[-1]
     const int cr = lane / LPR, cc = (lane % LPR) * 4;
     const bool vec = (L % 4 == 0) && vec_ok(x) && vec_ok(y) && vec_ok(g) && vec_ok(gx);
     const int64_t ntiles = (L + BCOLS - 1) / BCOLS;
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(64) void ballistics_bwd_kernel(const float* __restr
             *reinterpret_cast<float4*>(&ty[row * BPAD + cc]) = make_float4(b[0], b[1], b[2], b[3]);
             *reinterpret_cast<float4*>(&tg[row * BPAD + cc]) = make_float4(c[0], c[1], c[2], c[3]);
         }
-        const float y_before = (my < R && n0 > 0) ? y[my * L + n0 - 1] : 1.0f;  // y[-1] = 1
+        const float y_before = (my < R && n0 > 0) ? y[my * L + n0 - 1] : y_first;
         __syncthreads();
         // four steps per LDS access (rows are 68 floats apart: sixteen lanes' 16-byte accesses tile the 64 banks); past the
         // row's end the tiles hold x = y = g = 0 -- a zero gradient entering a zero carry, whatever the branch
@@ -138,6 +144,7 @@ __global__ __launch_bounds__(64) void ballistics_bwd_kernel(const float* __restr
         }
         return;
     }
+    if (gzi && my < R && t_lo == 0) gzi[my] = carry;   // (the chunk that holds sample 0, walked with the carry that enters it)
     if (my < R) {
         if (part) {
             part[((int64_t)blockIdx.y * R + my) * 2] = sa;
@@ -181,10 +188,7 @@ extern "C" {
 
 int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
                            int64_t R, int64_t L, void* stream) {
-    if (!x || !y || !g || !z_alpha || !gx || !gz || R <= 0 || L <= 0) return GFX_EINVAL;
-    hipLaunchKernelGGL(ballistics_bwd_kernel<64>, dim3((unsigned)((R + BROWS - 1) / BROWS)), dim3(64), 0,
-                       (hipStream_t)stream, x, y, g, z_alpha, gx, gz, R, L, (int64_t)0, (float*)nullptr);
-    return GFX_LAUNCH_OK();
+    return gfx_ballistics_bwd_state_f32(x, y, g, z_alpha, nullptr, gx, gz, nullptr, R, L, nullptr, 0, stream);
 }
 
 // chunks of the chunked adjoint: enough workgroups for ~16 waves per CU, chunks of at least 4096 samples (the 2048-sample
@@ -213,17 +217,34 @@ int gfx_ballistics_bwd_ws_f32(const float* x, const float* y, const float* g, co
                               int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || !g || !z_alpha || !gx || !gz || R <= 0 || L <= 0) return GFX_EINVAL;
     int chunks;
+    ballistics_bwd_chunk(R, L, &chunks);
+    if (chunks > 1 && !ws) return GFX_ENOSPC;
+    // (one chunk: the whole-row walk, whatever the workspace)
+    return gfx_ballistics_bwd_state_f32(x, y, g, z_alpha, nullptr, gx, gz, nullptr, R, L, chunks > 1 ? ws : nullptr, ws_bytes, stream);
+}
+
+int gfx_ballistics_bwd_state_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
+                                 float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !y || !g || !z_alpha || !gx || !gz || R <= 0 || L <= 0) return GFX_EINVAL;
+    int chunks;
     const int64_t chunk = ballistics_bwd_chunk(R, L, &chunks);
-    if (chunks <= 1) return gfx_ballistics_bwd_f32(x, y, g, z_alpha, gx, gz, R, L, stream);
-    if (!ws || ws_bytes < (size_t)chunks * R * 4 * sizeof(float)) return GFX_ENOSPC;
+    if (!ws || chunks <= 1) {   // every row walked whole by one lane
+        hipLaunchKernelGGL(ballistics_bwd_kernel<64>, dim3((unsigned)((R + BROWS - 1) / BROWS)), dim3(64), 0,
+                           (hipStream_t)stream, x, y, g, z_alpha, gx, gz, R, L, (int64_t)0, (float*)nullptr, (float*)nullptr, zi,
+                           gzi);
+        return GFX_LAUNCH_OK();
+    }
+    if (ws_bytes < (size_t)chunks * R * 4 * sizeof(float)) return GFX_ENOSPC;
     float* part = (float*)ws;
     float* agg = part + (size_t)chunks * R * 2;
     const dim3 grid((unsigned)((R + BROWS - 1) / BROWS), (unsigned)chunks);
     hipStream_t st = (hipStream_t)stream;
     // (32-column tiles: 28 KB of LDS per one-wave workgroup, five per CU; 64 columns 6.4 ms, 32 4.9, 16 5.6 at 9216 rows)
-    hipLaunchKernelGGL((ballistics_bwd_kernel<32, true>), grid, dim3(64), 0, st, x, y, g, z_alpha, gx, gz, R, L, chunk, part, agg);
+    hipLaunchKernelGGL((ballistics_bwd_kernel<32, true>), grid, dim3(64), 0, st, x, y, g, z_alpha, gx, gz, R, L, chunk, part, agg, zi,
+                       (float*)nullptr);
     hipLaunchKernelGGL(ballistics_bwd_carry_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, agg, R, chunks);
-    hipLaunchKernelGGL((ballistics_bwd_kernel<32, false>), grid, dim3(64), 0, st, x, y, g, z_alpha, gx, gz, R, L, chunk, part, agg);
+    hipLaunchKernelGGL((ballistics_bwd_kernel<32, false>), grid, dim3(64), 0, st, x, y, g, z_alpha, gx, gz, R, L, chunk, part, agg,
+                       zi, gzi);
     hipLaunchKernelGGL(ballistics_bwd_finish_kernel, dim3((unsigned)((2 * R + 255) / 256)), dim3(256), 0, st, (const float*)part,
                        z_alpha, gz, R, chunks);
     return GFX_LAUNCH_OK();

@@ -922,12 +922,26 @@ def _overlap(a, b):
     return a0 < b1 and b0 < a1
 
 
+def _ballistics_state(zi, R, what):
+    """The entering state of the ballistics entries: None (y[-1] = 1) or a contiguous float32 GPU tensor (R,), one value per
+    signal row.  The kernels read it in place, more than once per call."""
+    if zi is None:
+        return None
+    if not isinstance(zi, torch.Tensor) or not zi.is_cuda or zi.dtype != torch.float32 or tuple(zi.shape) != (R,) \
+            or not zi.is_contiguous():
+        got = f"{tuple(zi.shape)} {zi.dtype} on {zi.device}" if isinstance(zi, torch.Tensor) else type(zi).__name__
+        raise ValueError(f"{what}: zi must be a contiguous float32 GPU tensor of shape ({R},), got {got}")
+    return zi
+
+
 @_on_device
-def ballistics(u, z_alpha, coefficients=False, schedule=None, flags=None):
+def ballistics(u, z_alpha, coefficients=False, schedule=None, flags=None, zi=None, return_state=False):
     """Ballistics.forward (core/envelope.py:84-101) on (R, L) rows: the float32 sequential recursion, bit for bit, whichever
     schedule produces it.  ``coefficients``: ``z_alpha`` holds (at, rt) themselves instead of their logits.
     ``flags``: a list that receives the per-row int32 flags of the chunked schedule (1 = the row was walked whole by the
-    last launch: its coefficient is too slow for a chunk, or a chunk boundary failed the bit check) -- diagnostics."""
+    last launch: its coefficient is too slow for a chunk, or a chunk boundary failed the bit check) -- diagnostics.
+    ``zi`` (R,): y[-1] of every row instead of 1; ``return_state``: -> (y, zf), zf (R,) = y[:, L-1] -- handed to the next
+    block as its ``zi``, the blocks are the one-call output in the same bits."""
     schedule = BALLISTICS_SCHEDULE if schedule is None else schedule
     if schedule not in ("chunks", "rows"):
         raise ValueError(f"ballistics: unknown schedule {schedule!r}")
@@ -941,18 +955,28 @@ def ballistics(u, z_alpha, coefficients=False, schedule=None, flags=None):
     if schedule == "chunks":
         # zeroed: the single-pass schedules (short rows, very many rows) never write the flags this buffer is returned as
         ws = torch.zeros(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=u.device)
+    zi = _ballistics_state(zi, R, "ballistics")
+    zf = torch.empty(R, dtype=torch.float32, device=u.device) if return_state else None
     with _timed("ballistics_walk_kernel", 8 * R * L):
-        check(lib().gfx_ballistics_ws_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(y), R, L, _ptr(ws),
-                                          0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_ws_f32")
+        if zi is None and zf is None:
+            check(lib().gfx_ballistics_ws_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(y), R, L, _ptr(ws),
+                                              0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_ws_f32")
+        else:
+            check(lib().gfx_ballistics_state_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(y), R, L,
+                                                 _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                  "gfx_ballistics_state_f32")
     if flags is not None and ws is not None:
         flags.append(ws.view(torch.int32))
-    return y
+    return (y, zf) if return_state else y
 
 
 @_on_device
-def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, gate, out=None, param_rows=None, schedule=None):
+def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, gate, out=None, param_rows=None, schedule=None,
+                        zi=None, return_state=False):
     """Compressor / NoiseGate with the ballistics energy smoother and no gain smoother in one pass over ``x`` ((R, C, L) or
-    a strided (B, n, C, L) view): gfx_dynamics_ballistics_f32.  ``z_alpha``: (param_rows, 2)."""
+    a strided (B, n, C, L) view): gfx_dynamics_ballistics_f32.  ``z_alpha``: (param_rows, 2).  ``zi`` (R,), one value per
+    SIGNAL row: the envelope entering the block; ``return_state``: -> (out, zf), the envelope leaving it (the kernel never
+    stores the envelope itself)."""
     schedule = BALLISTICS_SCHEDULE if schedule is None else schedule
     _require_gpu(x, out, z_alpha)
     xmap, R, C, L = rowmap(x)
@@ -970,19 +994,29 @@ def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, ga
     ws = None
     if schedule == "chunks":
         ws = torch.empty(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=x.device)
+    zi = _ballistics_state(zi, R, "dynamics_ballistics")
+    zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     pin = _Pin()
     with _timed("ballistics_walk_kernel", 8 * R * C * L):
-        check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
-                                                pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P, R, C, L,
-                                                KNEES[knee], int(gate), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-              "gfx_dynamics_ballistics_f32")
-    return out
+        if zi is None and zf is None:
+            check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
+                                                    pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P, R, C, L,
+                                                    KNEES[knee], int(gate), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                  "gfx_dynamics_ballistics_f32")
+        else:
+            check(lib().gfx_dynamics_ballistics_state_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
+                                                          pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P,
+                                                          R, C, L, KNEES[knee], int(gate), _ptr(zi), _ptr(zf), _ptr(ws),
+                                                          0 if ws is None else ws.numel(), _stream()),
+                  "gfx_dynamics_ballistics_state_f32")
+    return (out, zf) if return_state else out
 
 
 @_on_device
-def ballistics_energy(x, z_alpha, coefficients=False, schedule=None):
+def ballistics_energy(x, z_alpha, coefficients=False, schedule=None, zi=None, return_state=False):
     """ballistics(mean_c x^2) in one pass over x ((R, C, L) or a strided (B, n, C, L) view) -> (R, L): the envelope of
-    Compressor / NoiseGate with energy_smoother="ballistics" (dynamics.py:390, core/envelope.py:84-101)."""
+    Compressor / NoiseGate with energy_smoother="ballistics" (dynamics.py:390, core/envelope.py:84-101).  ``zi`` /
+    ``return_state``: as :func:`ballistics`."""
     schedule = BALLISTICS_SCHEDULE if schedule is None else schedule
     _require_gpu(x, z_alpha)
     xmap, R, C, L = rowmap(x)
@@ -993,16 +1027,25 @@ def ballistics_energy(x, z_alpha, coefficients=False, schedule=None):
     ws = None
     if schedule == "chunks":
         ws = torch.empty(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=x.device)
+    zi = _ballistics_state(zi, R, "ballistics_energy")
+    zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     with _timed("ballistics_walk_kernel", 4 * R * (C + 1) * L):
-        check(lib().gfx_ballistics_energy_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(env), R, L, _ptr(ws),
-                                              0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_energy_f32")
-    return env
+        if zi is None and zf is None:
+            check(lib().gfx_ballistics_energy_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(env), R, L, _ptr(ws),
+                                                  0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_energy_f32")
+        else:
+            check(lib().gfx_ballistics_energy_state_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf),
+                                                        _ptr(env), R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                  "gfx_ballistics_energy_state_f32")
+    return (env, zf) if return_state else env
 
 
 @_on_device
-def ballistics_bwd(x, y, g, z_alpha, schedule="chunks"):
+def ballistics_bwd(x, y, g, z_alpha, schedule="chunks", zi=None):
     """Adjoint of :func:`ballistics`: -> (dL/dx (R,L), dL/dz_alpha (R,2)).  ``schedule``: "chunks" (rows cut into chunks
-    with a 2048-sample warm-up, gfx_ballistics_bwd_ws_f32) or "rows" (every row walked whole by one lane)."""
+    with a 2048-sample warm-up, gfx_ballistics_bwd_ws_f32) or "rows" (every row walked whole by one lane).  ``zi`` (R,): the
+    state the forward entered with; -> (gx, gz, dL/dzi (R,)) (gfx_ballistics_bwd_state_f32).  A cotangent of the final state
+    is a cotangent of y[:, L-1]: add it to ``g`` there."""
     _require_gpu(x, y, g, z_alpha)
     x, y, g, z_alpha = x.contiguous(), y.contiguous(), g.contiguous(), z_alpha.contiguous()
     R, L = x.shape
@@ -1010,6 +1053,16 @@ def ballistics_bwd(x, y, g, z_alpha, schedule="chunks"):
     _expect(g, (R, L), "ballistics_bwd: g")
     _expect(z_alpha, (R, 2), "ballistics_bwd: z_alpha")
     gx, gz = torch.empty_like(x), torch.empty((R, 2), dtype=torch.float32, device=x.device)
+    if zi is not None:
+        zi = _ballistics_state(zi, R, "ballistics_bwd")
+        gzi = torch.empty(R, dtype=torch.float32, device=x.device)
+        ws = None
+        if schedule != "rows":
+            ws = torch.empty(max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4), dtype=torch.uint8, device=x.device)
+        check(lib().gfx_ballistics_bwd_state_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(zi), _ptr(gx), _ptr(gz), _ptr(gzi),
+                                                 R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+              "gfx_ballistics_bwd_state_f32")
+        return gx, gz, gzi
     if schedule == "rows":
         check(lib().gfx_ballistics_bwd_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(gx), _ptr(gz), R, L, _stream()),
               "gfx_ballistics_bwd_f32")

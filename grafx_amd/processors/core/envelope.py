@@ -8,6 +8,13 @@ from ...autograd import needs_grad
 from .convolution import odd_length_alias, reference_aliases, resolve_flashfftconv
 
 
+def no_carried_state(iir_len):
+    """Why the truncated one-pole refuses ``state`` / ``return_state``."""
+    return (f"the truncated one-pole smoother (\"iir\") has a finite memory of iir_len - 1 = {iir_len - 1} samples and no "
+            "carried state: processing in blocks would need that many past input samples, not a state.  Use "
+            "energy_smoother=\"ballistics\" (gain_smoother=\"ballistics\"), whose state is one value per row")
+
+
 class TruncatedOnePoleIIRFilter(nn.Module):
     """y = relu(u * h), h[n] = (1-a) a^n for n < iir_len, a = min(sigmoid(z), 1-1e-5).
 
@@ -21,7 +28,9 @@ class TruncatedOnePoleIIRFilter(nn.Module):
         # upstream: FIRConvolution(mode="causal", **backend_kwargs) (envelope.py:32) -> warning + native convolve()
         self.flashfftconv = resolve_flashfftconv(flashfftconv)
 
-    def forward(self, input_signals, z_alpha):
+    def forward(self, input_signals, z_alpha, state=None, return_state=False):
+        if state is not None or return_state:
+            raise ValueError(no_carried_state(self.iir_len))
         if needs_grad(input_signals, z_alpha):
             return diff.truncated_one_pole(input_signals, z_alpha, self.iir_len, exact=self.flashfftconv)
         L = input_signals.shape[-1]
@@ -58,7 +67,22 @@ class TruncatedOnePoleIIRFilter(nn.Module):
 class Ballistics(nn.Module):
     """Attack/release one-pole recursion (torchcomp.compressor_core semantics as recalled)."""
 
-    def forward(self, input_signals, z_alpha):
-        if needs_grad(input_signals, z_alpha):
-            return diff.BallisticsFn.apply(input_signals, z_alpha)
-        return ops.ballistics(input_signals, z_alpha)
+    def forward(self, input_signals, z_alpha, state=None, return_state=False):
+        """``state``: float32 (R,) for (R, L) rows, the envelope the block is entered with (None: the reference's zi = 1);
+        ``return_state``: -> (y, state), the envelope the block leaves -- the next block's ``state``.  Blocks processed
+        this way are the one-call output bit for bit."""
+        if state is None and not return_state:
+            if needs_grad(input_signals, z_alpha):
+                return diff.BallisticsFn.apply(input_signals, z_alpha)
+            return ops.ballistics(input_signals, z_alpha)
+        if needs_grad(input_signals, z_alpha, state):
+            R = input_signals.shape[0]
+            if state is None:
+                state = torch.ones(R, dtype=torch.float32, device=input_signals.device)
+            elif tuple(state.shape) != (R,) or state.dtype != torch.float32 or not state.is_cuda:
+                raise ValueError(f"Ballistics: state must be a float32 GPU tensor of shape ({R},), got {tuple(state.shape)} "
+                                 f"{state.dtype} on {state.device}")
+            y, zf = diff.BallisticsStateFn.apply(input_signals, z_alpha, state)
+        else:
+            y, zf = ops.ballistics(input_signals, z_alpha, zi=None if state is None else state.contiguous(), return_state=True)
+        return (y, zf) if return_state else y

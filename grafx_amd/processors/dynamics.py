@@ -7,7 +7,7 @@ from .. import ops
 from ..autograd import needs_grad
 from .core._buffer_io import BufferIO, expand_shared, shared_reps
 from .core.convolution import reference_aliases, resolve_flashfftconv
-from .core.envelope import Ballistics, TruncatedOnePoleIIRFilter
+from .core.envelope import Ballistics, TruncatedOnePoleIIRFilter, no_carried_state
 
 
 class _Dynamics(BufferIO, nn.Module):
@@ -47,10 +47,15 @@ class _Dynamics(BufferIO, nn.Module):
         return self.forward(x4, _out=out4, _shared_rows=_shared_rows, _aux=_aux, **extra, **params)
 
     def forward(self, input_signals, log_threshold, log_ratio, log_knee=None, z_alpha_pre=None, z_alpha_post=None,
-                _out=None, _shared_rows=None, _aux=None, _mix=None):
+                _out=None, _shared_rows=None, _aux=None, _mix=None, state=None, return_state=False):
         """``_aux = (store, key)`` (render_grafx's training path): the tape-free forward render leaves the smoother's scan
         in ``store[key]`` and the stage-wise backward, which re-traces this call on the same rows, hands it to the
-        autograd node, so that the backward does not have to scan the input again."""
+        autograd node, so that the backward does not have to scan the input again.
+
+        ``state`` / ``return_state``: processing in blocks, see :meth:`_forward_blocks`."""
+        if state is not None or return_state:
+            return self._forward_blocks(input_signals, log_threshold, log_ratio, log_knee, z_alpha_pre, z_alpha_post, _out,
+                                        _shared_rows, state, return_state)
         if _shared_rows is not None and (needs_grad(input_signals, log_threshold, log_ratio, log_knee, z_alpha_pre,
                                                     z_alpha_post) or self.gain_smoother is not None
                                          or (self.energy_smoother == "ballistics" and self.gain_smoother is not None)
@@ -107,6 +112,70 @@ class _Dynamics(BufferIO, nn.Module):
             return ops.apply_gain(input_signals, self.gain_smoother_module(g, z_alpha=z_alpha_post), exp_gain=True, out=_out)
         gain = ops.dyn_gain(energy, log_threshold, log_ratio, log_knee, self.knee, self._gate, log_out=False)
         return ops.apply_gain(input_signals, self.gain_smoother_module(gain, z_alpha=z_alpha_post), out=_out)
+
+    def _forward_blocks(self, x, log_threshold, log_ratio, log_knee, z_alpha_pre, z_alpha_post, _out, _shared_rows, state,
+                        return_state):
+        """forward() of one block of a longer signal.  ``state``: float32 (R, S) -- (B, n, S) for a (B, n, C, L) view --, S the
+        number of "ballistics" smoothers of the module: column 0 the energy smoother's envelope, the last column the gain
+        smoother's, as the block before left them (None: the first block, every smoother starts from 1 as in a plain call).
+        ``return_state``: -> (y, state).  The envelopes of the blocks are the one-call envelopes bit for bit."""
+        if "iir" in (self.energy_smoother, self.gain_smoother):
+            raise ValueError(f"{type(self).__name__}: " + no_carried_state(self.iir_len))
+        pre, post = self.energy_smoother == "ballistics", self.gain_smoother == "ballistics"
+        S = int(pre) + int(post)
+        if S == 0:
+            raise ValueError(f"{type(self).__name__} without a smoother has no memory: there is no state to carry")
+        lead = tuple(x.shape[:-2])
+        R = lead[0] * (lead[1] if x.ndim == 4 else 1)
+        if state is not None and (tuple(state.shape) != (*lead, S) or state.dtype != torch.float32 or not state.is_cuda):
+            raise ValueError(f"{type(self).__name__}: state must be a float32 GPU tensor of shape {(*lead, S)} (one column per "
+                             f"ballistics smoother), got {tuple(state.shape)} {state.dtype} on {state.device}")
+        cols = None if state is None else state.reshape(R, S)
+        s_pre = None if cols is None or not pre else cols[:, 0].contiguous()
+        s_post = None if cols is None or not post else cols[:, -1].contiguous()
+        if _shared_rows is not None:   # one parameter row per signal row, as forward()'s other unshared paths
+            reps = shared_reps(x, _shared_rows)
+            log_threshold, log_ratio, log_knee, z_alpha_pre, z_alpha_post = (
+                expand_shared(t, reps) for t in (log_threshold, log_ratio, log_knee, z_alpha_pre, z_alpha_post))
+        if self.knee == "hard":
+            log_knee = None
+        out = []
+        if needs_grad(x, log_threshold, log_ratio, log_knee, z_alpha_pre, z_alpha_post, state):
+            x3 = x.reshape(-1, *x.shape[-2:])
+            energy = x3.square().mean(-2)
+            if pre:
+                energy, zf = self.energy_smoother_module(energy, z_alpha=z_alpha_pre, state=s_pre, return_state=True)
+                out.append(zf)
+            g = diff.log_gain(torch.log(energy + 1e-5), log_threshold - 6, log_ratio, log_knee, self.knee, self._gate)
+            if not post:
+                gain = torch.exp(g)
+            else:
+                gain, zf = self.gain_smoother_module(g if self.gain_smooth_in_log else torch.exp(g), z_alpha=z_alpha_post,
+                                                     state=s_post, return_state=True)
+                out.append(zf)
+                if self.gain_smooth_in_log:
+                    gain = torch.exp(gain)
+            y = (gain[:, None, :] * x3).view(x.shape)
+            if _out is not None:
+                _out.copy_(y.view(_out.shape))
+                y = _out
+        elif not post:   # the one-pass kernel (gfx_dynamics_ballistics_state_f32)
+            y, zf = ops.dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha_pre, self.knee, self._gate, out=_out,
+                                            zi=s_pre, return_state=True)
+            out.append(zf)
+        else:
+            if pre:
+                energy, zf = ops.ballistics_energy(x, z_alpha_pre, zi=s_pre, return_state=True)
+                out.append(zf)
+            else:
+                energy = ops.energy(x)
+            g = ops.dyn_gain(energy, log_threshold, log_ratio, log_knee, self.knee, self._gate, log_out=self.gain_smooth_in_log)
+            gain, zf = self.gain_smoother_module(g, z_alpha=z_alpha_post, state=s_post, return_state=True)
+            out.append(zf)
+            y = ops.apply_gain(x, gain, exp_gain=self.gain_smooth_in_log, out=_out)
+        if _out is None:
+            y = y.view(x.shape)
+        return (y, torch.stack(out, -1).view(*lead, S)) if return_state else y
 
     def reads_grad_source(self, length):
         """Whether the differentiable forward of a signal of this length is the ONE native node (DynamicsFn) that can take
@@ -255,7 +324,9 @@ class BaseEnvelopeFollower(nn.Module):
         self.detect_with = detect_with
         self.smoother = smoother
 
-    def forward(self, signal, *args, **kwargs):
+    def forward(self, signal, *args, state=None, return_state=False, **kwargs):
+        """``state`` / ``return_state``: handed to a smoother that carries one (Ballistics: float32 (R,)); the result is then
+        ``(log(y + 1e-5), state)``, and a signal followed in blocks is the signal followed in one call."""
         if self.detect_with == "energy":
             loudness = signal.square().mean(-2) if needs_grad(signal) else ops.energy(signal)
         elif self.detect_with == "amplitude":
@@ -263,7 +334,10 @@ class BaseEnvelopeFollower(nn.Module):
         else:
             raise AttributeError('detect_with="rms_channel" reads an attribute (eps) that upstream never defines '
                                  "(dynamics.py:1071); it cannot be used there either")
-        return torch.log(self.smoother(loudness, *args, **kwargs) + 1e-5)
+        if state is None and not return_state:
+            return torch.log(self.smoother(loudness, *args, **kwargs) + 1e-5)
+        y, state = self.smoother(loudness, *args, state=state, return_state=True, **kwargs)
+        return (torch.log(y + 1e-5), state) if return_state else torch.log(y + 1e-5)
 
     def parameter_size(self):
         return self.smoother.parameter_size()

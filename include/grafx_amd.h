@@ -414,6 +414,22 @@ int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, cons
 int gfx_dynamics_ballistics_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
                                 const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
                                 int64_t R, int64_t C, int64_t L, int knee, int gate, void* ws, size_t ws_bytes, void* stream);
+/* State across calls.  The three entries above with y[-1] = zi[r] instead of 1 for signal row r (zi: (R), NULL = 1; never
+ * indexed by param_rows) and y[L-1] of every row left in zf ((R), NULL = not wanted), in the sequential recursion's bits
+ * whichever schedule produced them: a signal cut anywhere and processed block by block, each block entering with the zf of
+ * the block before, gives the one-call output bit for bit (gfx_dynamics_ballistics_state_f32: the one-call ENVELOPE; the
+ * gain computer's output is the same bits when the blocks take the same kernel form, L % 4 == 0 on aligned rows).  Later
+ * launches of a call re-read zi for the rows they walk again, so zi and zf must not overlap: GFX_EINVAL.  With
+ * zi = zf = NULL these are the entries above. */
+int gfx_ballistics_state_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
+                             int64_t L, void* ws, size_t ws_bytes, void* stream);
+int gfx_ballistics_energy_state_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
+                                    const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
+                                    void* stream);
+int gfx_dynamics_ballistics_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
+                                      const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
+                                      int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
+                                      size_t ws_bytes, void* stream);
 /* Adjoint of the recursion above given the forward input x, output y and g = dL/dy:
  * gx = dL/dx (R, L), gz = dL/dz_alpha (R, 2).  The attack/release choice is treated as locally constant. */
 int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
@@ -425,6 +441,11 @@ int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const
 size_t gfx_ballistics_bwd_ws_bytes(int64_t R, int64_t L);
 int gfx_ballistics_bwd_ws_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
                               int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
+/* The adjoint with a state: y[-1] = zi[r] (NULL = 1), and gzi (R; NULL = not wanted) receives dL/dzi = (1 - c[0]) lambda[0],
+ * the carry that leaves sample 0.  A cotangent of zf is a cotangent of y[L-1]: the caller adds it to g[:, L-1].  ws == NULL:
+ * every row walked whole (gfx_ballistics_bwd_f32); otherwise the chunks of gfx_ballistics_bwd_ws_f32. */
+int gfx_ballistics_bwd_state_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
+                                 float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
 int gfx_dyn_gain_f32(const float* env, float* gain, const float* log_threshold, const float* log_ratio,
                      const float* log_knee, int64_t R, int64_t L, int knee, int gate, int log_out, void* stream);
 /* Backward of the gain computer, for the training path (forward: gfx_dynamics_fused_f32).
