@@ -227,16 +227,33 @@ def odd_alias(z, lo=0, length=None, precise=False):
     return OddAliasFn.apply(z, lo, length, bool(precise))
 
 
-def convolve(x, h, mode="causal", exact=False, final=False, precise=False):
+def convolve(x, h, mode="causal", exact=False, final=False, precise=False, state=None, return_state=False):
     """Differentiable twin of processors.core.convolution.convolve (reference core/convolution.py:119-134),
     including the odd-P aliasing (OddAliasFn).  ``final``: the result is the calling processor's output up to linear
-    operations (see tape_only)."""
+    operations (see tape_only).
+
+    ``state`` / ``return_state`` (causal mode): one block of a stream -- LinearConvFn over ``cat(state, x)`` at
+    ``off = N - 1``, ``Lout = L`` (always the linear convolution), the leaving state sliced from the same concatenation:
+    x, h and state all receive gradients from the cotangents of y and of the state, with no backward kernel of its own.
+    The concatenated copy is the price of the training path; inference reads the history in place (ops.fftconv_state)."""
     from .processors.core.convolution import reference_aliases
 
     flat = x.ndim == 2
     if flat:
         x, h = x.unsqueeze(1), h.unsqueeze(1)
+        state = None if state is None else state.unsqueeze(1)
     L, N = x.shape[-1], h.shape[-1]
+    if state is not None or return_state:
+        if mode != "causal":
+            raise ValueError(f"convolve: a carried state is the past of a causal convolution, mode={mode!r} has none")
+        lead = x.shape[:-1]
+        hist = x.new_zeros(*lead, N - 1) if state is None else state.reshape(*lead, N - 1)
+        xx = torch.cat([hist, x], -1)
+        y = LinearConvFn.apply(xx, h, L, N - 1, final)
+        zf = xx[..., L:].reshape(-1, x.shape[-2], N - 1).contiguous()
+        if flat:
+            y, zf = y.squeeze(1), zf.squeeze(1)
+        return (y, zf) if return_state else y
     if not reference_aliases(L, N, exact):
         if mode == "causal":
             y = LinearConvFn.apply(x, h, L, 0, final)

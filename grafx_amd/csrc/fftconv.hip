@@ -11,6 +11,8 @@
 //   macinv_pair_kernel  N > 8193: two output tiles per 512-thread workgroup, sum_p X[i-p] * H[p] in registers -> 2 x IFFT -> store
 //   macinv_kernel   the same with one output tile per 256-thread workgroup (GFX_SCHED_TILE)
 //   winmac_kernel / corr1_kernel / gfx_fftconv_pipe_*, gfx_corr_pipe (generated assembly): see below
+//   fftconv1_state_kernel / xspec_state_kernel / winmac_state_kernel: the window-loading kernels with the N - 1 samples
+//                   before the row read from a carried history (streaming, gfx_fftconv_state_f32); fir_state_kernel: the next one
 //
 // Algorithmic bytes: 4*(C_in + C_out) per output frame per row (read x once, write y once);
 // the tile overlap (N-1 of 16384 samples) is re-read through L2.
@@ -160,6 +162,35 @@ __device__ __forceinline__ void load_window(cx (&v)[32], const float* __restrict
     }
 }
 
+// The window of a streamed block (gfx_fftconv_state_f32): load_window, with the N - 1 samples before the row taken from the
+// row's carried history -- v holds hist[n + N - 1] for sample indices -(N-1) <= n < 0 and zero below that.  The windows of
+// the tile geometry start a whole number of 512-sample register rows before (or after) sample 0, so a register row lies
+// wholly in the history or wholly in the signal: one uniform test per row, the signal rows exactly as load_window's fast
+// form reads them.  History rows are read as single dwords with a mask per dword: N - 1 may be odd, so a history pair is
+// only 4-byte aligned (8-byte loads would be misaligned on every other row-channel), and when N is even the pair
+// (n, n + 1) = (-N, -(N-1)) straddles the start of the history -- its first half is zero, its second hist[0].  No pair
+// reaches past the end of the history: n is even and below 0, so n + 1 <= -1.
+__device__ __forceinline__ float buf_load_f1(rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+__device__ __forceinline__ void load_window_hist(cx (&v)[32], const float* __restrict__ row, const float* __restrict__ hist,
+                                                 int64_t s, int64_t L, int64_t N, int t) {
+    const rsrc_t r = make_rsrc(row + s, (L - s) * 4);
+    const rsrc_t hr = make_rsrc(hist, (N - 1) * 4);
+    const int a_lo = s < 0 ? (int)((-s) >> 9) : 0;             // register rows before sample 0 (uniform)
+    const int h0 = (int)(s + N - 1) + 2 * t;                   // history index of this lane's pair in register row 0
+#pragma unroll
+    for (int a = 0; a < 32; ++a) {
+        if (a < a_lo) {
+            const int h = h0 + 512 * a;                        // -16384 < h: a negative index never wraps into the range
+            const uint32_t lo = h >= 0 ? 4u * (uint32_t)h : OOB, hi = h >= -1 ? 4u * (uint32_t)(h + 1) : OOB;
+            v[a] = cx{buf_load_f1(hr, lo, 0), buf_load_f1(hr, hi, 0)};
+        } else {
+            v[a] = buf_load_f2(r, 8u * (uint32_t)t, 2048u * a);
+        }
+    }
+}
+
 // Time-reversed window of a segment of `len` (<= 16384) samples: v[a] = (seg[len-1-2m], seg[len-2-2m]), m = t + 256 a,
 // zero below the segment.  Lets the filter-gradient correlation use the signal as its own "filter" without a flipped
 // copy of it.
@@ -282,89 +313,17 @@ __global__ __launch_bounds__(TILE_T, 2) void hspec_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-template <bool TEE>
-__global__ __launch_bounds__(TILE_T, 2) void fftconv1_kernel(const float* __restrict__ x, const float4* __restrict__ Hs,
-                                                             float* __restrict__ y, float* __restrict__ xcopy,
-                                                             ConvArgs a, const float2* __restrict__ twtab,
-                                                             uint32_t* __restrict__ rowmax = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) cx lds[];
-    const int t = threadIdx.x;
-    const unsigned lb = xcd_logical_block();
-    if (lb >= (unsigned)a.nblocks) return;
-    const unsigned ntiles = (unsigned)a.ntiles;
-    const unsigned rco = lb / ntiles;
-    const int64_t tile = lb - rco * ntiles;
-    const unsigned r = rco / (unsigned)a.Cout;
-    const int c = (int)(rco - r * (unsigned)a.Cout);
-    const float* xrow = x + row_off(a.xmap, r, a.Cin == 1 ? 0 : c);
-    float* yrow = y + row_off(a.ymap, r, c);
-    const rsrc_t H = make_rsrc(Hs + ((int64_t)(r % a.hrows) * a.Cf + (a.Cf == 1 ? 0 : c)) * H_TILE_F4, H_TILE_F4 * 16);
-
-    // Every global load of the tile is issued up front: the window, the twiddles, and the filter spectrum
-    // (needed only after the forward transform, by which time it has long arrived).  Left to itself the
-    // compiler issues each spectrum load right before its use and waits for it: 16 serialised L2 round trips.
-    TileTw tw;
-    cx v[32], w[2][16];
-    f4v hreg[H_SLOTS];
-    load_window(v, xrow, a.off + tile * a.V - a.O, a.L, t, 1.0f);
-    tile_twiddles(tw, twtab, t);
-#pragma unroll
-    for (int q = 0; q < H_SLOTS; ++q) hreg[q] = buf_load_f4(H, 16u * (uint32_t)t, 4096u * q);
-    __builtin_amdgcn_sched_barrier(0);
-    // off == 0 here: the window's valid part is x[tile*V, tile*V + V) itself
-    if (TEE) store_valid<true>(v, xcopy + row_off(a.cmap, r, c), tile * a.V, a.O, a.L, t);
-    tile_forward(v, w, tw, lds, t);
-    for_each_pair(t, tw.base(), [&](int slot, int ia, int ib, cx wk, bool self) {
-        cx xe, xo, ye, yo, za, zb;
-        pair_split(NAT(w, ia), NAT(w, ib), xe, xo);
-        pair_product(xe, xo, hreg[slot], wk, ye, yo);
-        pair_merge(ye, yo, za, zb);
-        NAT(w, ia) = za;
-        if (!self) NAT(w, ib) = zb;
-    });
-    // no barrier here: the inverse starts by writing S2 rows j = t and 512 - t, the very rows (and the only rows)
-    // this thread read at the end of the forward transform -- nobody else touches them in between
-    tile_inverse(w, v, tw, lds, t);
-    store_valid(v, yrow, tile * a.V, a.O, a.Lout, t);
-    if (rowmax) tile_rowmax(v, rowmax, rco, tile * a.V, a.O, a.Lout, t);   // (see tile_rowmax)
-}
-
-// ------------------------------------------------------------------------------------------------
-// window j (j = jj - (nparts-1)) of x starts at off - O + j*V; windows that miss [0, L) are skipped.
+// window j of x starts at off - O + j * hop; windows that miss [0, L) are skipped.
 __device__ __forceinline__ bool window_live(int64_t s, int64_t L) { return s + TILE_F > 0 && s < L; }
 
-__global__ __launch_bounds__(TILE_T, 2) void xspec_kernel(const float* __restrict__ x, float2* __restrict__ Zs,
-                                                          ConvArgs a, int64_t nwin,
-                                                          const float2* __restrict__ twtab) {
-    extern __shared__ __attribute__((aligned(16))) cx lds[];
-    const int t = threadIdx.x;
-    const unsigned lb = xcd_logical_block();
-    if (lb >= (unsigned)a.nblocks) return;
-    const unsigned rcx = lb / (unsigned)nwin;
-    const int64_t jj = lb - rcx * (unsigned)nwin;
-    const int64_t s = a.off - a.O + (jj - (a.nparts - 1)) * a.hop;
-    if (!window_live(s, a.L)) return;
-    const unsigned xr = rcx / (unsigned)a.Cin;
-    const float* xrow = x + row_off(a.xmap, xr, (int)(rcx - xr * (unsigned)a.Cin));
-    TileTw tw;
-    cx v[32], w[2][16];
-    load_window(v, xrow, s, a.L, t, 1.0f);
-    tile_twiddles(tw, twtab, t);
-    tile_forward(v, w, tw, lds, t);
-    // stored the way the filter spectra are: per mirrored bin pair one 16-byte entry (Xe, Xo) at [slot][t] (the seventeenth
-    // slot: thread 0 only), already split -- the product kernels fetch a pair with ONE instruction where two 8-byte rows
-    // cost the CU's address unit twice as much (a vector-memory instruction occupies it ~22 cycles whatever its width, and
-    // that is what bounds their loop), and thread 0's different pairing is settled here, once, instead of in every turn.
-    f4v* out = reinterpret_cast<f4v*>(Zs) + (int64_t)lb * H_TILE_F4;
-    for_each_pair(t, tw.base(), [&](int slot, int ia, int ib, cx, bool) {
-        cx xe, xo;
-        pair_split(NAT(w, ia), NAT(w, ib), xe, xo);
-        // (streamed: the product kernel starts after ALL windows are written, by when only the last tenth is still in
-        // a cache -- cfg3 2.05 -> 2.02 ms with the product kernel)
-        __builtin_nontemporal_store(__builtin_shufflevector(xe, xo, 0, 1, 2, 3), &out[slot * TILE_T + t]);
-    });
-}
+#define FC_STATE 0
+#include "fftconv_window_kernels.hpp"   // fftconv1_kernel, xspec_kernel, winmac_kernel
+#undef FC_STATE
+#define FC_STATE 1
+#include "fftconv_window_kernels.hpp"   // fftconv1_state_kernel, xspec_state_kernel, winmac_state_kernel
+#undef FC_STATE
 
+// ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TILE_T, 2) void macinv_kernel(const float2* __restrict__ Zs, const float4* __restrict__ Hs,
                                                            float* __restrict__ y, ConvArgs a, int64_t nwin,
                                                            const float2* __restrict__ twtab,
@@ -609,50 +568,24 @@ __global__ __launch_bounds__(2 * TILE_T, 1) void macinv_pair_kernel(const float2
     if (rowmax && (grp == 0 || two)) tile_rowmax(v, rowmax, rco, (tile + grp) * a.V, a.O, a.Lout, t);
 }
 
-// One output tile per row (ntiles == 1, the filter-gradient shape: a long "filter", few outputs): every signal window
-// meets exactly one filter partition, so its spectrum is used once -- transform it here instead of writing it to
-// a workspace (xspec_kernel) and reading it back (macinv_kernel).
-__global__ __launch_bounds__(TILE_T, 2) void winmac_kernel(const float* __restrict__ x, const float4* __restrict__ Hs,
-                                                           float* __restrict__ y, ConvArgs a,
-                                                           const float2* __restrict__ twtab) {
-    extern __shared__ __attribute__((aligned(16))) cx lds[];
-    const int t = threadIdx.x;
-    const unsigned rco = xcd_logical_block();
-    if (rco >= (unsigned)a.nblocks) return;
-    const unsigned r = rco / (unsigned)a.Cout;
-    const int c = (int)(rco - r * (unsigned)a.Cout);
-    const float* xrow = x + row_off(a.xmap, r, a.Cin == 1 ? 0 : c);
-    float* yrow = y + row_off(a.ymap, r, c);
-    const f4v* H = reinterpret_cast<const f4v*>(Hs) + ((int64_t)(r % a.hrows) * a.Cf + (a.Cf == 1 ? 0 : c)) * a.nparts * H_TILE_F4;
-
-    cx ye[H_SLOTS], yo[H_SLOTS];
+// zf = the last H = N - 1 samples of zi || x per input row-channel (zi == nullptr: zeros): the history the next block of
+// the stream enters with.  A copy, so bit-exact; for L < H the old history shifts down by L.  One workgroup per 1024
+// samples of a state row.
+__global__ __launch_bounds__(256) void fir_state_kernel(const float* __restrict__ x, gfx_rowmap_t xmap,
+                                                        const float* __restrict__ zi, float* __restrict__ zf, int Cin,
+                                                        int64_t L, int64_t H, unsigned chunks) {
+    const unsigned rc = blockIdx.x / chunks, ch = blockIdx.x - rc * chunks;
+    const unsigned r = rc / (unsigned)Cin;
+    const float* xrow = x + row_off(xmap, r, (int)(rc - r * (unsigned)Cin));
+    const float* zrow = zi ? zi + (int64_t)rc * H : nullptr;
+    float* out = zf + (int64_t)rc * H;
 #pragma unroll
-    for (int s = 0; s < H_SLOTS; ++s) ye[s] = yo[s] = cx{0.0f, 0.0f};
-    TileTw tw;
-    tile_twiddles(tw, twtab, t);
-    for (int p = 0; p < a.nparts; ++p) {
-        const int64_t s = a.off - a.O - (int64_t)p * a.hop;  // window of partition p for output tile 0
-        if (!window_live(s, a.L)) continue;
-        const f4v* Hp = H + (int64_t)p * H_TILE_F4;
-        cx v[32], w[2][16];
-        load_window(v, xrow, s, a.L, t, 1.0f);
-        tile_forward(v, w, tw, lds, t);
-        for_each_pair(t, tw.base(), [&](int slot, int ia, int ib, cx wk, bool) {
-            cx xe, xo;
-            pair_split(NAT(w, ia), NAT(w, ib), xe, xo);
-            pair_product_acc(xe, xo, Hp[slot * TILE_T + t], wk, ye[slot], yo[slot]);
-        });
-        __syncthreads();  // S2 reads of this window are done before the next window's S1 writes
+    for (int k = 0; k < 4; ++k) {
+        const int64_t j = (int64_t)ch * 1024 + k * 256 + threadIdx.x;
+        if (j >= H) continue;
+        const int64_t p = j + L - H;                           // index into x; negative: still in the old history
+        out[j] = p >= 0 ? xrow[p] : (zrow ? zrow[j + L] : 0.0f);
     }
-    cx pz[2][16], v[32];
-    for_each_pair(t, tw.base(), [&](int slot, int ia, int ib, cx, bool self) {
-        cx za, zb;
-        pair_merge(ye[slot], yo[slot], za, zb);
-        NAT(pz, ia) = za;
-        if (!self) NAT(pz, ib) = zb;
-    });
-    tile_inverse(pz, v, tw, lds, t);
-    store_valid(v, yrow, 0, a.O, a.Lout, t);
 }
 
 // Filter gradient of the short-filter convolution, gh[r,c,k] = sum_n g[r,cg,n] x[r,cx,n+off-k], k < N <= 8193, as a
@@ -1040,7 +973,8 @@ int gfx_fftconv_ex_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_
 static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
                          gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
                          int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, int schedule,
-                         void* stream, uint32_t* rowmax, int* rowmax_written);
+                         void* stream, uint32_t* rowmax, int* rowmax_written, bool state_call = false,
+                         const float* zi = nullptr);
 
 int gfx_fftconv_sched_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
                           gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
@@ -1063,7 +997,9 @@ int gfx_fftconv_rowmax_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, in
 static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
                          gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
                          int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, int schedule,
-                         void* stream, uint32_t* rowmax, int* rowmax_written) {
+                         void* stream, uint32_t* rowmax, int* rowmax_written, bool state_call, const float* zi) {
+    // state_call (gfx_fftconv_state_f32): never the persistent kernels; zi: the rows' carried history (NULL: silence, which
+    // is what the stateless kernels compute)
     if (schedule != GFX_SCHED_AUTO && schedule != GFX_SCHED_TILE && schedule != GFX_SCHED_PIPE) return GFX_EINVAL;
     if (!x || !Hs || !y || R <= 0 || L <= 0 || Lout <= 0 || N <= 0) return GFX_EINVAL;
     if (h_rows < 1 || h_rows > R || h_rows > 0x7fffffffLL) return GFX_EINVAL;
@@ -1098,7 +1034,8 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
     // the persistent hand-scheduled kernel: by name, or by AUTO once a launch is large enough to fill its pipeline
     PipeModule* pm = pipe_module();   // (loaded on the first call on a device, whatever the schedule: never mid-capture)
     if (schedule == GFX_SCHED_AUTO && auto_schedule() != GFX_SCHED_AUTO) schedule = auto_schedule();
-    const int pv = pm ? pipe_variant(a, g, xcopy != nullptr, N) : -1;
+    if (state_call && schedule == GFX_SCHED_PIPE) schedule = GFX_SCHED_AUTO;   // (the override only steers what can be steered)
+    const int pv = pm && !state_call ? pipe_variant(a, g, xcopy != nullptr, N) : -1;
     if (schedule == GFX_SCHED_PIPE && pv < 0) {
         if (auto_schedule() == GFX_SCHED_PIPE) schedule = GFX_SCHED_TILE;   // the override only steers what can be steered
         else return GFX_EINVAL;
@@ -1113,6 +1050,14 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
     }
     if (g.nparts == 1) {
         if (allow_lds(fftconv1_kernel<false>) || allow_lds(fftconv1_kernel<true>)) return GFX_ELAUNCH;
+        if (zi) {
+            if (allow_lds(fftconv1_state_kernel<false>)) return GFX_ELAUNCH;
+            hipLaunchKernelGGL(fftconv1_state_kernel<false>, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x,
+                               (const float4*)Hs, y, (float*)nullptr, a, tw, (uint32_t*)nullptr, zi, N);
+            if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+            t_last_kernel = "fftconv1_state_kernel<false>";
+            return GFX_OK;
+        }
         if (xcopy)
             hipLaunchKernelGGL(fftconv1_kernel<true>, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x,
                                (const float4*)Hs, y, xcopy, a, tw, rowmax);
@@ -1125,6 +1070,14 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
         return GFX_OK;
     }
     if (g.ntiles == 1) {
+        if (zi) {
+            if (allow_lds(winmac_state_kernel)) return GFX_ELAUNCH;
+            hipLaunchKernelGGL(winmac_state_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x,
+                               (const float4*)Hs, y, a, tw, zi, N);
+            if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+            t_last_kernel = "winmac_state_kernel";
+            return GFX_OK;
+        }
         if (allow_lds(winmac_kernel)) return GFX_ELAUNCH;
         hipLaunchKernelGGL(winmac_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (const float4*)Hs, y,
                            a, tw);
@@ -1139,8 +1092,20 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
     ConvArgs ax = a;
     ax.nblocks = R * C_in * nwin;
     if (ax.nblocks > 0x7ffffff0LL) return GFX_EINVAL;
-    hipLaunchKernelGGL(xspec_kernel, dim3(pad8(ax.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (float2*)ws, ax,
-                       nwin, tw);
+    if (zi) {
+        if (allow_lds(xspec_state_kernel)) return GFX_ELAUNCH;
+        hipLaunchKernelGGL(xspec_state_kernel, dim3(pad8(ax.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (float2*)ws, ax,
+                           nwin, tw, zi, N);
+        // The product kernels consume spectra and know the signal only through which windows exist.  With a history every
+        // window that starts before the row end does (xspec_body), which is what they compute for a signal that begins
+        // nparts hops earlier: the same kernels, told off = nparts * hop and L + nparts * hop.  (They use off and L for
+        // nothing else; rows, tiles and stores go by Lout, O and V.)
+        a.off += (int64_t)g.nparts * g.hop;
+        a.L += (int64_t)g.nparts * g.hop;
+    } else {
+        hipLaunchKernelGGL(xspec_kernel, dim3(pad8(ax.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (float2*)ws, ax,
+                           nwin, tw);
+    }
     // (the pair kernel asks for "partition -1" at byte offset 0x40000000 and counts on the descriptor's range check to
     // return zeros: the filter's partitions must end below that offset -- ~126 M taps; longer filters take macinv_kernel)
     if (schedule != GFX_SCHED_TILE && (int64_t)(g.nparts + 1) * H_TILE_F4 * 16 < 0x40000000LL) {
@@ -1151,16 +1116,39 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
         hipLaunchKernelGGL(macinv_pair_kernel, dim3(pad8(ap.nblocks)), dim3(2 * TILE_T), 2 * TILE_LDS_BYTES, st,
                            (const float2*)ws, (const float4*)Hs, y, ap, nwin, tw, rowmax);
         if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-        t_last_kernel = "xspec_kernel+macinv_pair_kernel";
+        t_last_kernel = zi ? "xspec_state_kernel+macinv_pair_kernel" : "xspec_kernel+macinv_pair_kernel";
         if (rowmax && rowmax_written) *rowmax_written = 1;
         return GFX_OK;
     }
     hipLaunchKernelGGL(macinv_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, (const float2*)ws,
                        (const float4*)Hs, y, a, nwin, tw, rowmax);
     if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    t_last_kernel = "xspec_kernel+macinv_kernel";
+    t_last_kernel = zi ? "xspec_state_kernel+macinv_kernel" : "xspec_kernel+macinv_kernel";
     if (rowmax && rowmax_written) *rowmax_written = 1;
     return GFX_OK;
+}
+
+int gfx_fftconv_state_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, float* y, gfx_rowmap_t ymap,
+                          const float* zi, float* zf, int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t N, void* ws,
+                          size_t ws_bytes, int schedule, void* stream) {
+    if (schedule != GFX_SCHED_AUTO && schedule != GFX_SCHED_TILE) return GFX_EINVAL;
+    if (R <= 0 || C_in < 1 || L <= 0 || N <= 0) return GFX_EINVAL;
+    const int64_t H = N - 1;                                   // samples of state per row-channel
+    if (H == 0) zi = nullptr, zf = nullptr;                    // one tap: no memory
+    if (H >= (int64_t(1) << 29)) return GFX_EINVAL;            // the history is addressed by 32-bit byte offsets
+    if (zi && zf) {                                            // the state is written while the history may still be read
+        const int64_t n = R * C_in * H;
+        if (zi < zf + n && zf < zi + n) return GFX_EINVAL;
+    }
+    const int64_t chunks = (H + 1023) / 1024;
+    if (zf && R * C_in * chunks > 0x7fffffffLL) return GFX_EINVAL;
+    const gfx_rowmap_t none = {1, 0, 0, 0};
+    const int rc = fftconv_sched(x, xmap, Hs, h_rows, 0, y, ymap, nullptr, none, R, C_in, C_f, L, L, 0, N, ws, ws_bytes,
+                                 schedule, stream, nullptr, nullptr, true, zi);
+    if (rc != GFX_OK || !zf) return rc;
+    hipLaunchKernelGGL(fir_state_kernel, dim3((unsigned)(R * C_in * chunks)), dim3(256), 0, (hipStream_t)stream, x, xmap, zi,
+                       zf, (int)C_in, L, H, (unsigned)chunks);
+    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
 const char* gfx_fftconv_last_kernel(void) { return t_last_kernel; }

@@ -196,7 +196,8 @@ ROWMAX_BYPRODUCT = True
 
 
 @_on_device
-def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, part_len=0, schedule="auto", rowmax=None):
+def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, part_len=0, schedule="auto", rowmax=None,
+            zi=None, return_state=False):
     """y[r,c,n] = sum_k h[r % h_rows,cf,k] x[r,cx,n+off-k], n < Lout (x zero outside [0,L)).
 
     ``x`` / ``out`` may be (R,C,L) tensors or strided (B,n,C,L) views (see :func:`rowmap`).
@@ -208,7 +209,29 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
     ``rowmax`` (with schedule "auto"): a dict that receives ``rowmax["words"]`` -- an int32 tensor of R * max(C, Cf) words,
     the bits of max |y| of every output row-channel -- when the kernel that ran leaves them as a by-product
     (gfx_fftconv_rowmax_f32: the compiler-built tile kernels, one partition or many); untouched otherwise.  For odd_alias(rowmax=).
+    ``zi`` / ``return_state``: block-wise processing, see :func:`fftconv_state` (causal only: ``off`` = 0, ``Lout`` = L; no
+    ``tee``, ``rowmax`` or ``part_len``); with ``return_state`` the result is ``(y, zf)``.
     """
+    if zi is not None or return_state:
+        # the stateful entry is the causal convolution on the tile schedule and nothing else: say which argument does not go
+        # with a carried history instead of ignoring it
+        why = None
+        if tee is not None:
+            why = "tee: the input copy comes from the stateless one-partition kernels only"
+        elif rowmax is not None:
+            why = "rowmax: the row maxima feed the odd-length aliasing of one whole-signal call, which has no block form"
+        elif part_len != 0:
+            why = "part_len: a stateful call always takes the default partition geometry"
+        elif off != 0:
+            why = f"off={off}: a carried history is the past of a causal convolution (off = 0)"
+        elif Lout is not None and Lout != x.shape[-1]:
+            why = f"Lout={Lout}: a block of L samples gives L samples (the tail lives in the state, not in the output)"
+        elif schedule not in ("auto", "tile"):
+            why = f"schedule={schedule!r}: a stateful call always takes the tile schedule"
+        if why is not None:
+            raise ValueError(f"fftconv: zi / return_state cannot be combined with {why}")
+        y, zf = fftconv_state(x, Hs, N, Cf, zi=zi, out=out, h_rows=h_rows, return_state=return_state)
+        return (y, zf) if return_state else y
     _require_gpu(x, out, tee)
     xmap, R, Cin, L = rowmap(x)
     Lout = L if Lout is None else Lout
@@ -255,6 +278,63 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
         if t.rec is not None:             # the record is keyed by the kernel's own name, as a profile prints it
             t.name = lib().gfx_fftconv_last_kernel().decode()
     return out
+
+
+def _fir_state(z, shape, what, name):
+    """A carried input history of the stateful convolution: a contiguous float32 GPU tensor (R, C_in, N - 1), oldest sample
+    first.  The kernels read it in place through plain pointers."""
+    if z is None:
+        return None
+    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or tuple(z.shape) != tuple(shape) \
+            or not z.is_contiguous():
+        got = f"{tuple(z.shape)} {z.dtype} on {z.device}" if isinstance(z, torch.Tensor) else type(z).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous float32 GPU tensor of shape {tuple(shape)} "
+                         f"(rows, input channels, taps - 1; oldest sample first), got {got}")
+    return z
+
+
+@_on_device
+def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=True, zf=None, schedule="auto"):
+    """One block of a streamed causal convolution: y[r,c,n] = sum_k h[r % h_rows,cf,k] xx[r,cx,n-k], n < L, where xx is
+    the block ``x`` preceded by the carried history ``zi`` (R, C_in, N - 1), oldest sample first (None: silence), and
+    zf = the last N - 1 samples of ``zi || x`` (a copy: bit-exact, also when L < N - 1 and the old history shifts).
+    gfx_fftconv_state_f32: the window loader of the tile kernels reads the history in place -- no concatenated copy of
+    the signal, no allocation beyond ``out`` / ``zf`` (pass both for none at all).  Blocks of a signal cut anywhere, each
+    entering with the ``zf`` of the one before, concatenate to the linear convolution of the whole.
+
+    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``zf``: optional destination of the state (must not
+    share memory with ``zi``); ``schedule``: "auto" or "tile" (never the persistent kernels).  -> (out, zf); zf is None
+    unless ``return_state`` or a ``zf`` destination is given."""
+    _require_gpu(x, out)
+    if schedule not in ("auto", "tile"):
+        raise ValueError(f"fftconv_state: schedule must be 'auto' or 'tile' (a stateful call never takes the persistent "
+                         f"kernels), got {schedule!r}")
+    xmap, R, Cin, L = rowmap(x)
+    Cout = max(Cin, Cf)
+    h_rows = R if h_rows is None else h_rows
+    if out is None:
+        out = torch.empty((R, Cout, L), dtype=torch.float32, device=x.device)
+    ymap, Ry, Cy, Ly = rowmap(out)
+    if (Ry, Cy) != (R, Cout) or Ly < L:
+        raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={L}")
+    if Hs.numel() != lib().gfx_fir_spectrum_bytes_ex(h_rows * Cf, N, 0):
+        raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
+    shape = (R, Cin, N - 1)
+    zi = _fir_state(zi, shape, "fftconv_state", "zi")
+    zf = _fir_state(zf, shape, "fftconv_state", "zf")
+    if zf is None and return_state:
+        zf = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if zi is not None and zf is not None and _overlap(zi, zf):
+        raise ValueError("fftconv_state: zf must not share memory with zi (the state is written while the history may "
+                         "still be read)")
+    nbytes = lib().gfx_fftconv_workspace_bytes_ex(R, Cin, L, L, 0, N, 0)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    with _timed("fftconv", 4 * R * (Cin * (L + 2 * (N - 1)) + Cout * L)) as t:
+        check(lib().gfx_fftconv_state_f32(_ptr(x), xmap, _ptr(Hs), h_rows, _ptr(out), ymap, _ptr(zi), _ptr(zf), R, Cin, Cf, L,
+                                          N, _ptr(ws), nbytes, SCHEDULES[schedule], _stream()), "gfx_fftconv_state_f32")
+        if t.rec is not None:
+            t.name = lib().gfx_fftconv_last_kernel().decode()
+    return out, zf
 
 
 @_on_device

@@ -20,6 +20,13 @@ native convolve() above with upstream's warning, aliasing included (pinned by go
 
 ``set_exact_convolution(True)`` is the explicit opt-out of the quirk (true linear convolution
 for every length; deviates from the reference when P is odd).
+
+Streaming (``state=`` / ``return_state=`` in causal mode): the state is the last N - 1 input samples, (R, C_in, N - 1),
+oldest first, read in place by the tile kernels (gfx_fftconv_state_f32).  With a state the result is always the causal
+linear convolution, so the blocks of a signal cut anywhere concatenate to the linear convolution of the whole; the
+reference's odd-length aliasing is a property of one whole-signal transform and has no block form.  The blocks therefore
+equal the one-call output exactly when that call does not alias (L_total + N - 1 even) or under
+``set_exact_convolution(True)``.
 """
 import contextlib
 import contextvars
@@ -110,13 +117,42 @@ def compute_pad_len(x, y, pad_mode="min"):
     return x.shape[-1] + y.shape[-1] - 1
 
 
-def convolve_taps(x, Hs, N, Cf, mode, out=None, tee=None, exact=False, h_rows=None):
+def check_state(state, x, N, what="convolve"):
+    """A carried input history: a float32 GPU tensor (rows of x, channels of x, N - 1), oldest sample first."""
+    if state is None:
+        return None
+    rows = x.shape[0] * x.shape[1] if x.ndim == 4 else x.shape[0]
+    shape = (rows, x.shape[-2], N - 1)
+    if not isinstance(state, torch.Tensor) or tuple(state.shape) != shape or state.dtype != torch.float32 \
+            or state.device != x.device:
+        got = f"{tuple(state.shape)} {state.dtype} on {state.device}" if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"{what}: state must be a float32 tensor of shape {shape} (rows, input channels, taps - 1; oldest "
+                         f"sample first) on {x.device}, got {got}")
+    return state
+
+
+def causal_only(mode, what="convolve"):
+    if mode != "causal":
+        raise ValueError(f"{what}: state / return_state need mode='causal' (the state is the past of a causal convolution; "
+                         f"mode={mode!r} looks ahead of the block)")
+
+
+def convolve_taps(x, Hs, N, Cf, mode, out=None, tee=None, exact=False, h_rows=None, state=None, return_state=False):
     """convolve() given precomputed tile spectra of the taps.
 
     ``x`` is (R,C,L) or a strided (B,n,C,L) view of the signal buffer; with ``out`` (same kind of
     view) the kernels write the result in place and ``out`` is returned.  ``tee`` (a view shaped like
-    ``x``) additionally receives a copy of ``x`` -- from the convolution kernel itself when it can."""
+    ``x``) additionally receives a copy of ``x`` -- from the convolution kernel itself when it can.
+    ``state`` / ``return_state``: one block of a stream (module docstring); -> ``(y, state)`` with ``return_state``."""
     L = x.shape[-1]
+    if state is not None or return_state:
+        causal_only(mode, "convolve_taps")
+        state = check_state(state, x, N, "convolve_taps")
+        if tee is not None:
+            tee.copy_(x)
+        y, zf = ops.fftconv_state(x, Hs, N, Cf, zi=None if state is None else state.contiguous(), out=out, h_rows=h_rows,
+                                  return_state=return_state)
+        return (y, zf) if return_state else y
     if tee is not None:
         if mode == "causal" and not reference_aliases(L, N, exact) and ops.fftconv_can_tee(x.shape[-2], Cf, L, L, 0, N):
             return ops.fftconv(x, Hs, N, Cf, Lout=L, off=0, out=out, tee=tee, h_rows=h_rows)
@@ -146,9 +182,34 @@ def convolve_taps(x, Hs, N, Cf, mode, out=None, tee=None, exact=False, h_rows=No
     return out
 
 
-def convolve(x, h, mode="zerophase", pad_mode="min", exact=False):
-    """Reference-compatible convolve(): x (R,C,L) or (R,L); h (R,Cf,N) or (R,N).  ``exact``: see reference_aliases."""
+def convolve(x, h, mode="zerophase", pad_mode="min", exact=False, state=None, return_state=False):
+    """Reference-compatible convolve(): x (R,C,L) or (R,L); h (R,Cf,N) or (R,N).  ``exact``: see reference_aliases.
+
+    ``state`` / ``return_state`` (``mode="causal"`` only; any other mode raises ValueError): block-wise processing.
+    ``state``: the last N - 1 input samples before this block, (R, C, N - 1) -- (R, N - 1) for 2-D signals --, oldest first
+    (None: silence); with ``return_state`` the result is ``(y, state)``, the state to hand to the next block.  With a state
+    the result is always the causal linear convolution: the blocks of a signal cut anywhere concatenate to the linear
+    convolution of the whole, which equals the one-call output exactly when that call does not alias
+    (L_total + N - 1 even) or under ``set_exact_convolution(True)`` -- the reference's odd-length aliasing is a property
+    of one whole-signal transform and has no block form."""
     compute_pad_len(x, h, pad_mode)
+    if state is not None or return_state:
+        causal_only(mode)
+        flat = x.ndim == 2
+        if flat:
+            x, h = x.unsqueeze(1), h.unsqueeze(1)
+            state = state.unsqueeze(1) if isinstance(state, torch.Tensor) and state.ndim == 2 else state
+        R, Cf, N = h.shape
+        state = check_state(state, x, N)
+        if needs_grad(x, h, state):
+            y, zf = diff.convolve(x, h, "causal", state=state, return_state=True)
+        else:
+            # (always the FFT tile route: the matrix-core short-FIR kernel reads no history)
+            y, zf = convolve_taps(x, ops.fir_spectrum(h.reshape(R * Cf, N)), N, Cf, "causal", state=state,
+                                  return_state=True, h_rows=R)
+        if flat:
+            y, zf = y.squeeze(1), zf.squeeze(1)
+        return (y, zf) if return_state else y
     if needs_grad(x, h):
         return diff.convolve(x, h, mode, exact=exact)
     flat = x.ndim == 2
@@ -180,5 +241,10 @@ class FIRConvolution(nn.Module):
         self.mode = mode
         self.flashfftconv = resolve_flashfftconv(flashfftconv)
 
-    def forward(self, input_signals, fir):
+    def forward(self, input_signals, fir, state=None, return_state=False):
+        """``state`` / ``return_state`` (``mode="causal"`` only): block-wise processing, see :func:`convolve` -- with a
+        state the result is the causal linear convolution, and ``(y, state)`` comes back when a state is asked for."""
+        if state is not None or return_state:
+            return convolve(input_signals, fir, mode=self.mode, exact=self.flashfftconv, state=state,
+                            return_state=return_state)
         return convolve(input_signals, fir, mode=self.mode, exact=self.flashfftconv)

@@ -36,8 +36,19 @@ class MultitapDelay(nn.Module):
         self.processor_channel = processor_channel
         self.num_channels = 1 if processor_channel == "mono" else 2
 
-    def forward(self, input_signals, delay_z, log_fir_magnitude=None):
+    def forward(self, input_signals, delay_z, log_fir_magnitude=None, state=None, return_state=False):
+        """``state`` / ``return_state``: block-wise processing (core.convolution.convolve).  The state is the last
+        ``segment_len * num_segments + pre_delay - 1`` input samples, (R, C, that many), oldest first (the pre-delay is
+        part of the streamed impulse response); treat it as opaque, its layout is stable.  With a state the result is
+        the causal linear convolution, so blocks cut anywhere concatenate to the linear convolution of the whole (the
+        one-call output when that call does not alias, or under set_exact_convolution(True)).  Returns
+        ``(y, radii_loss, state)`` when a state is asked for."""
         ir, radii_loss = self.get_ir(delay_z, log_fir_magnitude)
+        if state is not None or return_state:
+            if self.pre_delay != 0:
+                ir = F.pad(ir, (self.pre_delay, 0))
+            y, zf = self.conv(input_signals, ir, state=state, return_state=True)
+            return (y, radii_loss, zf) if return_state else (y, radii_loss)
         y = self.conv(input_signals, ir)   # upstream convolves directly for every channel mode (delay.py:123)
         if self.pre_delay != 0:
             y = F.pad(y, (self.pre_delay, 0))[:, :, : -self.pre_delay]

@@ -30,11 +30,20 @@ class FIRFilter(nn.Module):
         backend_kwargs.pop("fir_len", None)
         self.conv = FIRConvolution(**backend_kwargs)
 
-    def forward(self, input_signals, fir):
+    def forward(self, input_signals, fir, state=None, return_state=False):
+        """``state`` / ``return_state``: block-wise processing (core.convolution.convolve): the state is the history of
+        what the convolution reads, (R, C, fir_len - 1), oldest first -- in "midside" mode the mid/side signal; treat it
+        as opaque, its layout is stable.  With a state the result is the causal linear convolution, so blocks cut
+        anywhere concatenate to the linear convolution of the whole (the one-call output when L_total + fir_len - 1 is
+        even, or under set_exact_convolution(True)); ``(y, state)`` comes back when a state is asked for."""
         fir = normalize_impulse(torch.tanh(fir))
+        block = {} if state is None and not return_state else {"state": state, "return_state": True}
+        x = lr_to_ms(input_signals) if self.processor_channel == "midside" else input_signals
+        y = self.conv(x, fir, **block)
+        y, zf = y if block else (y, None)
         if self.processor_channel == "midside":
-            return ms_to_lr(self.conv(lr_to_ms(input_signals), fir))
-        return self.conv(input_signals, fir)
+            y = ms_to_lr(y)
+        return (y, zf) if return_state else y
 
     def parameter_size(self):
         return {"fir": (self.num_channels, self.fir_len)}

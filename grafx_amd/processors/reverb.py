@@ -10,7 +10,7 @@ from .. import ops
 from ..autograd import needs_grad
 from .core._buffer_io import BufferIO, Prepared, expand_shared, shared_reps
 from .core.utils import normalize_impulse
-from .core.convolution import convolve_taps, resolve_flashfftconv
+from .core.convolution import check_state, convolve_taps, resolve_flashfftconv
 from .core.midside import lr_to_ms, ms_to_lr
 
 
@@ -139,7 +139,18 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         return Prepared(ops.fir_spectrum(ir.view(ir.shape[0] * 2, self.ir_len), gain=gain, gain_div=2))
 
     def forward(self, input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None, _out=None,
-                _shared_rows=None, _prepared=None):
+                _shared_rows=None, _prepared=None, state=None, return_state=False):
+        """``state`` / ``return_state``: block-wise processing (core.convolution.convolve).  The state is the history of
+        what the convolution reads, (R, 2, ir_len - 1), oldest first -- in "midside" mode the mid/side signal; treat it
+        as opaque, its layout is stable.  With a state the result is the causal linear convolution, so blocks cut
+        anywhere concatenate to the linear convolution of the whole: the one-call output exactly when that call does
+        not alias (L_total + ir_len - 1 even) or under set_exact_convolution(True) -- the reference's odd-length
+        aliasing is a property of one whole-signal transform and has no block form.  ``fixed_noise=False`` raises with
+        a state: a fresh impulse response per block is not a stream.  ``(y, state)`` comes back when a state is asked
+        for; the in-place ``_out`` and ``_prepared`` paths take both arguments too."""
+        if state is not None or return_state:
+            return self._forward_block(input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, _out,
+                                       _shared_rows, _prepared, state, return_state)
         if _prepared is not None:
             return convolve_taps(input_signals, _prepared.tensors[0], self.ir_len, 2, "causal", out=_out,
                                  exact=self.flashfftconv, h_rows=_shared_rows)
@@ -177,6 +188,46 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
             return ms_to_lr(convolve_taps(lr_to_ms(input_signals), Hs, self.ir_len, 2, "causal", exact=self.flashfftconv))
         return convolve_taps(input_signals, Hs, self.ir_len, 2, "causal", out=_out, exact=self.flashfftconv,
                              h_rows=_shared_rows)
+
+    def _forward_block(self, x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, _out, _shared_rows,
+                       _prepared, state, return_state):
+        """forward() with a carried state: the same impulse responses, the stateful causal convolution."""
+        if not self.fixed_noise:
+            raise ValueError("STFTMaskedNoiseReverb: fixed_noise=False draws a fresh impulse response per call, so a chain "
+                             "of blocks is not a stream; state / return_state need fixed_noise=True")
+        N = self.ir_len
+        if _prepared is not None:
+            return convolve_taps(x, _prepared.tensors[0], N, 2, "causal", out=_out, h_rows=_shared_rows, state=state,
+                                 return_state=return_state)
+        pseudo = self.processor_channel == "pseudo_midside"
+        midside = self.processor_channel == "midside"
+        if needs_grad(x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, state):
+            ir = self._compute_ir_differentiable(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
+            h = normalize_impulse(ms_to_lr(ir)) if pseudo else normalize_impulse(ir)
+            xs = x.reshape(-1, *x.shape[-2:]) if midside else x
+            if midside:
+                xs = lr_to_ms(xs)
+                if h.shape[0] != xs.shape[0]:
+                    h = expand_shared(h, xs.shape[0] // h.shape[0])
+            y, zf = diff.convolve(xs, h, "causal", state=check_state(state, xs, N, "STFTMaskedNoiseReverb"),
+                                  return_state=True)
+            if midside:
+                y = ms_to_lr(y)
+            if _out is not None:
+                _out.copy_(y.view(_out.shape))
+                y = _out
+            return (y, zf) if return_state else y
+        ir, gain = self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
+        Hs = ops.fir_spectrum(ir.view(ir.shape[0] * 2, N), gain=gain, gain_div=2)
+        if midside:  # the history is the mid/side signal the convolution reads
+            xs = lr_to_ms(x.reshape(-1, *x.shape[-2:]))
+            y, zf = convolve_taps(xs, Hs, N, 2, "causal", h_rows=_shared_rows or ir.shape[0], state=state, return_state=True)
+            y = ms_to_lr(y)
+            if _out is not None:
+                _out.copy_(y.view(_out.shape))
+                y = _out
+            return (y, zf) if return_state else y
+        return convolve_taps(x, Hs, N, 2, "causal", out=_out, h_rows=_shared_rows, state=state, return_state=return_state)
 
     def parameter_size(self):
         size = {"init_log_magnitude": (2, self.num_bins), "delta_log_magnitude": (2, self.num_bins)}
@@ -241,11 +292,27 @@ class FilteredNoiseShapingReverb(nn.Module):
         return ops.noise_shaping_ir(noise[0], log_decay, log_gain, fade[0], fade[1], self.ir_len, self.min_decay,
                                     self.max_decay)
 
-    def forward(self, input_signals, log_decay, log_gain, log_fade_in=None, z_fade_in_gain=None):
+    def forward(self, input_signals, log_decay, log_gain, log_fade_in=None, z_fade_in_gain=None, state=None,
+                return_state=False):
+        """``state`` / ``return_state``: block-wise processing (core.convolution.convolve).  The state is the history of
+        what the convolution reads, (R, C, ir_len - 1), oldest first -- in "midside" mode the mid/side signal; treat it
+        as opaque, its layout is stable.  With a state the result is the causal linear convolution, so blocks cut
+        anywhere concatenate to the linear convolution of the whole (the one-call output when L_total + ir_len - 1 is
+        even, or under set_exact_convolution(True)).  ``noise_randomness="pseudo-random"`` raises with a state: it cuts
+        a fresh impulse response per call, and a chain of blocks is then not a stream.  ``(y, state)`` comes back when
+        a state is asked for."""
+        block = {} if state is None and not return_state else {"state": state, "return_state": True}
+        if block and self.noise_randomness != "fixed":
+            raise ValueError('FilteredNoiseShapingReverb: noise_randomness="pseudo-random" cuts a fresh impulse response '
+                             'per call, so a chain of blocks is not a stream; state / return_state need '
+                             'noise_randomness="fixed"')
         ir = normalize_impulse(self.compute_ir(log_decay, log_gain, log_fade_in, z_fade_in_gain))
+        x = lr_to_ms(input_signals) if self.processor_channel == "midside" else input_signals
+        y = self.conv(x, ir, **block)
+        y, zf = y if block else (y, None)
         if self.processor_channel == "midside":
-            return ms_to_lr(self.conv(lr_to_ms(input_signals), ir))
-        return self.conv(input_signals, ir)
+            y = ms_to_lr(y)
+        return (y, zf) if return_state else y
 
     def parameter_size(self):
         shape = (self.num_channels, self.num_bands)

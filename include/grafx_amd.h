@@ -154,6 +154,23 @@ int gfx_fftconv_rowmax_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, in
                            int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
                            void* ws, size_t ws_bytes, uint32_t* rowmax, int* rowmax_written, void* stream);
 
+/* State across calls: one block of a streamed CAUSAL convolution (Lout = L, off = 0, default partition geometry).
+ *   y[r, c, n] = sum_k h[r % h_rows, c_f, k] xx[r, c_x, n - k],  n in [0, L),  xx = zi || x
+ * zi, zf: contiguous float32 (R, C_in, N - 1), oldest sample first -- the last N - 1 input samples before / after this
+ * block.  zi == NULL: silence before the block; zf == NULL: no state wanted.  zf = the last N - 1 samples of zi || x: a
+ * copy (bit-exact; for L < N - 1 the old history shifts), written by a small kernel of its own, stream-ordered after the
+ * convolution.  The window loaders of the tile kernels read the history in place where the stateless kernels take zeros
+ * (fftconv1_state_kernel, xspec_state_kernel, winmac_state_kernel): no concatenated copy of the signal, no allocation.
+ * Blocks of a signal cut anywhere, each entering with the zf of the block before, concatenate to the linear convolution
+ * of the whole.  zi and zf must not overlap: GFX_EINVAL.  N = 1 has an empty state (zi, zf ignored).  Workspace:
+ * gfx_fftconv_workspace_bytes_ex(R, C_in, L, L, 0, N, 0).  schedule: GFX_SCHED_AUTO or GFX_SCHED_TILE (which product kernel
+ * a partitioned convolution takes, as in gfx_fftconv_sched_f32); a call with state never takes the hand-scheduled
+ * kernels: GFX_SCHED_PIPE is GFX_EINVAL.  Everything else (row maps, channel broadcast, h_rows, row-count limits) as
+ * gfx_fftconv_sched_f32. */
+int gfx_fftconv_state_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, float* y, gfx_rowmap_t ymap,
+                          const float* zi, float* zf, int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t N,
+                          void* ws, size_t ws_bytes, int schedule, void* stream);
+
 /* Diagnostic: the name -- as rocprofv3's kernel trace prints it -- of the (dominant) kernel that the calling thread's last
  * successful gfx_fftconv_* call launched: "gfx_fftconv_pipe_t1_o8", "fftconv1_kernel<true>", "winmac_kernel",
  * "xspec_kernel+macinv_pair_kernel"; "" before the first call.  The string is static.  (bench.py labels its live per-launch

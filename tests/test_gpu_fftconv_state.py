@@ -1,0 +1,476 @@
+"""GPU: the causal FIR convolution carried across calls (gfx_fftconv_state_f32, ops.fftconv_state, state= / return_state=
+on convolve, FIRConvolution, FIRFilter, MultitapDelay and the two reverbs).
+
+The reference for values is a float64 linear convolution of the UNCUT signal, computed on the CPU here; comparisons use
+assert_close at 1e-5, the bound of every test of tests/test_gpu_fftconv.py.  The state itself is a copy and is compared bit
+for bit.  Every test needs the new entry or a new keyword and fails without them."""
+import warnings
+
+import pytest
+import torch
+
+from conftest import assert_close
+
+pytestmark = pytest.mark.gpu
+
+TILE_F = 16384
+
+
+def _overlap_of(N):
+    """The tile overlap O of an N-tap filter (csrc/fftconv.hip: conv_geom)."""
+    return (N - 1 + 511) // 512 * 512 if N <= 8193 else 8192
+
+
+def _lin64(x, h, zi=None):
+    """float64 causal linear convolution of the whole signal on the CPU: x (R, Cin, T), h (hr, Cf, N) with row r taking
+    filter r % hr, channels broadcast 1 <-> 2, optionally preceded by the history zi (R, Cin, N - 1) -> (R, Cout, T)."""
+    x, h = x.double().cpu(), h.double().cpu()
+    R, T, N = x.shape[0], x.shape[-1], h.shape[-1]
+    if zi is not None:
+        x = torch.cat([zi.double().cpu(), x], -1)
+    h = h[torch.arange(R) % h.shape[0]]
+    n = 1 << (x.shape[-1] + N).bit_length()
+    full = torch.fft.irfft(torch.fft.rfft(x, n=n) * torch.fft.rfft(h, n=n), n=n)
+    lo = x.shape[-1] - T
+    return full[..., lo : lo + T]
+
+
+def _chain(x, Hs, N, Cf, cuts, zi=None, kernels=None, **kw):
+    """The blocks of x cut at `cuts`, each entering with the state the block before left -> (concatenated output, last state)."""
+    from grafx_amd import ops
+    from grafx_amd._lib import lib
+
+    assert sum(cuts) == x.shape[-1]
+    out, pos, state = [], 0, zi
+    for n in cuts:
+        y, state = ops.fftconv_state(x[..., pos : pos + n].contiguous(), Hs, N, Cf, zi=state, **kw)
+        if kernels is not None:
+            kernels.append((n, lib().gfx_fftconv_last_kernel().decode()))
+        out.append(y)
+        pos += n
+    return torch.cat(out, -1), state
+
+
+def _tail(x, n, zi=None):
+    """The last n samples of zi || x (zi None: zeros), the state a chain over x must leave."""
+    R, C, _ = x.shape
+    hist = torch.zeros(R, C, n, device=x.device) if zi is None else zi
+    full = torch.cat([hist, x], -1)
+    return full[..., full.shape[-1] - n :]
+
+
+def _cuts(N):
+    """Odd lengths, a block of one sample, a block shorter than N - 1 (the history must shift), and -- for one-partition
+    filters -- 16384 - O + 1: the shortest block that spans two tiles, of which only the first may read history."""
+    O = _overlap_of(N)
+    return [1, 7, max(N - 2, 1), 4096, TILE_F - O + 1, 333]
+
+
+# ------------------------------------------------------------------------------------------------- block equality
+@pytest.mark.parametrize("with_zi", [False, True])
+@pytest.mark.parametrize("N", [1, 2, 64, 513, 514, 1025, 8193])
+def test_blocks_concatenate_to_the_linear_convolution_one_partition(N, with_zi):
+    """513 / 514: the overlap O is 512 / 1024 (N - 1 a whole number of register rows, and one sample more); 8193: the last
+    one-partition length; N even: the pair (-N, -(N-1)) straddles the start of the history; N odd / even: history pairs
+    8-byte / only 4-byte aligned."""
+    from grafx_amd import ops
+
+    g = torch.Generator().manual_seed(N)
+    cuts = _cuts(N)
+    x = torch.randn(2, 2, sum(cuts), generator=g)
+    h = torch.randn(2, 2, N, generator=g) / N**0.5
+    zi = torch.randn(2, 2, N - 1, generator=g) if with_zi else None
+    Hs = ops.fir_spectrum(h.cuda().reshape(4, N))
+    kernels = []
+    y, zf = _chain(x.cuda(), Hs, N, 2, cuts, zi=None if zi is None else zi.cuda(), kernels=kernels)
+    assert_close(y.cpu(), _lin64(x, h, zi), 1e-5, f"one partition N={N}")
+    assert torch.equal(zf, _tail(x.cuda(), N - 1, None if zi is None else zi.cuda())), "last state != tail of the whole input"
+    # a block that enters with a history runs the history kernel (never the persistent ones); the first, without one, and
+    # every block of a one-tap filter (no memory) run the stateless tile kernel
+    for i, (n, k) in enumerate(kernels):
+        want = "fftconv1_kernel<false>" if N == 1 or (i == 0 and not with_zi) else "fftconv1_state_kernel<false>"
+        assert k == want, (n, k)
+
+
+@pytest.mark.parametrize("with_zi", [False, True])
+@pytest.mark.parametrize("schedule", ["auto", "tile"])
+def test_blocks_concatenate_to_the_linear_convolution_partitioned(schedule, with_zi):
+    """N = 20000 (three partitions of 8192): blocks of up to 8192 samples are one output tile (winmac_state_kernel, every
+    partition's window in the history), 8193 is two tiles and 20000 three (xspec_state_kernel + the product kernels: the
+    pair kernel under "auto", one tile per workgroup under "tile")."""
+    from grafx_amd import ops
+
+    N = 20000
+    g = torch.Generator().manual_seed(20000 + with_zi)
+    cuts = [1000, 1, 8192, 7, 20000, 8193, 333]
+    x = torch.randn(2, 2, sum(cuts), generator=g)
+    h = torch.randn(2, 2, N, generator=g) / N**0.5
+    zi = torch.randn(2, 2, N - 1, generator=g) if with_zi else None
+    Hs = ops.fir_spectrum(h.cuda().reshape(4, N))
+    kernels = []
+    y, zf = _chain(x.cuda(), Hs, N, 2, cuts, zi=None if zi is None else zi.cuda(), kernels=kernels, schedule=schedule)
+    assert_close(y.cpu(), _lin64(x, h, zi), 1e-5, f"partitioned, schedule {schedule}")
+    assert torch.equal(zf, _tail(x.cuda(), N - 1, None if zi is None else zi.cuda()))
+    product = "macinv_pair_kernel" if schedule == "auto" else "macinv_kernel"
+    for i, (n, k) in enumerate(kernels):
+        stateless = i == 0 and not with_zi
+        if n <= 8192:
+            assert k == ("winmac_kernel" if stateless else "winmac_state_kernel"), (n, k)
+        else:
+            assert k == ("xspec_kernel+" if stateless else "xspec_state_kernel+") + product, (n, k)
+
+
+@pytest.mark.parametrize("Cin,Cf", [(1, 1), (1, 2), (2, 1), (2, 2)])
+@pytest.mark.parametrize("N", [514, 20000])
+def test_channel_broadcast_and_shared_filters(N, Cin, Cf):
+    """The state has C_in channels whatever the filter has; three rows share two filters (h_rows < R: row r takes filter
+    r % h_rows)."""
+    from grafx_amd import ops
+
+    g = torch.Generator().manual_seed(N + 10 * Cin + Cf)
+    cuts = [301, 9000, 5] if N > 8193 else [301, TILE_F - _overlap_of(N) + 1, 5]
+    R, hr = 4, 2
+    x = torch.randn(R, Cin, sum(cuts), generator=g)
+    h = torch.randn(hr, Cf, N, generator=g) / N**0.5
+    zi = torch.randn(R, Cin, N - 1, generator=g)
+    Hs = ops.fir_spectrum(h.cuda().reshape(hr * Cf, N))
+    y, zf = _chain(x.cuda(), Hs, N, Cf, cuts, zi=zi.cuda(), h_rows=hr)
+    assert tuple(zf.shape) == (R, Cin, N - 1)
+    assert_close(y.cpu(), _lin64(x, h, zi), 1e-5, f"N={N} Cin={Cin} Cf={Cf} h_rows={hr}")
+    assert torch.equal(zf, _tail(x.cuda(), N - 1, zi.cuda()))
+
+
+@pytest.mark.parametrize("N", [514, 20000])
+def test_strided_views_in_place(N):
+    """x and out as strided (B, n, C, L) views of a larger buffer (the render's signal buffer): the rows are read and
+    written in place and the neighbouring node's samples stay what they were."""
+    from grafx_amd import ops
+
+    B, n, C, L = 2, 2, 2, 700
+    g = torch.Generator().manual_seed(N + 1)
+    x = torch.randn(B * n, C, L, generator=g)
+    h = torch.randn(B * n, C, N, generator=g) / N**0.5
+    zi = torch.randn(B * n, C, N - 1, generator=g)
+    xbuf = torch.full((B, n + 1, C, L + 3), 7.0, device="cuda")
+    xbuf[:, :n, :, :L] = x.view(B, n, C, L).cuda()
+    obuf = torch.full((B, n + 1, C, L + 3), float("nan"), device="cuda")
+    Hs = ops.fir_spectrum(h.cuda().reshape(B * n * C, N))
+    y, zf = ops.fftconv_state(xbuf[:, :n, :, :L], Hs, N, C, zi=zi.cuda(), out=obuf[:, 1:, :, :L])
+    assert y.data_ptr() == obuf[:, 1:, :, :L].data_ptr()
+    assert_close(obuf[:, 1:, :, :L].reshape(B * n, C, L).cpu(), _lin64(x, h, zi), 1e-5, f"views N={N}")
+    assert torch.isnan(obuf[:, 0]).all() and torch.isnan(obuf[..., L:]).all(), "bytes next to the output rows were written"
+    assert (xbuf[:, n] == 7).all() and (xbuf[..., L:] == 7).all()
+    assert torch.equal(zf, _tail(x.cuda(), N - 1, zi.cuda()))
+
+
+# ------------------------------------------------------------------------------------------------- the state
+@pytest.mark.parametrize("N", [2, 514, 1025, 20000])
+@pytest.mark.parametrize("L", [1, 300, 30001])
+def test_state_is_the_tail_of_history_and_block_bit_for_bit(N, L):
+    """zf = the last N - 1 samples of zi || x, a copy: also for L < N - 1 (the old history shifts) and for zi = None (leading
+    zeros); a caller's zf buffer is written in place."""
+    from grafx_amd import ops
+
+    g = torch.Generator().manual_seed(N * 7 + L)
+    x = torch.randn(3, 2, L, generator=g).cuda()
+    h = torch.randn(3, 1, N, generator=g).cuda()
+    zi = torch.randn(3, 2, N - 1, generator=g).cuda()
+    Hs = ops.fir_spectrum(h.reshape(3, N))
+    for z in (zi, None):
+        own = torch.full((3, 2, N - 1), float("nan"), device="cuda")
+        _, zf = ops.fftconv_state(x, Hs, N, 1, zi=z, zf=own)
+        assert zf is own
+        assert torch.equal(zf, _tail(x, N - 1, z)), f"N={N} L={L} zi={'given' if z is not None else None}"
+
+
+@pytest.mark.parametrize("N", [514, 20000])
+def test_only_the_last_N_minus_1_samples_are_read(N):
+    """Two pasts that differ in every sample older than N - 1 and agree on the last N - 1 give the same state and the same
+    output bits for the block that follows."""
+    from grafx_amd import ops
+
+    g = torch.Generator().manual_seed(N + 2)
+    M = N - 1 + 2000
+    past1 = torch.randn(2, 2, M, generator=g)
+    past2 = past1.clone()
+    past2[..., : M - (N - 1)] = torch.randn(2, 2, M - (N - 1), generator=g) + 3.0
+    x = torch.randn(2, 2, 1500, generator=g).cuda()
+    h = torch.randn(2, 2, N, generator=g).cuda() / N**0.5
+    Hs = ops.fir_spectrum(h.reshape(4, N))
+    ys = []
+    for past in (past1, past2):
+        _, z = ops.fftconv_state(past.cuda(), Hs, N, 2)
+        ys.append(ops.fftconv_state(x, Hs, N, 2, zi=z))
+    assert torch.equal(ys[0][1], ys[1][1])
+    assert torch.equal(ys[0][0], ys[1][0]), "samples older than N - 1 reached the output"
+    assert_close(ys[0][0].cpu(), _lin64(x.cpu(), h.cpu(), past1[..., M - (N - 1) :]), 1e-5, f"N={N}")
+
+
+# ------------------------------------------------------------------------------------------------- rows
+def test_more_than_65535_row_channels():
+    """R * C = 65538 row-channels at a tiny L and N, the new entry only (in the manner of tests/test_gpu_many_rows.py):
+    workgroups and state rows are counted on grid.x."""
+    from grafx_amd import ops
+
+    R, C, L, N = 32769, 2, 64, 5
+    g = torch.Generator().manual_seed(65538)
+    x = torch.randn(R, C, L, generator=g)
+    h = torch.randn(3, 1, N, generator=g)
+    zi = torch.randn(R, C, N - 1, generator=g)
+    Hs = ops.fir_spectrum(h.cuda().reshape(3, N))
+    out = torch.full((R, C, L), float("nan"), device="cuda")
+    y, zf = ops.fftconv_state(x.cuda(), Hs, N, 1, zi=zi.cuda(), out=out, h_rows=3)
+    assert torch.isfinite(y).all()
+    assert_close(y.cpu(), _lin64(x, h, zi), 1e-5, "65538 row-channels")
+    assert torch.equal(zf, _tail(x.cuda(), N - 1, zi.cuda()))
+
+
+# ------------------------------------------------------------------------------------------------- gradients
+@pytest.mark.parametrize("N", [301, 9001])
+def test_gradients_of_a_two_block_chain(N):
+    """x, h and the entering state from random cotangents of both outputs and of the last state, against float64 autograd
+    of the same chain: 1e-5, the bound tests/test_gpu_autograd.py:46-48 holds LinearConvFn to.  The two blocks' filter
+    gradients add up to the one-call filter gradient within the same bound."""
+    from grafx_amd.processors.core.convolution import convolve
+
+    g = torch.Generator().manual_seed(N)
+    L1, L2, R, C = 700, 801, 2, 2
+    x1, x2 = torch.randn(R, C, L1, generator=g), torch.randn(R, C, L2, generator=g)
+    h = torch.randn(R, C, N, generator=g) / N**0.5
+    zi = torch.randn(R, C, N - 1, generator=g)
+    w1, w2, wz = torch.randn(R, C, L1, generator=g), torch.randn(R, C, L2, generator=g), torch.randn(R, C, N - 1, generator=g)
+
+    def chain(x1, x2, ha, hb, zi, conv):
+        y1, z1 = conv(x1, ha, zi)
+        y2, z2 = conv(x2, hb, z1)
+        return y1, y2, z2
+
+    def native(x, h, z):
+        return convolve(x, h, mode="causal", state=z, return_state=True)
+
+    def ref64(x, h, z):   # the same block in float64 torch ops on the CPU
+        xx = torch.cat([z, x], -1)
+        n = 1 << (xx.shape[-1] + N).bit_length()
+        full = torch.fft.irfft(torch.fft.rfft(xx, n=n) * torch.fft.rfft(h, n=n), n=n)
+        return full[..., N - 1 : N - 1 + x.shape[-1]], xx[..., xx.shape[-1] - (N - 1) :]
+
+    leaves = [t.cuda().requires_grad_() for t in (x1, x2, h, h.clone(), zi)]
+    y1, y2, z2 = chain(*leaves, native)
+    got = torch.autograd.grad((y1 * w1.cuda()).sum() + (y2 * w2.cuda()).sum() + (z2 * wz.cuda()).sum(), leaves)
+    leaves64 = [t.double().requires_grad_() for t in (x1, x2, h, h.clone(), zi)]
+    r1, r2, rz = chain(*leaves64, ref64)
+    want = torch.autograd.grad((r1 * w1.double()).sum() + (r2 * w2.double()).sum() + (rz * wz.double()).sum(), leaves64)
+    assert_close(y1.detach().cpu(), r1.detach(), 1e-5, "y block 1")
+    assert_close(y2.detach().cpu(), r2.detach(), 1e-5, "y block 2")
+    assert torch.equal(z2.detach().cpu(), rz.detach().float())
+    for name, a, b in zip(("grad x1", "grad x2", "grad h (block 1)", "grad h (block 2)", "grad state"), got, want):
+        assert_close(a.cpu(), b, 1e-5, f"{name} N={N}")   # tests/test_gpu_autograd.py:46-48
+
+    xw, hw, zw = torch.cat([x1, x2], -1).cuda(), h.cuda().requires_grad_(), zi.cuda()
+    yw, _ = convolve(xw, hw, mode="causal", state=zw, return_state=True)
+    (gh,) = torch.autograd.grad((yw * torch.cat([w1, w2], -1).cuda()).sum(), [hw])
+    assert_close((got[2] + got[3]).cpu(), gh.cpu(), 1e-5, f"sum of the blocks' filter gradients N={N}")
+    assert_close(gh.cpu(), want[2] + want[3], 1e-5, f"one-call filter gradient N={N}")
+
+
+# ------------------------------------------------------------------------------------------------- processors
+BLOCKS = (700, 1, 1347)
+
+
+def _params(module, R, seed):
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k, shape in module.parameter_size().items():
+        shape = (shape,) if isinstance(shape, int) else tuple(shape)
+        out[k] = (torch.randn(R, *shape, generator=g) * 0.3).cuda()
+    return out
+
+
+def _stream(call, x, blocks=BLOCKS):
+    """call(block, state) -> (y, state) over the blocks of x -> the concatenated output."""
+    out, pos, state = [], 0, None
+    for n in blocks:
+        y, state = call(x[..., pos : pos + n].contiguous(), state)
+        out.append(y)
+        pos += n
+    return torch.cat(out, -1), state
+
+
+def _exact():
+    from grafx_amd.processors.core.convolution import exact_convolution_scope
+
+    return exact_convolution_scope(True)   # the one call is then the linear convolution whatever its length's parity
+
+
+def test_fir_convolution_module_streams():
+    from grafx_amd.processors.core.convolution import FIRConvolution
+
+    g = torch.Generator().manual_seed(1)
+    conv = FIRConvolution(mode="causal", flashfftconv=False)
+    x = torch.randn(2, 2, sum(BLOCKS), generator=g).cuda()
+    fir = (torch.randn(2, 2, 300, generator=g) / 17).cuda()
+    with torch.no_grad(), _exact():
+        whole = conv(x, fir)
+        y, state = _stream(lambda b, s: conv(b, fir, state=s, return_state=True), x)
+    assert tuple(state.shape) == (2, 2, 299)
+    assert_close(y.cpu(), whole.cpu(), 1e-5, "FIRConvolution blocks vs one call")
+    assert_close(y.cpu(), _lin64(x.cpu(), fir.cpu()), 1e-5, "FIRConvolution blocks vs float64")
+    # 2-D signals: the state loses its channel axis with them
+    with torch.no_grad(), _exact():
+        y2, s2 = conv(x[:, 0], fir[:, 0], state=None, return_state=True)
+    assert tuple(y2.shape) == (2, sum(BLOCKS)) and tuple(s2.shape) == (2, 299)
+    assert_close(y2.cpu(), _lin64(x[:, :1].cpu(), fir[:, :1].cpu())[:, 0], 1e-5, "FIRConvolution 2-D")
+
+
+@pytest.mark.parametrize("channel", ["mono", "stereo", "midside"])
+def test_fir_filter_streams(channel):
+    from grafx_amd.processors import FIRFilter
+
+    m = FIRFilter(fir_len=255, processor_channel=channel, flashfftconv=False).cuda()
+    C = 1 if channel == "mono" else 2
+    x = torch.randn(2, C, sum(BLOCKS), generator=torch.Generator().manual_seed(2)).cuda()
+    p = _params(m, 2, 3)
+    with torch.no_grad(), _exact():
+        whole = m(x, **p)
+        y, state = _stream(lambda b, s: m(b, **p, state=s, return_state=True), x)
+    assert tuple(state.shape) == (2, C, 254)
+    assert_close(y.cpu(), whole.cpu(), 1e-5, f"FIRFilter {channel}")
+
+
+@pytest.mark.parametrize("pre_delay", [0, 5])
+def test_multitap_delay_streams(pre_delay):
+    from grafx_amd.processors import MultitapDelay
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        m = MultitapDelay(segment_len=100, num_segments=3, zp_filter_bins=5, flashfftconv=False, pre_delay=pre_delay).cuda()
+    x = torch.randn(2, 2, sum(BLOCKS), generator=torch.Generator().manual_seed(4)).cuda()
+    p = _params(m, 2, 5)
+    with torch.no_grad(), _exact():
+        whole, _ = m(x, **p)
+
+        def block(b, s):
+            y, loss, s = m(b, **p, state=s, return_state=True)
+            assert "radii_reg" in loss
+            return y, s
+
+        y, state = _stream(block, x)
+    assert tuple(state.shape) == (2, 2, 300 + pre_delay - 1)
+    assert_close(y.cpu(), whole.cpu(), 1e-5, f"MultitapDelay pre_delay={pre_delay}")
+
+
+@pytest.mark.parametrize("channel", ["midside", "stereo", "mono"])
+def test_filtered_noise_shaping_reverb_streams(channel):
+    from grafx_amd.processors import FilteredNoiseShapingReverb
+
+    m = FilteredNoiseShapingReverb(ir_len=600, num_bands=3, processor_channel=channel, noise_randomness="fixed",
+                                   flashfftconv=False).cuda()
+    C = 1 if channel == "mono" else 2
+    x = torch.randn(2, C, sum(BLOCKS), generator=torch.Generator().manual_seed(6)).cuda()
+    p = _params(m, 2, 7)
+    with torch.no_grad(), _exact():
+        whole = m(x, **p)
+        y, state = _stream(lambda b, s: m(b, **p, state=s, return_state=True), x)
+    assert tuple(state.shape) == (2, C, 599)
+    assert_close(y.cpu(), whole.cpu(), 1e-5, f"FilteredNoiseShapingReverb {channel}")
+
+
+@pytest.mark.parametrize("path", ["direct", "out", "prepared"])
+@pytest.mark.parametrize("channel", ["mono", "stereo", "midside", "pseudo_midside"])
+def test_stft_masked_noise_reverb_streams(channel, path):
+    """fixed_noise=True in every channel mode: forward() on (R, C, L) rows, in-place rendering into a strided view of a
+    buffer (_out), and the render's prepared path (spectra from prepare(); not offered in "midside" mode)."""
+    from grafx_amd.processors import STFTMaskedNoiseReverb
+
+    m = STFTMaskedNoiseReverb(ir_len=1501, processor_channel=channel, fixed_noise=True, flashfftconv=False).cuda()
+    B, n, C = 1, 2, 2
+    x = torch.randn(B * n, C, sum(BLOCKS), generator=torch.Generator().manual_seed(8)).cuda()
+    p = _params(m, B * n, 9)
+    prep = m.prepare(**p) if path == "prepared" else None
+    if path == "prepared" and prep is None:
+        assert channel == "midside"
+        path = "out"
+
+    def block(b, s):
+        if path == "direct":
+            return m(b, **p, state=s, return_state=True)
+        L = b.shape[-1]
+        xbuf = torch.zeros(B, n + 1, C, L, device="cuda")
+        xbuf[:, :n] = b.view(B, n, C, L)
+        obuf = torch.full((B, n + 1, C, L), float("nan"), device="cuda")
+        y, s = m(xbuf[:, :n], **p, _out=obuf[:, 1:], _prepared=prep, state=s, return_state=True)
+        assert y.data_ptr() == obuf[:, 1:].data_ptr() and torch.isnan(obuf[:, 0]).all()
+        return obuf[:, 1:].reshape(B * n, C, L).clone(), s
+
+    with torch.no_grad(), _exact():
+        whole = m(x, **p)
+        y, state = _stream(block, x)
+    assert tuple(state.shape) == (B * n, C, 1500)
+    assert_close(y.cpu(), whole.cpu(), 1e-5, f"STFTMaskedNoiseReverb {channel} ({path})")
+
+
+# ------------------------------------------------------------------------------------------------- refusals
+def test_refusals():
+    from grafx_amd import ops
+    from grafx_amd.processors import FilteredNoiseShapingReverb, STFTMaskedNoiseReverb
+    from grafx_amd.processors.core.convolution import FIRConvolution, convolve
+
+    N, L = 65, 256
+    x = torch.randn(2, 2, L, device="cuda")
+    h = torch.randn(2, 2, N, device="cuda")
+    Hs = ops.fir_spectrum(h.reshape(4, N))
+    zi = torch.zeros(2, 2, N - 1, device="cuda")
+    # modes that look ahead of the block have no carried past
+    for mode in ("zerophase", "full"):
+        with pytest.raises(ValueError, match="causal"):
+            convolve(x, h, mode=mode, state=zi)
+        with pytest.raises(ValueError, match="causal"):
+            FIRConvolution(mode=mode, flashfftconv=False)(x, h, return_state=True)
+    # a fresh impulse response per block is not a stream
+    m = STFTMaskedNoiseReverb(ir_len=1501, fixed_noise=False, flashfftconv=False).cuda()
+    with pytest.raises(ValueError, match="fixed_noise"):
+        m(x, **_params(m, 2, 1), return_state=True)
+    f = FilteredNoiseShapingReverb(ir_len=600, num_bands=3, flashfftconv=False).cuda()
+    with pytest.raises(ValueError, match="noise_randomness"):
+        f(x, **_params(f, 2, 1), return_state=True)
+    # what the stateful entry does not do
+    with pytest.raises(ValueError, match="tee"):
+        ops.fftconv(x, Hs, N, 2, tee=torch.empty_like(x), zi=zi)
+    with pytest.raises(ValueError, match="rowmax"):
+        ops.fftconv(x, Hs, N, 2, rowmax={}, zi=zi)
+    with pytest.raises(ValueError, match="off"):
+        ops.fftconv(x, Hs, N, 2, off=N // 2, zi=zi)
+    with pytest.raises(ValueError, match="Lout"):
+        ops.fftconv(x, Hs, N, 2, Lout=L + N - 1, return_state=True)
+    with pytest.raises(ValueError, match="part_len"):
+        ops.fftconv(x, Hs, N, 2, part_len=9000, zi=zi)
+    with pytest.raises(ValueError, match="schedule"):
+        ops.fftconv_state(x, Hs, N, 2, zi=zi, schedule="pipe")
+    # the state: shape (named in the message), dtype, device
+    for bad in (torch.zeros(2, 2, N, device="cuda"), torch.zeros(2, 1, N - 1, device="cuda"), torch.zeros(4, N - 1, device="cuda")):
+        with pytest.raises(ValueError, match=r"\(2, 2, 64\)"):
+            ops.fftconv_state(x, Hs, N, 2, zi=bad)
+        with pytest.raises(ValueError, match=r"\(2, 2, 64\)"):
+            convolve(x, h, mode="causal", state=bad)
+    for bad in (zi.double(), zi.half(), zi.cpu()):
+        with pytest.raises(ValueError, match=r"\(2, 2, 64\)"):
+            ops.fftconv_state(x, Hs, N, 2, zi=bad)
+        with pytest.raises(ValueError, match=r"\(2, 2, 64\)"):
+            convolve(x, h, mode="causal", state=bad)
+    # zi and zf sharing memory: refused by the wrapper, and by the library itself
+    buf = torch.zeros(2 * 2 * (N - 1) + 8, device="cuda")
+    a, b = buf[: 4 * (N - 1)].view(2, 2, N - 1), buf[8 : 8 + 4 * (N - 1)].view(2, 2, N - 1)
+    with pytest.raises(ValueError, match="share memory"):
+        ops.fftconv_state(x, Hs, N, 2, zi=a, zf=b)
+    with pytest.raises(ValueError, match="share memory"):
+        ops.fftconv_state(x, Hs, N, 2, zi=a, zf=a)
+    from grafx_amd._lib import lib
+
+    y = torch.empty_like(x)
+    xmap, ymap = ops.rowmap(x)[0], ops.rowmap(y)[0]
+    rc = lib().gfx_fftconv_state_f32(x.data_ptr(), xmap, Hs.data_ptr(), 2, y.data_ptr(), ymap, a.data_ptr(), b.data_ptr(), 2, 2,
+                                     2, L, N, 0, 0, 0, torch.cuda.current_stream().cuda_stream)
+    assert rc == ops.GFX_EINVAL
+    rc = lib().gfx_fftconv_state_f32(x.data_ptr(), xmap, Hs.data_ptr(), 2, y.data_ptr(), ymap, a.data_ptr(), 0, 2, 2, 2, L, N,
+                                     0, 0, 2, torch.cuda.current_stream().cuda_stream)
+    assert rc == ops.GFX_EINVAL, "GFX_SCHED_PIPE must be refused: a call with state never takes the persistent kernels"
