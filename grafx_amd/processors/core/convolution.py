@@ -87,6 +87,15 @@ def reference_aliases(lx, lh, exact=False):
     return (lx + lh - 1) % 2 == 1 and not (_EXACT.get() or exact)
 
 
+def require_alias_length(P):
+    """Every route to the aliasing kernels asks here first: beyond their range the caller learns the limit and the way
+    out, not the plan build's status code."""
+    if not ops.odd_alias_supported(P):
+        raise NotImplementedError(f"convolve: the reference's odd-length aliasing (P = Lx + Lh - 1 = {P}) is implemented for "
+                                  "P <= 11,184,811; use a filter length that makes P even, or "
+                                  "set_exact_convolution(True) for the plain linear convolution")
+
+
 def odd_length_alias(z, lo=0, length=None, precise=False):
     """irfft_{P-1}(rfft_P(z))[..., lo : lo + length] for a full linear convolution z of odd length P
     (convolution.py:123-126): two chirp-z transforms on the LDS FFT tile (gfx_odd_alias_f32, no FFT library).
@@ -99,10 +108,7 @@ def odd_length_alias(z, lo=0, length=None, precise=False):
     1.5 P: 233 s of audio at 48 kHz); longer signals raise."""
     P = z.shape[-1]
     length = P - 1 - lo if length is None else length
-    if not ops.odd_alias_supported(P):
-        raise NotImplementedError(f"convolve: the reference's odd-length aliasing (P = Lx + Lh - 1 = {P}) is implemented for "
-                                  "P <= 11,184,811; use a filter length that makes P even, or "
-                                  "set_exact_convolution(True) for the plain linear convolution")
+    require_alias_length(P)
     if torch.is_grad_enabled() and z.requires_grad:
         from ... import autograd as diff
 
@@ -168,6 +174,7 @@ def convolve_taps(x, Hs, N, Cf, mode, out=None, tee=None, exact=False, h_rows=No
             return ops.fftconv(x, Hs, N, Cf, Lout=L, off=N // 2, out=out, h_rows=h_rows)
         return ops.fftconv(x, Hs, N, Cf, Lout=L + N - 1, off=0, out=out, h_rows=h_rows)
     lo, length = {"causal": (0, L), "zerophase": (N // 2, L)}.get(mode, (0, L + N - 2))
+    require_alias_length(L + N - 1)      # (before the full-length convolution is spent on it; the calls below go straight to ops)
     rm = {}     # the rows' maxima, when the convolution kernel leaves them (the pair scaling of the aliasing: ops.odd_alias)
     z = ops.fftconv(x, Hs, N, Cf, Lout=L + N - 1, off=0, h_rows=h_rows, tee=tee, rowmax=rm)
     if out is not None and not (torch.is_grad_enabled() and z.requires_grad):
