@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .core._buffer_io import StreamIO, child_stream
 from .core.utils import rms_difference
 
 
@@ -14,7 +15,18 @@ def _split(out):
     return out if isinstance(out, tuple) else (out, None)
 
 
-class DryWet(nn.Module):
+class _Container(StreamIO):
+    """The block protocol of a container: its carry is the tuple of its children's carries, in their order."""
+
+    def _children(self):
+        return [self.processor] if hasattr(self, "processor") else list(self.processors.values())
+
+    def stream_check(self):
+        for proc in self._children():
+            child_stream(proc, self).stream_check()
+
+
+class DryWet(_Container, nn.Module):
     """y = w * processor(x) + (1 - w) * x (container.py:10-82)."""
 
     def __init__(self, processor, external_param=True):
@@ -28,6 +40,14 @@ class DryWet(nn.Module):
         mixed = w * wet + (1 - w) * input_signals
         return mixed if extra is None else (mixed, extra)
 
+    def stream_block(self, x4, out4, carry, drywet_weight, **processor_kwargs):
+        wet = torch.empty_like(out4, memory_format=torch.contiguous_format)
+        carry = child_stream(self.processor, self).stream_block(x4, wet, None if carry is None else carry[0],
+                                                                **processor_kwargs)
+        w = drywet_weight.view(*x4.shape[:2], 1, 1)
+        torch.add(w * wet, (1 - w) * x4, out=out4)
+        return (carry,)
+
     def parameter_size(self):
         size = self.processor.parameter_size()
         if not self.external_param:
@@ -35,7 +55,7 @@ class DryWet(nn.Module):
         return size
 
 
-class SerialChain(nn.Module):
+class SerialChain(_Container, nn.Module):
     """Processors applied one after another; parameters are a dict keyed like the processors (85-148)."""
 
     def __init__(self, processors):
@@ -50,11 +70,20 @@ class SerialChain(nn.Module):
                 intermediates[name] = extra
         return signal, intermediates
 
+    def stream_block(self, x4, out4, carry, **processors_kwargs):
+        signal, carries, last = x4, [], len(self.processors) - 1
+        for i, (name, proc) in enumerate(self.processors.items()):
+            dest = out4 if i == last else torch.empty_like(out4, memory_format=torch.contiguous_format)
+            carries.append(child_stream(proc, self).stream_block(signal, dest, None if carry is None else carry[i],
+                                                                 **processors_kwargs[name]))
+            signal = dest
+        return tuple(carries)
+
     def parameter_size(self):
         return {k: v.parameter_size() for k, v in self.processors.items()}
 
 
-class ParallelMix(nn.Module):
+class ParallelMix(_Container, nn.Module):
     """Weighted sum of processors fed the same input (151-222)."""
 
     def __init__(self, processors, activation="softmax"):
@@ -81,13 +110,25 @@ class ParallelMix(nn.Module):
             total = out if total is None else total + out
         return total, intermediates
 
+    def stream_block(self, x4, out4, carry, parallel_weights, **processors_kwargs):
+        weights = self.get_weight(parallel_weights).view(*x4.shape[:2], -1)
+        total, carries = None, []
+        for i, (name, proc) in enumerate(self.processors.items()):
+            branch = torch.empty_like(out4, memory_format=torch.contiguous_format)
+            carries.append(child_stream(proc, self).stream_block(x4, branch, None if carry is None else carry[i],
+                                                                 **processors_kwargs[name]))
+            branch = branch * weights[..., i, None, None]
+            total = branch if total is None else total + branch
+        out4.copy_(total)
+        return tuple(carries)
+
     def parameter_size(self):
         size = {k: v.parameter_size() for k, v in self.processors.items()}
         size["parallel_weights"] = len(self.processors)
         return size
 
 
-class GainStagingRegularization(nn.Module):
+class GainStagingRegularization(_Container, nn.Module):
     """Adds the input/output log-RMS difference to the intermediates (231-299)."""
 
     def __init__(self, processor, key="gain_reg"):
@@ -101,6 +142,11 @@ class GainStagingRegularization(nn.Module):
         assert self.key not in extra
         extra[self.key] = rms_difference(input_signals, out)
         return out, extra
+
+    def stream_block(self, x4, out4, carry, **processor_kwargs):
+        """The regulariser is a by-product of the signal path: a streamed block renders the wrapped processor alone."""
+        return (child_stream(self.processor, self).stream_block(x4, out4, None if carry is None else carry[0],
+                                                                **processor_kwargs),)
 
     def parameter_size(self):
         return self.processor.parameter_size()

@@ -8,7 +8,13 @@ through a gfx_rowmap_t read and write the buffer directly; the default falls bac
 
 ``prepare(**params[, _shared_rows]) -> Prepared | None`` (optional): the parameter-only part of ``render_into``
 (filter design, impulse-response synthesis, spectra).  The render loop runs it ahead of time on a side stream,
-under the signal kernels of the earlier stages, and hands the result back as ``render_into(..., _prepared=...)``."""
+under the signal kernels of the earlier stages, and hands the result back as ``render_into(..., _prepared=...)``.
+
+``stream_block(x4, out4, carry, **params) -> carry`` (every processor class): one block of a streamed render.  It writes
+the block's output into ``out4`` like ``render_into`` and returns what the next block's call needs in ``carry`` -- whatever
+the processor's own keywords call it (``state=``, ``history=``), None for a memoryless processor and for the first block.
+``stream_check()`` raises the processor's own ValueError when its configuration cannot be rendered in blocks; the render
+asks every stage before it launches the first."""
 
 
 class Prepared:
@@ -19,7 +25,40 @@ class Prepared:
         self.__dict__.update(scalars)
 
 
-class BufferIO:
+def write_rows(out4, y):
+    """A processor's (R, C, L) / (B, n, C, L) result (or ``(result, by-products)``) into the (B, n, C, L) destination view."""
+    y = y[0] if isinstance(y, tuple) else y
+    if y.data_ptr() != out4.data_ptr():
+        out4.copy_(y.reshape(out4.shape))
+    return out4
+
+
+def child_stream(proc, owner):
+    """The wrapped processor of a container, which must speak the block protocol itself."""
+    if not hasattr(proc, "stream_block"):
+        raise ValueError(f"{type(owner).__name__}: the wrapped {type(proc).__name__} has no stream_block()")
+    return proc
+
+
+class StreamIO:
+    """The block protocol of a processor without memory: the block is rendered like any signal, nothing is carried."""
+
+    def stream_check(self):
+        """Raises ValueError, with the reason, when this configuration cannot be rendered in blocks."""
+
+    def stream_block(self, x4, out4, carry, _shared_rows=None, **params):
+        self.stream_check()
+        if hasattr(self, "render_into"):
+            extra = {} if _shared_rows is None else {"_shared_rows": _shared_rows}
+            self.render_into(x4, out4, **extra, **params)
+        else:
+            if _shared_rows is not None:
+                params = {k: expand_shared(v, shared_reps(x4, _shared_rows)) for k, v in params.items()}
+            write_rows(out4, self.forward(x4.reshape(-1, *x4.shape[2:]), **params))
+        return None
+
+
+class BufferIO(StreamIO):
     def render_into(self, x4, out4, **params):
         y = self.forward(x4.reshape(-1, *x4.shape[2:]), **params)
         out4.copy_(y.view(out4.shape))

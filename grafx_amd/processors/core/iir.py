@@ -7,7 +7,24 @@ import torch.nn as nn
 from ... import autograd as diff
 from ... import ops
 from ...autograd import needs_grad
-from .convolution import FIRConvolution, convolve_taps
+from ._buffer_io import StreamIO, write_rows
+from .convolution import FIRConvolution, check_state, convolve_taps
+
+
+def map_signal(fn, result):
+    """``fn`` on the signal of a result that is ``y`` or, from a block-wise call, ``(y, carry)``."""
+    return (fn(result[0]), *result[1:]) if isinstance(result, tuple) else fn(result)
+
+
+class BiquadStream(StreamIO):
+    """The block protocol of a processor whose ``forward(x, **params, **block)`` hands the block-wise keywords on to its
+    ``self.biquad``: the carry is the input history on the "fsm" backend, the recursion's state on "lfilter" / "ssm"."""
+
+    def stream_block(self, x4, out4, carry, **params):
+        key = "history" if self.biquad.backend == "fsm" else "state"
+        y, carry = self.forward(x4.reshape(-1, *x4.shape[2:]), **params, **{key: carry, "return_" + key: True})
+        write_rows(out4, y)
+        return carry
 
 
 class IIRFilter(nn.Module):
@@ -165,18 +182,50 @@ class IIRFilter(nn.Module):
             y = b0[:, :, k] * y + diff.BiquadCascadeFn.apply(x, Bk, Ak)
         return y
 
+    def _process_fsm_block(self, x, Bs, As, out, tee, shared_rows, final, history, return_history):
+        """One block of a stream on the frequency-sampled backend: the same taps, the stateful causal convolution."""
+        N = self.fsm_fir_len
+        if tee is not None:
+            tee.copy_(x)
+        if needs_grad(x, Bs, As, history):
+            if N <= self.FSM_NATIVE_MAX and Bs.shape[-1] == 3:
+                h = diff.FsmFirFn.apply(Bs, As, N, self._plan(Bs.device))
+            else:
+                h = diff.fsm_fir(Bs, As, N)
+            y, zf = diff.convolve(x, h, "causal", final=final, state=check_state(history, x, N, "IIRFilter(backend='fsm')"),
+                                  return_state=True)
+            if out is not None:
+                out.copy_(y.view(out.shape))
+                y = out
+        else:
+            y, zf = convolve_taps(x, ops.fir_spectrum(self._taps(Bs, As)), N, Bs.shape[1], "causal", out=out,
+                                  h_rows=shared_rows, state=history, return_state=True)
+        return (y, zf) if return_history else y
+
     def forward(self, input_signal, Bs, As, out=None, tee=None, shared_rows=None, final=False, state=None,
-                return_state=False):
+                return_state=False, history=None, return_history=False):
         """``shared_rows``: Bs/As hold that many rows, shared by the batch (signal row r uses r % shared_rows).
         ``final``: the caller returns this output as its own up to linear operations (autograd.TAPE_ONLY).
         ``state`` / ``return_state`` (recursive backends): block-wise processing of a long signal.  ``state`` is the filter
         state entering this block, float32 (R, Cout, K, 2) -- (B, n, Cout, K, 2) for a (B, n, C, L) input -- with
         (w[n-1], w[n-2]) of every section's a0-normalised direct form II (first-order sections: a zero second entry); None
         is silence.  With ``return_state`` the result is ``(y, state)``, the state after the block's last sample: pass it
-        to the next block's call and the blocks' outputs are the one-call output, gradients included."""
+        to the next block's call and the blocks' outputs are the one-call output, gradients included.
+        ``history`` / ``return_history`` (backend "fsm"): block-wise processing of the frequency-sampled FIR.  ``history`` is
+        the last fsm_fir_len - 1 input samples before this block, float32 (R, C_in, fsm_fir_len - 1), oldest first (None:
+        silence) -- the state of core.convolution.convolve, read in place; with ``return_history`` the result is
+        ``(y, history)``.  A call with a history is always the causal linear convolution with the sampled taps: blocks cut
+        anywhere concatenate to the linear convolution of the whole, which equals the one-call output exactly when that
+        call does not alias (L_total + fsm_fir_len - 1 even) or under set_exact_convolution(True) -- the reference's
+        odd-length aliasing is a property of one whole-signal transform and has no block form."""
         if self.backend == "fsm" and (state is not None or return_state):
             raise ValueError("IIRFilter(backend='fsm'): the frequency-sampled FIR carries no recursive state; use the "
                              "recursive backends (backend='lfilter' or 'ssm') for block-wise processing")
+        if history is not None or return_history:
+            if self.backend != "fsm":
+                raise ValueError(f"IIRFilter(backend={self.backend!r}): history / return_history carry the input history of the "
+                                 "frequency-sampled FIR (backend='fsm'); a recursive backend carries state / return_state")
+            return self._process_fsm_block(input_signal, Bs, As, out, tee, shared_rows, final, history, return_history)
         if shared_rows is not None and self.backend != "fsm":
             rows = input_signal.shape[0] * input_signal.shape[1] if input_signal.ndim == 4 else input_signal.shape[0]
             Bs, As = Bs.repeat(rows // shared_rows, 1, 1, 1), As.repeat(rows // shared_rows, 1, 1, 1)  # no row sharing

@@ -8,13 +8,14 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .core._buffer_io import StreamIO, write_rows
 from .core.convolution import FIRConvolution, convolve
 from .core.delay import SurrogateDelay
 from .core.fir import ZeroPhaseFIR
 from .core.utils import normalize_impulse
 
 
-class MultitapDelay(nn.Module):
+class MultitapDelay(StreamIO, nn.Module):
     def __init__(self, segment_len=3000, num_segments=20, num_delay_per_segment=1, processor_channel="stereo",
                  zp_filter_per_tap=True, zp_filter_bins=20, flashfftconv=True, max_input_len=2**17, pre_delay=0,
                  **surrogate_delay_kwargs):
@@ -53,6 +54,12 @@ class MultitapDelay(nn.Module):
         if self.pre_delay != 0:
             y = F.pad(y, (self.pre_delay, 0))[:, :, : -self.pre_delay]
         return y, radii_loss
+
+    def stream_block(self, x4, out4, carry, **params):
+        """The carry is the input history (forward(state=)); the radii loss is no part of the signal path."""
+        y, _, carry = self.forward(x4.reshape(-1, *x4.shape[2:]), state=carry, return_state=True, **params)
+        write_rows(out4, y)
+        return carry
 
     def get_ir(self, delay_z, log_fir_magnitude):
         irs, radii_loss = self.delay(torch.view_as_complex(delay_z.contiguous()))     # (B, taps, T)

@@ -5,7 +5,7 @@ import torch.nn as nn
 from .. import autograd as diff
 from .. import ops
 from ..autograd import needs_grad
-from .core._buffer_io import BufferIO, expand_shared, shared_reps
+from .core._buffer_io import BufferIO, StreamIO, expand_shared, shared_reps
 from .core.convolution import reference_aliases, resolve_flashfftconv
 from .core.envelope import Ballistics, TruncatedOnePoleIIRFilter, no_carried_state
 
@@ -45,6 +45,18 @@ class _Dynamics(BufferIO, nn.Module):
     def render_into(self, x4, out4, _shared_rows=None, _aux=None, _mix=None, **params):
         extra = {} if _mix is None else {"_mix": _mix}
         return self.forward(x4, _out=out4, _shared_rows=_shared_rows, _aux=_aux, **extra, **params)
+
+    def stream_check(self):
+        if "iir" in (self.energy_smoother, self.gain_smoother):
+            raise ValueError(f"{type(self).__name__}: " + no_carried_state(self.iir_len))
+
+    def stream_block(self, x4, out4, carry, _shared_rows=None, **params):
+        """The carry is the (B, n, S) state of the "ballistics" smoothers; without a smoother there is no memory."""
+        self.stream_check()
+        if "ballistics" not in (self.energy_smoother, self.gain_smoother):
+            self.render_into(x4, out4, _shared_rows=_shared_rows, **params)
+            return None
+        return self.forward(x4, _out=out4, _shared_rows=_shared_rows, state=carry, return_state=True, **params)[1]
 
     def forward(self, input_signals, log_threshold, log_ratio, log_knee=None, z_alpha_pre=None, z_alpha_post=None,
                 _out=None, _shared_rows=None, _aux=None, _mix=None, state=None, return_state=False):
@@ -119,8 +131,7 @@ class _Dynamics(BufferIO, nn.Module):
         number of "ballistics" smoothers of the module: column 0 the energy smoother's envelope, the last column the gain
         smoother's, as the block before left them (None: the first block, every smoother starts from 1 as in a plain call).
         ``return_state``: -> (y, state).  The envelopes of the blocks are the one-call envelopes bit for bit."""
-        if "iir" in (self.energy_smoother, self.gain_smoother):
-            raise ValueError(f"{type(self).__name__}: " + no_carried_state(self.iir_len))
+        self.stream_check()
         pre, post = self.energy_smoother == "ballistics", self.gain_smoother == "ballistics"
         S = int(pre) + int(post)
         if S == 0:
@@ -267,7 +278,7 @@ class ApproxCompressor(Compressor):
         return {"z_alpha": 1, "log_threshold": 1, "log_ratio": 1, "log_knee": 1}
 
 
-class ApproxNoiseGate(nn.Module):
+class ApproxNoiseGate(StreamIO, nn.Module):
     """Reference dynamics.py:123-210.  Its knee differs from NoiseGate's (ratio = exp(r), full-width knee,
     +1e-3 in the denominator), so the gain curve is evaluated with elementwise torch ops on the smoothed
     log-energy produced by the HIP one-pole kernel."""
@@ -284,6 +295,9 @@ class ApproxNoiseGate(nn.Module):
             energy = ops.energy(input_signals)
         G = torch.log(self.smoother(energy, z_alpha) + 1e-5)
         return self.compute_gain(G, log_threshold - 6, log_ratio, log_knee) * input_signals
+
+    def stream_check(self):
+        raise ValueError("ApproxNoiseGate: " + no_carried_state(self.smoother.iir_len))
 
     def compute_gain(self, log_energy, log_threshold, log_ratio, log_knee):
         """(R, 1, L) linear gain of this gate's own knee (dynamics.py:185-203)."""

@@ -3,13 +3,13 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .core._buffer_io import BufferIO, Prepared, expand_shared, shared_reps
+from .core._buffer_io import BufferIO, Prepared, StreamIO, expand_shared, shared_reps, write_rows
 from .core.convolution import convolve, convolve_taps
 from .core.fir import ZeroPhaseFilterBankFIR, ZeroPhaseFIR
 from .core.geq import GraphicEqualizerBiquad
 from .. import autograd as diff
 from ..autograd import needs_grad
-from .core.iir import IIRFilter
+from .core.iir import BiquadStream, IIRFilter, map_signal
 from .core.midside import lr_to_ms, ms_to_lr
 
 
@@ -28,18 +28,23 @@ class ParametricEqualizer(BufferIO, nn.Module):
     accepts_strided_rows = True   # forward() also takes a strided (B, n, C, L) view and then returns (B, n, C, L)
 
     def forward(self, input_signals, w0, q_inv, log_gain, _out=None, _tee=None, _shared_rows=None, state=None,
-                return_state=False):
+                return_state=False, history=None, return_history=False):
         """``state`` / ``return_state``: block-wise processing on a recursive backend (IIRFilter.forward); the state belongs
-        to the filtered channels, i.e. to mid and side when ``processor_channel="midside"``."""
+        to the filtered channels, i.e. to mid and side when ``processor_channel="midside"``.
+        ``history`` / ``return_history``: block-wise processing on the "fsm" backend (IIRFilter.forward): the last
+        fsm_fir_len - 1 samples of what the convolution reads -- in "midside" mode the mid/side signal --, oldest first.
+        A call with a history is always the causal linear convolution (see core.convolution.convolve)."""
         self._check_bands()
         if needs_grad(input_signals, w0, q_inv, log_gain):
             Bs, As = diff.PeqCoeffsFn.apply(w0, q_inv, log_gain, self.use_shelving_filters)
         else:
             Bs, As = ops.peq_coeffs(w0, q_inv, log_gain, self.use_shelving_filters)
         block = {} if state is None and not return_state else {"state": state, "return_state": return_state}
+        if history is not None or return_history:
+            block.update(history=history, return_history=return_history)
         if self.processor_channel == "midside":
             y = self.biquad(lr_to_ms(input_signals), Bs, As, shared_rows=_shared_rows, final=True, **block)
-            return (ms_to_lr(y[0]), y[1]) if return_state else ms_to_lr(y)
+            return (ms_to_lr(y[0]), y[1]) if return_state or return_history else ms_to_lr(y)
         return self.biquad(input_signals, Bs, As, out=_out, tee=_tee, shared_rows=_shared_rows, final=True, **block)
 
     def get_biquad_coefficients_with_shelving_filters(self, cos_w0, alpha, A):
@@ -69,7 +74,22 @@ class ParametricEqualizer(BufferIO, nn.Module):
         Bs, As = ops.peq_coeffs(w0, q_inv, log_gain, self.use_shelving_filters)
         return Prepared(ops.fir_spectrum(self.biquad._taps(Bs, As)), Cf=Bs.shape[1])
 
-    def render_into(self, x4, out4, tee=None, _shared_rows=None, _prepared=None, **params):
+    def render_into(self, x4, out4, tee=None, _shared_rows=None, _prepared=None, history=None, return_history=False,
+                    **params):
+        """``history`` / ``return_history``: as in forward(); the prepared spectra are the same with and without one."""
+        if history is not None or return_history:
+            if _prepared is not None:
+                y, zf = convolve_taps(x4, _prepared.tensors[0], self.biquad.fsm_fir_len, _prepared.Cf, "causal", out=out4,
+                                      tee=tee, h_rows=_shared_rows, state=history, return_state=True)
+            elif self.processor_channel == "midside":
+                if tee is not None:
+                    tee.copy_(x4)
+                y, zf = self.forward(x4, _shared_rows=_shared_rows, history=history, return_history=True, **params)
+                y = write_rows(out4, y)
+            else:
+                y, zf = self.forward(x4, _out=out4, _tee=tee, _shared_rows=_shared_rows, history=history,
+                                     return_history=True, **params)
+            return (y, zf) if return_history else y
         if _prepared is not None:
             return convolve_taps(x4, _prepared.tensors[0], self.biquad.fsm_fir_len, _prepared.Cf, "causal", out=out4,
                                  tee=tee, exact=self.biquad.flashfftconv, h_rows=_shared_rows)
@@ -81,13 +101,30 @@ class ParametricEqualizer(BufferIO, nn.Module):
             return super().render_into(x4, out4, **params)
         return self.forward(x4, _out=out4, _tee=tee, _shared_rows=_shared_rows, **params)
 
+    def stream_block(self, x4, out4, carry, _shared_rows=None, _prepared=None, **params):
+        """The carry is the input history on the "fsm" backend, the recursion's state on "lfilter" / "ssm"."""
+        if self.biquad.backend == "fsm":
+            return self.render_into(x4, out4, _shared_rows=_shared_rows, _prepared=_prepared, history=carry,
+                                    return_history=True, **params)[1]
+        midside = self.processor_channel == "midside"
+        y, carry = self.forward(x4, _out=None if midside else out4, _shared_rows=_shared_rows, state=carry,
+                                return_state=True, **params)
+        write_rows(out4, y)
+        return carry
+
     def parameter_size(self):
         n_channels = 1 if self.processor_channel == "mono" else 2
         size = (n_channels, self.num_filters)
         return {k: size for k in ["w0", "q_inv", "log_gain"]}
 
 
-class ZeroPhaseFIREqualizer(nn.Module):
+class _ZeroPhase(StreamIO):
+    def stream_check(self):
+        raise ValueError(f"{type(self).__name__}: a zero-phase convolution looks ahead of the block by half its filter, so a "
+                         "chain of blocks is not a stream")
+
+
+class ZeroPhaseFIREqualizer(_ZeroPhase, nn.Module):
     """Single-channel zero-phase FIR equaliser (reference eq.py:25-79): log-magnitude -> windowed
     zero-phase FIR of 2*bins-1 taps (odd, so the reference's convolve is an exact linear convolution for
     even audio lengths) -> HIP overlap-save convolution in "zerophase" mode."""
@@ -105,7 +142,7 @@ class ZeroPhaseFIREqualizer(nn.Module):
         return {"log_magnitude": self.num_magnitude_bins}
 
 
-class NewZeroPhaseFIREqualizer(nn.Module):
+class NewZeroPhaseFIREqualizer(_ZeroPhase, nn.Module):
     """Zero-phase FIR equaliser with optional perceptual filterbank parameterisation (reference eq.py:80-214).
     Taps = 2*bins-1 (odd), so for even audio lengths the reference's convolve() is an exact linear convolution
     and the whole signal path is the HIP overlap-save kernel in "zerophase" mode."""
@@ -133,7 +170,7 @@ class NewZeroPhaseFIREqualizer(nn.Module):
         return {"log_magnitude": (1 if self.processor_channel == "mono" else 2, n_bins)}
 
 
-class GraphicEqualizer(nn.Module):
+class GraphicEqualizer(BiquadStream, nn.Module):
     """Cascade of fixed-frequency peaking biquads (24 Bark or 31 third-octave bands; reference eq.py:339-436):
     band design on the GPU (core/geq.py), then the native frequency-sampling kernels."""
 
@@ -150,13 +187,14 @@ class GraphicEqualizer(nn.Module):
     # 1e-4 .. 4e-4 from a float64 evaluation of its formulas there; 24 Bark bands meet it at 1e-5 in float32)
     PRECISE_BANDS = 24
 
-    def forward(self, input_signals, log_gains):
+    def forward(self, input_signals, log_gains, **block):
+        """``**block``: the block-wise keywords of IIRFilter.forward (``state`` / ``history`` and their ``return_`` twins)."""
         precise = (self.geq.num_bands > self.PRECISE_BANDS and self.biquad.backend == "fsm"
                    and ops.iir_fsm_native(self.biquad.fsm_fir_len) and not needs_grad(input_signals, log_gains))
         Bs, As = self.geq(log_gains, precise=precise)
         if self.processor_channel == "midside":
-            return ms_to_lr(self.biquad(lr_to_ms(input_signals), Bs, As))
-        return self.biquad(input_signals, Bs, As)
+            return map_signal(ms_to_lr, self.biquad(lr_to_ms(input_signals), Bs, As, **block))
+        return self.biquad(input_signals, Bs, As, **block)
 
     def parameter_size(self):
         return {"log_gains": (1 if self.processor_channel == "mono" else 2, self.geq.num_bands)}

@@ -6,16 +6,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .core._buffer_io import BufferIO
+from .core._buffer_io import BufferIO, StreamIO, write_rows
 from .. import autograd as diff
 from ..autograd import needs_grad
 from .core.convolution import FIRConvolution
-from .core.iir import IIRFilter
+from .core.iir import BiquadStream, IIRFilter, map_signal
 from .core.midside import lr_to_ms, ms_to_lr
 from .core.utils import normalize_impulse
 
 
-class FIRFilter(nn.Module):
+class FIRFilter(StreamIO, nn.Module):
     """Learnable FIR taps: tanh -> energy normalisation -> causal convolution (reference filter.py:20-84).
     Upstream's constructor reads ``self.processor_channel`` before assigning it (filter.py:39) and therefore
     cannot be instantiated; this class implements what the rest of that code plainly intends."""
@@ -45,11 +45,16 @@ class FIRFilter(nn.Module):
             y = ms_to_lr(y)
         return (y, zf) if return_state else y
 
+    def stream_block(self, x4, out4, carry, **params):
+        y, carry = self.forward(x4.reshape(-1, *x4.shape[2:]), state=carry, return_state=True, **params)
+        write_rows(out4, y)
+        return carry
+
     def parameter_size(self):
         return {"fir": (self.num_channels, self.fir_len)}
 
 
-class PoleZeroFilter(nn.Module):
+class PoleZeroFilter(BiquadStream, nn.Module):
     """Biquad cascade parameterised by complex zeros and (tanh-radius-limited) poles (reference filter.py:171-239).
     Two upstream details are kept because they change the numbers: the denominator's z^-2 coefficient uses the
     *unlimited* pole radius (filter.py:224), and one coefficient set is shared by all channels."""
@@ -59,15 +64,16 @@ class PoleZeroFilter(nn.Module):
         self.num_filters = num_filters
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, log_gain, poles, zeros):
+    def forward(self, input_signals, log_gain, poles, zeros, **block):
+        """``**block``: the block-wise keywords of IIRFilter.forward (``state`` / ``history`` and their ``return_`` twins)."""
         p, z = torch.view_as_complex(poles.contiguous()), torch.view_as_complex(zeros.contiguous())
         p_radius, z_radius = p.abs(), z.abs()
         p = p * torch.tanh(p_radius) / (p_radius + 1e-5)
         one = torch.ones_like(p_radius)
         Bs = torch.stack([one, -2 * z.real, z_radius.square()], -1)
         As = torch.stack([one, -2 * p.real, p_radius.square()], -1)
-        y = self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1))
-        return torch.exp(log_gain).unsqueeze(-1) * y
+        y = self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), **block)
+        return map_signal(lambda v: torch.exp(log_gain).unsqueeze(-1) * v, y)
 
     def parameter_size(self):
         return {"log_gain": 1, "poles": (self.num_filters, 2), "zeros": (self.num_filters, 2)}
@@ -80,17 +86,26 @@ class BiquadFilter(BufferIO, nn.Module):
         self.normalized = normalized
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, Bs, A1_pre, A2_pre, A0=None, _out=None, state=None, return_state=False):
-        """``state`` / ``return_state``: block-wise processing on a recursive backend (IIRFilter.forward)."""
+    def forward(self, input_signals, Bs, A1_pre, A2_pre, A0=None, _out=None, state=None, return_state=False, history=None,
+                return_history=False):
+        """``state`` / ``return_state``: block-wise processing on a recursive backend (IIRFilter.forward).
+        ``history`` / ``return_history``: block-wise processing on the "fsm" backend (IIRFilter.forward): the last
+        fsm_fir_len - 1 input samples, oldest first; a call with a history is always the causal linear convolution."""
         A0 = A0 if self.normalized else None
         block = {} if state is None and not return_state else {"state": state, "return_state": return_state}
-        if needs_grad(input_signals, Bs, A1_pre, A2_pre, A0, state):
+        if history is not None or return_history:
+            block.update(history=history, return_history=return_history)
+        if needs_grad(input_signals, Bs, A1_pre, A2_pre, A0, state, history):
             return self.biquad(input_signals, *diff.biquad_coefficients(Bs, A1_pre, A2_pre, A0), out=_out, final=True, **block)
         Bs, As = ops.biquad_coeffs(Bs, A1_pre, A2_pre, A0)
         return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), out=_out, **block)
 
     def render_into(self, x4, out4, **params):
         return self.forward(x4, _out=out4, **params)
+
+    def stream_block(self, x4, out4, carry, **params):
+        key = "history" if self.biquad.backend == "fsm" else "state"
+        return self.forward(x4, _out=out4, **params, **{key: carry, "return_" + key: True})[1]
 
     def parameter_size(self):
         size = {"Bs": (self.num_filters, 3), "A1_pre": self.num_filters, "A2_pre": self.num_filters}
@@ -102,16 +117,17 @@ class BiquadFilter(BufferIO, nn.Module):
 # ---- single-biquad parametric filters (reference filter.py:263-560) ----------------------------------
 # Coefficient formulas are a few elementwise ops on (R, 1) tensors (torch, on the GPU); the filtering is
 # the HIP frequency-sampling path of IIRFilter.
-class BaseParametricFilter(nn.Module):
+class BaseParametricFilter(BiquadStream, nn.Module):
     def __init__(self, **backend_kwargs):
         super().__init__()
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, w0, q_inv):
+    def forward(self, input_signals, w0, q_inv, **block):
+        """``**block``: the block-wise keywords of IIRFilter.forward (``state`` / ``history`` and their ``return_`` twins)."""
         w0, q = self.filter_parameter_activations(w0, q_inv)
         cos_w0, alpha = self.compute_common_filter_parameters(w0, q)
         Bs, As = self.get_biquad_coefficients(cos_w0, alpha)
-        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1))
+        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), **block)
 
     @staticmethod
     def get_biquad_coefficients(cos_w0, alpha):
@@ -167,7 +183,7 @@ class AllPassFilter(BaseParametricFilter):
         return den.flip(-1), den
 
 
-class BaseParametricEqualizerFilter(nn.Module):
+class BaseParametricEqualizerFilter(BiquadStream, nn.Module):
     """Stack of `num_filters` equaliser sections of one kind (filter.py:563-617)."""
 
     def __init__(self, num_filters=1, **backend_kwargs):
@@ -175,11 +191,12 @@ class BaseParametricEqualizerFilter(nn.Module):
         self.num_filters = num_filters
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, w0, q_inv, log_gain):
+    def forward(self, input_signals, w0, q_inv, log_gain, **block):
+        """``**block``: the block-wise keywords of IIRFilter.forward (``state`` / ``history`` and their ``return_`` twins)."""
         w, qi, A = self.filter_parameter_activations(w0, q_inv, log_gain)
         cw, alpha = self.compute_common_filter_parameters(w, qi)
         Bs, As = self.get_biquad_coefficients(cw, alpha, A)
-        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1))
+        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), **block)
 
     # the reference's static helpers (filter.py:593-604 and the per-kind coefficient maps), usable on their own
     @staticmethod
@@ -227,7 +244,7 @@ class HighShelf(BaseParametricEqualizerFilter):
         return _shelf_coefficients(cos_w0, alpha, A, -1.0)
 
 
-class StateVariableFilter(nn.Module):
+class StateVariableFilter(BiquadStream, nn.Module):
     """SVF-parameterised biquads (filter.py:223-300)."""
 
     def __init__(self, num_filters=1, **backend_kwargs):
@@ -235,11 +252,12 @@ class StateVariableFilter(nn.Module):
         self.num_filters = num_filters
         self.biquad = IIRFilter(order=2, **backend_kwargs)
 
-    def forward(self, input_signals, twoR, G, c_hp, c_bp, c_lp):
+    def forward(self, input_signals, twoR, G, c_hp, c_bp, c_lp, **block):
+        """``**block``: the block-wise keywords of IIRFilter.forward (``state`` / ``history`` and their ``return_`` twins)."""
         G = torch.tan(math.pi / 2 * torch.sigmoid(G))
         twoR = F.softplus(twoR) / math.log(2) + 1e-2
         Bs, As = self.get_biquad_coefficients(twoR, G, c_hp, c_bp, c_lp)
-        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1))
+        return self.biquad(input_signals, Bs.unsqueeze(1), As.unsqueeze(1), **block)
 
     @staticmethod
     def get_biquad_coefficients(twoR, G, c_hp, c_bp, c_lp):

@@ -16,6 +16,11 @@ def _center(x, remove_dc):
 
 
 class _Waveshaper(BufferIO, nn.Module):
+    def stream_check(self):
+        if self.remove_dc:
+            raise ValueError(f"{type(self).__name__}: remove_dc=True subtracts the mean of the whole signal, which a block "
+                             "does not know; a chain of blocks is not a stream")
+
     def render_into(self, x4, out4, **params):
         if needs_grad(x4, *params.values()):
             return super().render_into(x4, out4, **params)

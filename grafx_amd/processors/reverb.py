@@ -8,7 +8,7 @@ import torch.nn.functional as F
 from .. import autograd as diff
 from .. import ops
 from ..autograd import needs_grad
-from .core._buffer_io import BufferIO, Prepared, expand_shared, shared_reps
+from .core._buffer_io import BufferIO, Prepared, StreamIO, expand_shared, shared_reps, write_rows
 from .core.utils import normalize_impulse
 from .core.convolution import check_state, convolve_taps, resolve_flashfftconv
 from .core.midside import lr_to_ms, ms_to_lr
@@ -192,9 +192,7 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
     def _forward_block(self, x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, _out, _shared_rows,
                        _prepared, state, return_state):
         """forward() with a carried state: the same impulse responses, the stateful causal convolution."""
-        if not self.fixed_noise:
-            raise ValueError("STFTMaskedNoiseReverb: fixed_noise=False draws a fresh impulse response per call, so a chain "
-                             "of blocks is not a stream; state / return_state need fixed_noise=True")
+        self.stream_check()
         N = self.ir_len
         if _prepared is not None:
             return convolve_taps(x, _prepared.tensors[0], N, 2, "causal", out=_out, h_rows=_shared_rows, state=state,
@@ -229,6 +227,16 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
             return (y, zf) if return_state else y
         return convolve_taps(x, Hs, N, 2, "causal", out=_out, h_rows=_shared_rows, state=state, return_state=return_state)
 
+    def stream_check(self):
+        if not self.fixed_noise:
+            raise ValueError("STFTMaskedNoiseReverb: fixed_noise=False draws a fresh impulse response per call, so a chain "
+                             "of blocks is not a stream; state / return_state need fixed_noise=True")
+
+    def stream_block(self, x4, out4, carry, _shared_rows=None, _prepared=None, **params):
+        """The carry is the input history of the convolution (forward(state=))."""
+        return self.forward(x4, _out=out4, _shared_rows=_shared_rows, _prepared=_prepared, state=carry, return_state=True,
+                            **params)[1]
+
     def parameter_size(self):
         size = {"init_log_magnitude": (2, self.num_bins), "delta_log_magnitude": (2, self.num_bins)}
         if self.gain_envelope:
@@ -236,7 +244,7 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         return size
 
 
-class FilteredNoiseShapingReverb(nn.Module):
+class FilteredNoiseShapingReverb(StreamIO, nn.Module):
     """Band-wise exponentially decaying filtered noise (mirrors reference reverb.py:231-401).
 
     Init: uniform noise split into `num_bands` bands by a Linkwitz-Riley crossover (host side, scipy).
@@ -302,10 +310,8 @@ class FilteredNoiseShapingReverb(nn.Module):
         a fresh impulse response per call, and a chain of blocks is then not a stream.  ``(y, state)`` comes back when
         a state is asked for."""
         block = {} if state is None and not return_state else {"state": state, "return_state": True}
-        if block and self.noise_randomness != "fixed":
-            raise ValueError('FilteredNoiseShapingReverb: noise_randomness="pseudo-random" cuts a fresh impulse response '
-                             'per call, so a chain of blocks is not a stream; state / return_state need '
-                             'noise_randomness="fixed"')
+        if block:
+            self.stream_check()
         ir = normalize_impulse(self.compute_ir(log_decay, log_gain, log_fade_in, z_fade_in_gain))
         x = lr_to_ms(input_signals) if self.processor_channel == "midside" else input_signals
         y = self.conv(x, ir, **block)
@@ -313,6 +319,17 @@ class FilteredNoiseShapingReverb(nn.Module):
         if self.processor_channel == "midside":
             y = ms_to_lr(y)
         return (y, zf) if return_state else y
+
+    def stream_check(self):
+        if self.noise_randomness != "fixed":
+            raise ValueError('FilteredNoiseShapingReverb: noise_randomness="pseudo-random" cuts a fresh impulse response '
+                             'per call, so a chain of blocks is not a stream; state / return_state need '
+                             'noise_randomness="fixed"')
+
+    def stream_block(self, x4, out4, carry, **params):
+        y, carry = self.forward(x4.reshape(-1, *x4.shape[2:]), state=carry, return_state=True, **params)
+        write_rows(out4, y)
+        return carry
 
     def parameter_size(self):
         shape = (self.num_channels, self.num_bands)

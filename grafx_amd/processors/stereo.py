@@ -2,7 +2,7 @@
 import torch.nn as nn
 
 from .. import ops
-from .core._buffer_io import BufferIO
+from .core._buffer_io import BufferIO, StreamIO
 import torch
 
 from ..autograd import needs_grad
@@ -28,7 +28,7 @@ class StereoGain(BufferIO, nn.Module):
 INV_SQRT_2 = 1 / 2**0.5
 
 
-class SideGainImager(nn.Module):
+class SideGainImager(StreamIO, nn.Module):
     """Stereo width via side-channel gain (stereo.py:51-100); elementwise."""
 
     def forward(self, input_signals, log_gain):
@@ -41,7 +41,7 @@ class SideGainImager(nn.Module):
         return {"log_gain": 1}
 
 
-class MonoToStereo(nn.Module):
+class MonoToStereo(StreamIO, nn.Module):
     def forward(self, input_signals):
         assert input_signals.shape[1] == 1
         return input_signals.repeat(1, 2, 1)
@@ -50,7 +50,7 @@ class MonoToStereo(nn.Module):
         return {}
 
 
-class StereoToMidSide(nn.Module):
+class StereoToMidSide(StreamIO, nn.Module):
     def __init__(self, normalize=True):
         super().__init__()
         self.normalize = normalize
@@ -66,7 +66,7 @@ class StereoToMidSide(nn.Module):
         return {}
 
 
-class MidSideToStereo(nn.Module):
+class MidSideToStereo(StreamIO, nn.Module):
     def __init__(self, normalize=True):
         super().__init__()
         self.normalization_const = INV_SQRT_2 if normalize else 0.5

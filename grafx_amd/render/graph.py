@@ -283,8 +283,8 @@ class GenericRenderPathWarning(UserWarning):
     """A render of CUDA signals that does not take the in-place buffer path (see _buffer_io_reason)."""
 
 
-def _buffer_io_reason(processors, input_signals, render_data, per_type_parameters):
-    """None when the render can take the in-place buffer path (gradients are handled by _BufferRenderFn around it), else
+def _buffer_io_reason(processors, input_signals, render_data, per_type_parameters, method="render_into"):
+    """``method``: what every processor must offer (the streamed render asks for ``stream_block``).  None when the render can take the in-place buffer path (gradients are handled by _BufferRenderFn around it), else
     what keeps it off: the render then runs upstream's loop (render/graph.py:104-175 of the reference: copies on read,
     torch routing, one processor call per stage -- the processors themselves still run their HIP kernels)."""
     if not input_signals.is_cuda:
@@ -295,8 +295,8 @@ def _buffer_io_reason(processors, input_signals, render_data, per_type_parameter
         return "the graph holds multi-input / multi-output processors (render/prepare.py:109-192 of the reference)"
     for step in render_data.iter_list[1:]:
         if step.node_type in processors:
-            if not hasattr(processors[step.node_type], "render_into"):
-                return f"processor type {step.node_type!r} ({type(processors[step.node_type]).__name__}) has no render_into()"
+            if not hasattr(processors[step.node_type], method):
+                return f"processor type {step.node_type!r} ({type(processors[step.node_type]).__name__}) has no {method}()"
         elif step.node_type not in UTILITY_TYPES:
             return f"node type {step.node_type!r} has no processor"
         if step.dest_write.method != "slice" or len(step.source_reads) != 1 or step.source_reads[0].method == "none":
@@ -894,6 +894,160 @@ def _render_buffer_io_with_grad(processors, input_signals, per_type_parameters, 
     return out, [], buf
 
 
+# ---- streaming: the same in-place render, one block at a time ---------------------------------------------
+class RenderState:
+    """What a render of one block leaves for the render of the next (``render_grafx(..., state=, return_state=True)``).
+
+    Opaque to the caller.  It holds one carry per render STEP -- keyed by the step's index in ``render_data.iter_list``, in
+    whatever form that step's processor hands it back (``stream_block``) -- so a node type whose nodes are spread over
+    several steps keeps one carry per step and nothing is sliced or re-assembled between blocks.  It also records what it
+    was made for (batch size -- None for an unbatched 3-D render --, channels, device, every step's node type and row
+    count) and ``samples``, the number of samples rendered so far.  A render never changes the state it is given: it
+    returns a new one."""
+
+    __slots__ = ("batch", "channels", "device", "steps", "carries", "samples")
+
+    def __init__(self, batch, channels, device, steps, carries=None, samples=0):
+        self.batch, self.channels, self.device = batch, channels, torch.device(device)
+        self.steps = tuple((str(t), int(n)) for t, n in steps)
+        self.carries = dict(carries or {})
+        self.samples = int(samples)
+        if any(not 1 <= i <= len(self.steps) for i in self.carries):
+            raise ValueError(f"RenderState: a carry for a step outside 1..{len(self.steps)}")
+
+    @staticmethod
+    def steps_of(render_data):
+        """(node type, rows written) of every render step after the sources."""
+        steps = []
+        for step in render_data.iter_list[1 : render_data.max_order + 1]:
+            d0, d1 = step.dest_write.idx
+            steps.append((step.node_type, d1 - d0))
+        return tuple(steps)
+
+    def mismatch(self, batch, channels, device, steps):
+        """Why this state does not belong to a render of that shape (None: it does)."""
+        if self.batch != batch:
+            say = lambda b: "an unbatched render" if b is None else f"batch size {b}"   # noqa: E731
+            return f"the state was made for {say(self.batch)}, this render has {say(batch)}"
+        if self.channels != channels:
+            return f"the state was made for {self.channels} channels, this render has {channels}"
+        if self.device != torch.device(device):
+            return f"the state lives on device {self.device}, this render runs on {torch.device(device)}"
+        steps = tuple((str(t), int(n)) for t, n in steps)
+        if len(self.steps) != len(steps):
+            return f"the state was made for a render of {len(self.steps)} steps, this render_data has {len(steps)}"
+        for i, (mine, theirs) in enumerate(zip(self.steps, steps), 1):
+            if mine != theirs:
+                return (f"render step {i} of the state is {mine[1]} rows of node type {mine[0]!r}, this render_data has "
+                        f"{theirs[1]} rows of {theirs[0]!r} there")
+        return None
+
+    def advanced(self, carries, samples):
+        """The state after one more block of ``samples`` samples that left ``carries``."""
+        return RenderState(self.batch, self.channels, self.device, self.steps, carries, self.samples + samples)
+
+    def __repr__(self):
+        return (f"RenderState(batch={self.batch}, channels={self.channels}, device={str(self.device)!r}, "
+                f"steps={len(self.steps)}, samples={self.samples})")
+
+
+def _render_stream(processors, input_signals, per_type_parameters, render_data, common_parameters, state,
+                   keep_signal_buffer):
+    """One block of a streamed render: the in-place buffer render with every stage called through ``stream_block``.
+    No mix fusion, no tee and no side streams (none of them takes a carry): a routing sum is its own gather-sum, every
+    stage designs its filters right before it runs."""
+    from .. import ops
+
+    if input_signals.ndim not in (3, 4):
+        raise Exception(f"input_signal has shape of {input_signals.shape} ({input_signals.ndim} ndims), which is not 3 or 4 dims.")
+    reason = _buffer_io_reason(processors, input_signals, render_data, per_type_parameters, method="stream_block")
+    if reason is not None:
+        raise ValueError(f"render_grafx: a render with a state runs on the in-place buffer path, which this one cannot take "
+                         f"because {reason}")
+    if _wants_grad(input_signals, per_type_parameters, common_parameters):
+        raise NotImplementedError("render_grafx: a render with a state does not carry gradients (a parameter or the input "
+                                  "requires grad); back-propagation through a streamed graph is not implemented -- render "
+                                  "under torch.no_grad(), or without state / return_state")
+    squeeze = input_signals.ndim == 3
+    x = input_signals.unsqueeze(0) if squeeze else input_signals
+    B, n_src, C, L = x.shape
+    dev = x.device
+    steps = RenderState.steps_of(render_data)
+    if state is None:
+        state = RenderState(None if squeeze else B, C, dev, steps)
+    elif not isinstance(state, RenderState):
+        raise ValueError(f"render_grafx: state must be a RenderState from an earlier block, got {type(state).__name__}")
+    else:
+        why = state.mismatch(None if squeeze else B, C, dev, steps)
+        if why is not None:
+            raise ValueError(f"render_grafx: {why}")
+    # every stage is asked before the first launch: a refusal leaves no half-written buffer and no half-advanced state
+    for i in range(1, render_data.max_order + 1):
+        node_type = render_data.iter_list[i].node_type
+        if node_type in processors:
+            try:
+                processors[node_type].stream_check()
+            except ValueError as err:
+                raise ValueError(f"render_grafx: node type {node_type!r} cannot be rendered in blocks: {err}") from None
+
+    shared_tree = per_type_parameters if (not squeeze and common_parameters is None) else None
+    expanded_tree = None
+    if not squeeze and common_parameters is not None:
+        common_parameters = expand_tensor_or_tensor_dict(common_parameters, expand=B, dim=0)
+    node_dim = 0 if squeeze else 1
+    postprocess = None if squeeze else flatten_batch_and_node
+
+    buf = torch.empty(B, render_data.num_nodes, C, L, device=dev)
+    sources_in_buf = keep_signal_buffer     # an output-only render copies the sources only when a stage reads them there
+    if sources_in_buf:
+        buf[:, :n_src].copy_(x)
+    carries = {}
+    out_view = None
+    for i in range(1, render_data.max_order + 1):
+        step = render_data.iter_list[i]
+        d0, d1 = step.dest_write.idx
+        out_view = buf.narrow(1, d0, d1 - d0)
+        plan = _gather_plan(step, dev)
+        read = step.source_reads[0]
+        from_inputs = plan is None and read.idx[1] <= n_src
+        if not from_inputs and not sources_in_buf and _touches_inputs(read, n_src):
+            buf[:, :n_src].copy_(x)
+            sources_in_buf = True
+        if plan is None:
+            a, b = read.idx
+            x_view = (x if from_inputs else buf).narrow(1, a, b - a)
+        node_type = step.node_type
+        if node_type not in processors:  # in / out / mix: the (summed) input is the output
+            if plan is None:
+                out_view.copy_(x_view)
+            else:
+                _gather(ops, buf, plan, out_view)
+            continue
+        if plan is not None:
+            x_view = _gather(ops, buf, plan, torch.empty(B, plan[2], C, L, device=dev))
+        proc = processors[node_type]
+        extra = {}
+        if squeeze:
+            params = read_tensor_or_tensor_dict(per_type_parameters[node_type], step.parameter_read, dim=0)
+        elif shared_tree is not None and getattr(proc, "accepts_shared_params", False):
+            params = read_tensor_or_tensor_dict(shared_tree[node_type], step.parameter_read, dim=0)
+            extra["_shared_rows"] = d1 - d0
+        else:
+            if expanded_tree is None:
+                expanded_tree = expand_tensor_or_tensor_dict(per_type_parameters, expand=B, dim=0)
+            params = read_tensor_or_tensor_dict(expanded_tree[node_type], step.parameter_read, dim=1,
+                                                postprocess=flatten_batch_and_node)
+        common_i = {}
+        if common_parameters is not None:
+            common_i = read_tensor_or_tensor_dict(common_parameters, step.dest_write, dim=node_dim, postprocess=postprocess)
+        carries[i] = proc.stream_block(x_view, out_view, state.carries.get(i), **extra, **params, **common_i)
+    new_state = state.advanced(carries, L)
+    out = out_view[0] if squeeze else out_view
+    if not keep_signal_buffer:
+        return out, [], None, new_state
+    return out, [], (buf[0] if squeeze else buf), new_state
+
+
 def render_grafx(
     processors,
     input_signals,
@@ -903,10 +1057,25 @@ def render_grafx(
     parameters_grad=True,
     input_signal_grad=False,
     keep_signal_buffer=True,
+    state=None,
+    return_state=False,
 ):
     """``keep_signal_buffer=False`` (an extension; upstream always returns the buffer): an output-only render on the HIP
     path without gradients -- the third return value is None and rows that nothing reads are not written (the sources'
-    copy, the rows of a stage that only feed the routing sum fused into its kernel).  The output is the same bits."""
+    copy, the rows of a stage that only feed the routing sum fused into its kernel).  The output is the same bits.
+
+    ``state`` / ``return_state`` (an extension): rendering a long signal block by block.  ``state`` is the
+    :class:`RenderState` the block before returned (None: the first block, every processor starts from silence); with
+    ``return_state`` the result is ``(output, intermediates, signal_buffer, state)``.  The blocks' outputs, concatenated,
+    are the one-call render with every FIR convolution taken as the linear convolution (set_exact_convolution(True): the
+    reference's odd-length aliasing has no block form).  Runs on the in-place buffer path only and without gradients; a
+    processor that cannot stream (the "iir" smoother of the dynamics processors) is refused, by node type and with its
+    own reason, before anything is launched.  Every block pays a full N-tap convolution per FIR node, so blocks much
+    shorter than the longest filter are expensive.  With both arguments left alone nothing changes."""
+    if state is not None or return_state:
+        result = _render_stream(processors, input_signals, per_type_parameters, render_data, common_parameters, state,
+                                keep_signal_buffer)
+        return result if return_state else result[:3]
     method = render_data.method
     ndim = input_signals.ndim
     if ndim in (3, 4) and _buffer_io_ok(processors, input_signals, render_data, per_type_parameters):
