@@ -25,6 +25,12 @@ class _Container(StreamIO):
         for proc in self._children():
             child_stream(proc, self).stream_check()
 
+    def stream_silence(self, carry):
+        """Child by child: every wrapped processor says what its own silence is."""
+        if carry is None:
+            return None
+        return tuple(child_stream(proc, self).stream_silence(c) for proc, c in zip(self._children(), carry))
+
 
 class DryWet(_Container, nn.Module):
     """y = w * processor(x) + (1 - w) * x (container.py:10-82)."""

@@ -14,7 +14,11 @@ under the signal kernels of the earlier stages, and hands the result back as ``r
 the block's output into ``out4`` like ``render_into`` and returns what the next block's call needs in ``carry`` -- whatever
 the processor's own keywords call it (``state=``, ``history=``), None for a memoryless processor and for the first block.
 ``stream_check()`` raises the processor's own ValueError when its configuration cannot be rendered in blocks; the render
-asks every stage before it launches the first."""
+asks every stage before it launches the first.
+``stream_silence(carry) -> carry`` takes a carry this processor returned and gives back, in new tensors of the same
+shapes, the carry that means "nothing came before": what a first block's None stands for, materialised, so that a stream
+can start on the kernels every later block runs (render.silent_state, render.CapturedStream)."""
+import torch
 
 
 class Prepared:
@@ -31,6 +35,24 @@ def write_rows(out4, y):
     if y.data_ptr() != out4.data_ptr():
         out4.copy_(y.reshape(out4.shape))
     return out4
+
+
+def map_carry(fn, carry):
+    """``fn`` on every tensor leaf of a carry (None, a tensor, or a tuple / list of carries) -> a carry of the same form."""
+    if carry is None:
+        return None
+    if isinstance(carry, torch.Tensor):
+        return fn(carry)
+    return type(carry)(map_carry(fn, c) for c in carry)
+
+
+def carry_leaves(carry):
+    """The tensor leaves of a carry, in order."""
+    if carry is None:
+        return []
+    if isinstance(carry, torch.Tensor):
+        return [carry]
+    return [leaf for c in carry for leaf in carry_leaves(c)]
 
 
 def child_stream(proc, owner):
@@ -56,6 +78,10 @@ class StreamIO:
                 params = {k: expand_shared(v, shared_reps(x4, _shared_rows)) for k, v in params.items()}
             write_rows(out4, self.forward(x4.reshape(-1, *x4.shape[2:]), **params))
         return None
+
+    def stream_silence(self, carry):
+        """Histories and filter states start from zero (a processor whose None means something else overrides this)."""
+        return map_carry(torch.zeros_like, carry)
 
 
 class BufferIO(StreamIO):

@@ -86,3 +86,8 @@ class Ballistics(nn.Module):
         else:
             y, zf = ops.ballistics(input_signals, z_alpha, zi=None if state is None else state.contiguous(), return_state=True)
         return (y, zf) if return_state else y
+
+    def stream_silence(self, carry):
+        """The state a None stands for, in a new tensor shaped like ``carry`` (a state this module returned): the
+        reference's zi = 1."""
+        return None if carry is None else torch.ones_like(carry)

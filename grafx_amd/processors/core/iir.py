@@ -134,7 +134,7 @@ class IIRFilter(nn.Module):
         if not return_state:
             return y
         if first_order:     # a first-order section has one state value: w[n-2] is read by nothing (a2 = b2 = 0)
-            zf = zf * zf.new_tensor([1.0, 0.0])
+            zf = zf * torch.arange(1, -1, -1, dtype=zf.dtype, device=zf.device)   # (1, 0), made on the device
         return y, (zf.view(*lead, *zf.shape[1:]) if lead is not None else zf)
 
     def _stateful_differentiable(self, x, Bs, As, state):

@@ -5,7 +5,7 @@ import torch.nn as nn
 from .. import autograd as diff
 from .. import ops
 from ..autograd import needs_grad
-from .core._buffer_io import BufferIO, StreamIO, expand_shared, shared_reps
+from .core._buffer_io import BufferIO, StreamIO, expand_shared, map_carry, shared_reps
 from .core.convolution import reference_aliases, resolve_flashfftconv
 from .core.envelope import Ballistics, TruncatedOnePoleIIRFilter, no_carried_state
 
@@ -57,6 +57,10 @@ class _Dynamics(BufferIO, nn.Module):
             self.render_into(x4, out4, _shared_rows=_shared_rows, **params)
             return None
         return self.forward(x4, _out=out4, _shared_rows=_shared_rows, state=carry, return_state=True, **params)[1]
+
+    def stream_silence(self, carry):
+        """Every "ballistics" smoother starts from 1 (_forward_blocks: what a None state stands for)."""
+        return map_carry(torch.ones_like, carry)
 
     def forward(self, input_signals, log_threshold, log_ratio, log_knee=None, z_alpha_pre=None, z_alpha_post=None,
                 _out=None, _shared_rows=None, _aux=None, _mix=None, state=None, return_state=False):
@@ -366,3 +370,7 @@ class IIREnvelopeFollower(BaseEnvelopeFollower):
 class BallisticsEnvelopeFollower(BaseEnvelopeFollower):
     def __init__(self, detect_with="energy"):
         super().__init__(Ballistics(), detect_with=detect_with)
+
+    def stream_silence(self, carry):
+        """The state of forward(state=) that a None stands for: the smoother's (Ballistics.stream_silence)."""
+        return self.smoother.stream_silence(carry)

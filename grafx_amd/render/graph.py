@@ -951,13 +951,9 @@ class RenderState:
                 f"steps={len(self.steps)}, samples={self.samples})")
 
 
-def _render_stream(processors, input_signals, per_type_parameters, render_data, common_parameters, state,
-                   keep_signal_buffer):
-    """One block of a streamed render: the in-place buffer render with every stage called through ``stream_block``.
-    No mix fusion, no tee and no side streams (none of them takes a carry): a routing sum is its own gather-sum, every
-    stage designs its filters right before it runs."""
-    from .. import ops
-
+def _stream_admit(processors, input_signals, per_type_parameters, render_data, common_parameters, state):
+    """Everything a streamed render refuses, asked before the first launch (so a refusal leaves no half-written buffer and
+    no half-advanced state) -> the state to render from (a fresh one for None)."""
     if input_signals.ndim not in (3, 4):
         raise Exception(f"input_signal has shape of {input_signals.shape} ({input_signals.ndim} ndims), which is not 3 or 4 dims.")
     reason = _buffer_io_reason(processors, input_signals, render_data, per_type_parameters, method="stream_block")
@@ -969,19 +965,16 @@ def _render_stream(processors, input_signals, per_type_parameters, render_data, 
                                   "requires grad); back-propagation through a streamed graph is not implemented -- render "
                                   "under torch.no_grad(), or without state / return_state")
     squeeze = input_signals.ndim == 3
-    x = input_signals.unsqueeze(0) if squeeze else input_signals
-    B, n_src, C, L = x.shape
-    dev = x.device
+    B, C = (None if squeeze else input_signals.shape[0]), input_signals.shape[-2]
     steps = RenderState.steps_of(render_data)
     if state is None:
-        state = RenderState(None if squeeze else B, C, dev, steps)
+        state = RenderState(B, C, input_signals.device, steps)
     elif not isinstance(state, RenderState):
         raise ValueError(f"render_grafx: state must be a RenderState from an earlier block, got {type(state).__name__}")
     else:
-        why = state.mismatch(None if squeeze else B, C, dev, steps)
+        why = state.mismatch(B, C, input_signals.device, steps)
         if why is not None:
             raise ValueError(f"render_grafx: {why}")
-    # every stage is asked before the first launch: a refusal leaves no half-written buffer and no half-advanced state
     for i in range(1, render_data.max_order + 1):
         node_type = render_data.iter_list[i].node_type
         if node_type in processors:
@@ -989,13 +982,73 @@ def _render_stream(processors, input_signals, per_type_parameters, render_data, 
                 processors[node_type].stream_check()
             except ValueError as err:
                 raise ValueError(f"render_grafx: node type {node_type!r} cannot be rendered in blocks: {err}") from None
+    return state
 
+
+def _stream_stage_parameters(processors, input_signals, per_type_parameters, render_data, common_parameters):
+    """-> ``stage(i)`` = (extra keywords, parameters, common parameters) of render step i of a streamed render: the rows
+    ``stream_block`` (and ``prepare``) of the step's processor take."""
+    squeeze = input_signals.ndim == 3
+    B = 1 if squeeze else input_signals.shape[0]
     shared_tree = per_type_parameters if (not squeeze and common_parameters is None) else None
     expanded_tree = None
     if not squeeze and common_parameters is not None:
         common_parameters = expand_tensor_or_tensor_dict(common_parameters, expand=B, dim=0)
     node_dim = 0 if squeeze else 1
     postprocess = None if squeeze else flatten_batch_and_node
+
+    def stage(i):
+        nonlocal expanded_tree
+        step = render_data.iter_list[i]
+        node_type = step.node_type
+        extra = {}
+        if squeeze:
+            params = read_tensor_or_tensor_dict(per_type_parameters[node_type], step.parameter_read, dim=0)
+        elif shared_tree is not None and getattr(processors[node_type], "accepts_shared_params", False):
+            params = read_tensor_or_tensor_dict(shared_tree[node_type], step.parameter_read, dim=0)
+            extra["_shared_rows"] = step.dest_write.idx[1] - step.dest_write.idx[0]
+        else:
+            if expanded_tree is None:
+                expanded_tree = expand_tensor_or_tensor_dict(per_type_parameters, expand=B, dim=0)
+            params = read_tensor_or_tensor_dict(expanded_tree[node_type], step.parameter_read, dim=1,
+                                                postprocess=flatten_batch_and_node)
+        common_i = {}
+        if common_parameters is not None:
+            common_i = read_tensor_or_tensor_dict(common_parameters, step.dest_write, dim=node_dim, postprocess=postprocess)
+        return extra, params, common_i
+
+    return stage
+
+
+def _design_stream(processors, input_signals, per_type_parameters, render_data, common_parameters):
+    """The parameter-only work of a streamed render, apart from its blocks: {step: Prepared} for every step whose processor
+    offers ``prepare()`` and returns a Prepared for these parameters -- what ``_render_stream(prepared=)`` takes."""
+    stage = _stream_stage_parameters(processors, input_signals, per_type_parameters, render_data, common_parameters)
+    prepared = {}
+    for i in range(1, render_data.max_order + 1):
+        proc = processors[render_data.iter_list[i].node_type] if render_data.iter_list[i].node_type in processors else None
+        if hasattr(proc, "prepare"):
+            extra, params, common_i = stage(i)
+            design = proc.prepare(**extra, **params, **common_i)
+            if design is not None:
+                prepared[i] = design
+    return prepared
+
+
+def _render_stream(processors, input_signals, per_type_parameters, render_data, common_parameters, state,
+                   keep_signal_buffer, prepared=None):
+    """One block of a streamed render: the in-place buffer render with every stage called through ``stream_block``.
+    No mix fusion, no tee and no side streams (none of them takes a carry): a routing sum is its own gather-sum, every
+    stage designs its filters right before it runs -- except the steps of ``prepared`` ({step: Prepared}, _design_stream),
+    which take their design from there."""
+    from .. import ops
+
+    state = _stream_admit(processors, input_signals, per_type_parameters, render_data, common_parameters, state)
+    squeeze = input_signals.ndim == 3
+    x = input_signals.unsqueeze(0) if squeeze else input_signals
+    B, n_src, C, L = x.shape
+    dev = x.device
+    stage = _stream_stage_parameters(processors, input_signals, per_type_parameters, render_data, common_parameters)
 
     buf = torch.empty(B, render_data.num_nodes, C, L, device=dev)
     sources_in_buf = keep_signal_buffer     # an output-only render copies the sources only when a stage reads them there
@@ -1025,27 +1078,33 @@ def _render_stream(processors, input_signals, per_type_parameters, render_data, 
             continue
         if plan is not None:
             x_view = _gather(ops, buf, plan, torch.empty(B, plan[2], C, L, device=dev))
-        proc = processors[node_type]
-        extra = {}
-        if squeeze:
-            params = read_tensor_or_tensor_dict(per_type_parameters[node_type], step.parameter_read, dim=0)
-        elif shared_tree is not None and getattr(proc, "accepts_shared_params", False):
-            params = read_tensor_or_tensor_dict(shared_tree[node_type], step.parameter_read, dim=0)
-            extra["_shared_rows"] = d1 - d0
-        else:
-            if expanded_tree is None:
-                expanded_tree = expand_tensor_or_tensor_dict(per_type_parameters, expand=B, dim=0)
-            params = read_tensor_or_tensor_dict(expanded_tree[node_type], step.parameter_read, dim=1,
-                                                postprocess=flatten_batch_and_node)
-        common_i = {}
-        if common_parameters is not None:
-            common_i = read_tensor_or_tensor_dict(common_parameters, step.dest_write, dim=node_dim, postprocess=postprocess)
-        carries[i] = proc.stream_block(x_view, out_view, state.carries.get(i), **extra, **params, **common_i)
+        extra, params, common_i = stage(i)
+        if prepared is not None and i in prepared:
+            extra["_prepared"] = prepared[i]
+        carries[i] = processors[node_type].stream_block(x_view, out_view, state.carries.get(i), **extra, **params, **common_i)
     new_state = state.advanced(carries, L)
     out = out_view[0] if squeeze else out_view
     if not keep_signal_buffer:
         return out, [], None, new_state
     return out, [], (buf[0] if squeeze else buf), new_state
+
+
+def silent_state(processors, input_signals, per_type_parameters, render_data, common_parameters=None):
+    """The :class:`RenderState` that means "nothing came before", materialised: every carry a render of blocks shaped like
+    ``input_signals`` hands on, filled with what its processor calls silence (``stream_silence``: zero histories and filter
+    states, envelopes at 1).  A render from it computes what a render from ``state=None`` computes, on the kernels every
+    later block runs (a None carry takes the stateless ones) -- which is what lets one fixed kernel list serve the whole
+    stream (CapturedStream).  Learns the carries' shapes from one eager block rendered from ``state=None``, and so makes
+    the refusals of ``render_grafx(state=)``; ``.samples`` is 0."""
+    state = _render_stream(processors, input_signals, per_type_parameters, render_data, common_parameters, None, False)[3]
+    carries = {}
+    for i, carry in state.carries.items():
+        proc = processors[render_data.iter_list[i].node_type]
+        if not hasattr(proc, "stream_silence"):
+            raise ValueError(f"silent_state: processor type {render_data.iter_list[i].node_type!r} ({type(proc).__name__}) "
+                             "has no stream_silence()")
+        carries[i] = proc.stream_silence(carry)
+    return RenderState(state.batch, state.channels, state.device, state.steps, carries, 0)
 
 
 def render_grafx(
