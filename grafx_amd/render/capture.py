@@ -22,7 +22,8 @@ see :class:`CapturedStream`.
 import torch
 
 from ..processors.core._buffer_io import carry_leaves, map_carry
-from .graph import RenderState, _design_stream, _render_stream, _stream_admit, render_grafx, silent_state
+from .graph import render_grafx
+from .stream import RenderState, _design_stream, _render_stream, _stream_admit, silent_state
 
 
 def _clone_tree(tree):

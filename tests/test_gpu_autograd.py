@@ -463,7 +463,7 @@ def test_block_form_routing_adjoint_on_other_console_shapes(n_ch, n_bus):
     strip per bus (no two strips share their destinations: nothing to share, the expanded path) -- block form on and off give
     the same bits."""
     import bench
-    from grafx_amd.render import graph as render_graph
+    from grafx_amd.render import backward as render_graph
     from grafx_amd.utils import create_empty_parameters
 
     dev = torch.device("cuda")
@@ -500,7 +500,7 @@ def test_block_form_routing_adjoint_gives_the_bits_of_the_expanded_one(smoother)
     one native node (the ballistics smoother) cannot read that form: the rows are written out for it, same bits again."""
     import bench
     from grafx_amd.processors import Compressor
-    from grafx_amd.render import graph as render_graph
+    from grafx_amd.render import backward as render_graph
     from grafx_amd.utils import create_empty_parameters
 
     dev = torch.device("cuda")

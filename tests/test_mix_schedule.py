@@ -51,7 +51,7 @@ def test_block_structure_of_a_routing_sums_adjoint():
 
     import torch
 
-    from grafx_amd.render.graph import _block_fan
+    from grafx_amd.render.plans import _block_fan
 
     dev = torch.device("cpu")
 

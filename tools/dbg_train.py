@@ -7,7 +7,6 @@ import torch.nn as nn
 import bench
 from grafx_amd.data import convert_to_tensor
 from grafx_amd.render import prepare_render, render_grafx, reorder_for_fast_render
-from grafx_amd.render import graph as rg
 from grafx_amd.utils import create_empty_parameters
 
 dev = torch.device("cuda")

@@ -1,5 +1,5 @@
 """ops.dynamics_bwd at the console's channel-strip shape with the output gradient (a) one row per strip, (b) in block
-form -- eight strips read one row through a zero stride (render/graph.py: _block_fan):
+form -- eight strips read one row through a zero stride (render/plans.py: _block_fan):
     GRAFX_DYN_BWD_SHARE=0|1 python tools/dyn_bwd_share_bench.py"""
 import os
 import sys

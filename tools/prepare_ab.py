@@ -9,7 +9,7 @@ import torch
 sys.path.insert(0, ".")
 import bench
 from grafx_amd import ops
-from grafx_amd.render import graph as rg
+from grafx_amd.render import forward as rg
 
 dev = torch.device("cuda")
 step = bench.console_case(torch, dev, 256, 131072, bench.LENS)
