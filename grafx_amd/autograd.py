@@ -606,6 +606,44 @@ class DynamicsFn(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+class WaveshaperFn(torch.autograd.Function):
+    """The memoryless distortions (nonlinear.py:46-79, 120-175, 210-233, 270-307) as one autograd node: forward is the
+    streaming inference kernel, backward ONE streaming pass over x and dL/dy (gfx_waveshaper_bwd_f32) that leaves the input
+    gradient and every parameter's row sums -- instead of K full-size basis terms (polynomial shapers) or a dozen full-size
+    elementwise tensors (tanh shapers) on autograd's tape.  Saved: x, the parameters and the R * C means of remove_dc."""
+
+    @staticmethod
+    def forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc):
+        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+            x = x.contiguous()
+        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
+            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+            dc = ops.row_mean(x) if remove_dc else None
+        else:
+            y, dc = ops.waveshaper(x, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
+                                   inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, return_dc=True)
+        ctx.save_for_backward(x, log_pre_gain, log_post_gain, p0, p1, dc)
+        ctx.cfg = (mode, use_tanh, inverse_post_gain, remove_dc)
+        return y.view(x.shape) if four else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, log_pre_gain, log_post_gain, p0, p1, dc = ctx.saved_tensors
+        mode, use_tanh, inverse_post_gain, remove_dc = ctx.cfg
+        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+            gy = gy.contiguous()
+        want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
+        gx, grads = ops.waveshaper_bwd(x, gy, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
+                                       inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, dc=dc,
+                                       out=_sink_for(x) if "x" in want else None, want=want)
+        like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
+        return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain),
+                like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None)
+
+
 def truncated_one_pole(u, z_alpha, iir_len, exact=False):
     """core/envelope.py:34-49."""
     from .processors.core.convolution import reference_aliases

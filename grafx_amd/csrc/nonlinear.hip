@@ -72,6 +72,37 @@ __device__ __forceinline__ float shape(float x, const WsRow& q, int K, bool use_
     return y * q.post;
 }
 
+// the row's constants, as both the forward and the backward kernel use them (polynomial weights: tanh'ed, into LDS)
+template <int MODE>
+__device__ __forceinline__ void ws_row_setup(WsRow& q, float* sw, int64_t r, int K, int inverse_post,
+                                             const float* __restrict__ log_pre, const float* __restrict__ log_post,
+                                             const float* __restrict__ p0, const float* __restrict__ p1) {
+    q.w = sw;
+    q.pre = log_pre ? expf(log_pre[r]) : 1.0f;
+    q.post = inverse_post ? 1.0f / q.pre : (log_post ? expf(log_post[r]) : 1.0f);
+    q.b = q.tb = 0.0f;
+    if (MODE == GFX_WS_TANH && p0) {
+        q.b = p0[r];
+        q.tb = tanhf(q.b);
+    }
+    if (MODE == GFX_WS_PIECEWISE) {
+        // nonlinear.py:163-166: threshold splits as (kn, kp), hardness as (gp, gn)
+        q.gp = expf(p0[2 * r]);
+        q.gn = expf(p0[2 * r + 1]);
+        q.kn = 1.0f / (1.0f + expf(-p1[2 * r]));
+        q.kp = 1.0f / (1.0f + expf(-p1[2 * r + 1]));
+        q.bp = tanhf(q.kp);
+        q.bn = -tanhf(q.kn);
+        q.ap = (1.0f - q.bp) / q.gp;
+        q.an = (1.0f + q.bn) / q.gn;
+    }
+    if (MODE == GFX_WS_POWER || MODE == GFX_WS_CHEBYSHEV) {
+        __syncthreads();  // previous row's readers are done
+        if ((int)threadIdx.x < K) sw[threadIdx.x] = tanhf(p0[r * K + threadIdx.x]);
+        __syncthreads();
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void waveshaper_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                          const float* __restrict__ log_pre,
@@ -81,30 +112,7 @@ __global__ __launch_bounds__(256) void waveshaper_kernel(const float* __restrict
     __shared__ float sw[WS_MAX_K];
     for (int64_t r = blockIdx.y; r < a.R; r += gridDim.y) {
         WsRow q;
-        q.w = sw;
-        q.pre = log_pre ? expf(log_pre[r]) : 1.0f;
-        q.post = a.inverse_post ? 1.0f / q.pre : (log_post ? expf(log_post[r]) : 1.0f);
-        q.b = q.tb = 0.0f;
-        if (MODE == GFX_WS_TANH && p0) {
-            q.b = p0[r];
-            q.tb = tanhf(q.b);
-        }
-        if (MODE == GFX_WS_PIECEWISE) {
-            // nonlinear.py:163-166: threshold splits as (kn, kp), hardness as (gp, gn)
-            q.gp = expf(p0[2 * r]);
-            q.gn = expf(p0[2 * r + 1]);
-            q.kn = 1.0f / (1.0f + expf(-p1[2 * r]));
-            q.kp = 1.0f / (1.0f + expf(-p1[2 * r + 1]));
-            q.bp = tanhf(q.kp);
-            q.bn = -tanhf(q.kn);
-            q.ap = (1.0f - q.bp) / q.gp;
-            q.an = (1.0f + q.bn) / q.gn;
-        }
-        if (MODE == GFX_WS_POWER || MODE == GFX_WS_CHEBYSHEV) {
-            __syncthreads();  // previous row's readers are done
-            if ((int)threadIdx.x < a.K) sw[threadIdx.x] = tanhf(p0[r * a.K + threadIdx.x]);
-            __syncthreads();
-        }
+        ws_row_setup<MODE>(q, sw, r, a.K, a.inverse_post, log_pre, log_post, p0, p1);
         for (int c = 0; c < a.C; ++c) {
             q.dc = dc ? dc[r * a.C + c] : 0.0f;
             const float* xr = x + nrow_off(a.xmap, r, c);
@@ -198,6 +206,444 @@ int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t
             break;
     }
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+}
+
+}  // extern "C"
+
+// ---- waveshaper backward ---------------------------------------------------------------------------------------------
+// One streaming pass over x and gy (12 B per channel-sample with gx, 8 B without), the K polynomial terms in registers as in
+// the forward.  With u = (x - dc) pre, G = gy post, y = post s(u):
+//   gx          = G s'(u) pre                     (remove_dc: minus its mean over time per row-channel, ws_sub_mean_kernel)
+//   g_log_pre   = sum G (s'(u) u - [inverse_post] s(u))            (the difference per sample: summing both parts and
+//   g_log_post  = sum G s(u)                                        subtracting the sums cancels to ~1e-2 of them)
+//   g_bias      = sum G (sech^2(u + b) - sech^2(b))
+//   g_w[k]      = (1 - tanh^2 w_k) sum G f(B_k(u)),   s' = sum_k tanh(w_k) f'(B_k) B_k',   B_k' = k u^(k-1) or k U_(k-1)(u)
+//   piecewise   : d/d log_hardness, d/d z_threshold of the two outer branches, see bwd_samples.
+// Row sums: every workgroup reduces its share (registers -> wave shuffles -> LDS) and STORES one partial per sum into the
+// workspace; ws_bwd_finish_kernel adds a row's partials in double, in a fixed order -- no float atomics, bit-identical runs.
+namespace gfx {
+
+struct WsBwdArgs {
+    gfx_rowmap_t xmap, gmap, omap;
+    int64_t R, L;
+    int C, K, NS;                   // NS: sums per row in the workspace (ws_nsums)
+    int use_tanh, inverse_post, want_par;
+};
+
+// slots of a row's sums: 0 = d/d log_pre, 1 = d/d log_post, 2.. = the mode's own
+template <int MODE>
+struct WsAcc {
+    static constexpr int N = MODE == GFX_WS_TANH ? 3 : MODE == GFX_WS_PIECEWISE ? 6 : 2 + WS_MAX_K;
+};
+
+static inline int ws_nsums(int64_t K) { return K > 0 ? 2 + (int)K : 6; }
+static inline int64_t ws_blocks(int64_t L) {
+    const int64_t bx = (L / 4 + 255) / 256;
+    return bx > 64 ? 64 : (bx < 1 ? 1 : bx);
+}
+
+// NV samples of one row-channel: their input gradient into go[], their terms onto the thread's sums acc[] (every index a
+// compile-time constant after unrolling: a run-time-indexed accumulator array would live in scratch memory)
+template <int MODE, int NV>
+__device__ __forceinline__ void bwd_samples(const float (&xs)[NV], const float (&gs)[NV], float (&go)[NV], const WsRow& q,
+                                            int K, bool use_tanh, float inv, bool par, float (&acc)[WsAcc<MODE>::N]) {
+    if (MODE == GFX_WS_TANH) {
+        const float db = 1.0f - q.tb * q.tb;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const float u = (xs[j] - q.dc) * q.pre, G = gs[j] * q.post;
+            const float th = tanhf(u + q.b), d = 1.0f - th * th, s = th - q.tb;
+            go[j] = G * d * q.pre;
+            if (par) {
+                acc[0] += G * (d * u - inv * s);
+                acc[1] += G * s;
+                acc[2] += G * (d - db);
+            }
+        }
+    } else if (MODE == GFX_WS_PIECEWISE) {
+        // hi: y = ap tanh(gp (u - kp)) + bp,  ap = (1 - tanh kp) / gp   -> d/d log gp = ap (a d - t),  a = gp (u - kp)
+        //     d/d kp = sech^2(kp) (1 - t / gp) - (1 - bp) d;   lo mirrors it with kn, gn;   (acc[2..5] are scaled by
+        //     ap, an, kn (1 - kn), kp (1 - kp) when the partials are written)
+        const float skp = 1.0f - q.bp * q.bp, skn = 1.0f - q.bn * q.bn, rgp = 1.0f / q.gp, rgn = 1.0f / q.gn;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const float u = (xs[j] - q.dc) * q.pre, G = gs[j] * q.post;
+            float s, sp;
+            if (u > q.kp) {
+                const float a = q.gp * (u - q.kp), t = tanhf(a), d = 1.0f - t * t;
+                s = q.ap * t + q.bp;
+                sp = (1.0f - q.bp) * d;
+                if (par) {
+                    acc[2] += G * (a * d - t);
+                    acc[5] += G * (skp * (1.0f - t * rgp) - sp);
+                }
+            } else if (u < -q.kn) {
+                const float a = q.gn * (u + q.kn), t = tanhf(a), d = 1.0f - t * t;
+                s = q.an * t + q.bn;
+                sp = (1.0f + q.bn) * d;
+                if (par) {
+                    acc[3] += G * (a * d - t);
+                    acc[4] += G * (sp - skn * (1.0f + t * rgn));
+                }
+            } else {
+                s = tanhf(u);
+                sp = 1.0f - s * s;
+            }
+            go[j] = G * sp * q.pre;
+            if (par) {
+                acc[0] += G * (sp * u - inv * s);
+                acc[1] += G * s;
+            }
+        }
+    } else {
+        // k outermost, unrolled to the bound: the recurrences' state and the sums stay in registers.  Chebyshev: T_k and
+        // U_(k-1) by the same three-term recurrence (T_k' = k U_(k-1)), started one step early so that k = 1 needs no case.
+        float u[NV], G[NV], sp[NV], t0[NV], t1[NV], v0[NV], v1[NV];
+        float a0 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            u[j] = (xs[j] - q.dc) * q.pre;
+            G[j] = gs[j] * q.post;
+            sp[j] = 0.0f;
+            t0[j] = u[j]; t1[j] = 1.0f;      // T_(-1) = T_1 = u, T_0 = 1   (power: t1 = u^(k-1))
+            v0[j] = -1.0f; v1[j] = 0.0f;     // U_(-2) = -1, U_(-1) = 0
+            a0 += G[j];
+        }
+        if (par) acc[2] += a0;               // (times f(1) when the partials are written)
+#pragma unroll
+        for (int k = 1; k < WS_MAX_K; ++k) {
+            if (k < K) {
+                const float wk = q.w[k];
+                float a = 0.0f;
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    float B, Bp;
+                    if (MODE == GFX_WS_POWER) {
+                        Bp = (float)k * t1[j];
+                        B = t1[j] * u[j];
+                        t1[j] = B;
+                    } else {
+                        B = 2.0f * u[j] * t1[j] - t0[j];
+                        const float U = 2.0f * u[j] * v1[j] - v0[j];
+                        t0[j] = t1[j]; t1[j] = B;
+                        v0[j] = v1[j]; v1[j] = U;
+                        Bp = (float)k * U;
+                    }
+                    float f = B, df = 1.0f;
+                    if (use_tanh) {
+                        f = tanhf(B);
+                        df = 1.0f - f * f;
+                    }
+                    sp[j] += wk * df * Bp;
+                    a += G[j] * f;
+                }
+                if (par) acc[2 + k] += a;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            go[j] = G[j] * sp[j] * q.pre;
+            if (par) acc[0] += G[j] * sp[j] * u[j];
+        }
+    }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void waveshaper_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                             float* __restrict__ gx, const float* __restrict__ log_pre,
+                                                             const float* __restrict__ log_post,
+                                                             const float* __restrict__ p0, const float* __restrict__ p1,
+                                                             const float* __restrict__ dc, float* __restrict__ part,
+                                                             float* __restrict__ dcpart, WsBwdArgs a, int vec) {
+    constexpr int NA = WsAcc<MODE>::N;
+    constexpr bool POLY = MODE == GFX_WS_POWER || MODE == GFX_WS_CHEBYSHEV;
+    __shared__ float sw[WS_MAX_K];
+    __shared__ float red[4][NA];
+    __shared__ float tot[NA];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool par = a.want_par != 0, use_tanh = a.use_tanh != 0;
+    const float inv = a.inverse_post ? 1.0f : 0.0f;
+    const int nsum = POLY ? 2 + a.K : NA;            // sums of this mode that are in use
+    for (int64_t r = blockIdx.y; r < a.R; r += gridDim.y) {
+        WsRow q;
+        ws_row_setup<MODE>(q, sw, r, a.K, a.inverse_post, log_pre, log_post, p0, p1);
+        float acc[NA];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) acc[j] = 0.0f;
+        for (int c = 0; c < a.C; ++c) {
+            q.dc = dc ? dc[r * a.C + c] : 0.0f;
+            const float* xr = x + nrow_off(a.xmap, r, c);
+            const float* gr = gy + nrow_off(a.gmap, r, c);
+            float* outr = gx ? gx + nrow_off(a.omap, r, c) : nullptr;
+            const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+            float dsum = 0.0f;
+            int64_t n0 = tid;                        // first sample of the scalar loop: the whole row, or the tail
+            if (vec) {
+                using f4 = float __attribute__((ext_vector_type(4)));
+                for (int64_t i = tid; i < a.L / 4; i += nthr) {
+                    const f4 v = reinterpret_cast<const f4*>(xr)[i], g = reinterpret_cast<const f4*>(gr)[i];
+                    const float xs[4] = {v.x, v.y, v.z, v.w}, gs[4] = {g.x, g.y, g.z, g.w};
+                    float go[4];
+                    bwd_samples<MODE, 4>(xs, gs, go, q, a.K, use_tanh, inv, par, acc);
+                    if (outr) {
+                        f4 o;
+                        o.x = go[0]; o.y = go[1]; o.z = go[2]; o.w = go[3];
+                        reinterpret_cast<f4*>(outr)[i] = o;      // (a plain store: remove_dc reads it back)
+                        dsum += (go[0] + go[1]) + (go[2] + go[3]);
+                    }
+                }
+                n0 = (a.L & ~int64_t(3)) + tid;
+            }
+            for (int64_t n = n0; n < a.L; n += nthr) {
+                const float xs[1] = {xr[n]}, gs[1] = {gr[n]};
+                float go[1];
+                bwd_samples<MODE, 1>(xs, gs, go, q, a.K, use_tanh, inv, par, acc);
+                if (outr) {
+                    outr[n] = go[0];
+                    dsum += go[0];
+                }
+            }
+            if (dcpart) {                            // sum over time of this row-channel's gx, for the centring's adjoint
+                dsum = wave_sum(dsum);
+                __syncthreads();                     // red[][0] free again
+                if (lane == 0) red[wave][0] = dsum;
+                __syncthreads();
+                if (threadIdx.x == 0)
+                    dcpart[(r * a.C + c) * gridDim.x + blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+            }
+        }
+        if (par) {
+            __syncthreads();                         // red / tot free again
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                if (j < nsum) {
+                    const float s = wave_sum(acc[j]);
+                    if (lane == 0) red[wave][j] = s;
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < nsum) {
+                const int j = threadIdx.x;
+                float s = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+                if (MODE == GFX_WS_PIECEWISE) {
+                    if (j == 2) s *= q.ap;
+                    if (j == 3) s *= q.an;
+                    if (j == 4) s *= q.kn * (1.0f - q.kn);
+                    if (j == 5) s *= q.kp * (1.0f - q.kp);
+                }
+                if (POLY && j >= 2) {                // raw sums of G f(B_k) first: the output sum needs them
+                    if (j == 2) s *= use_tanh ? tanhf(1.0f) : 1.0f;
+                    tot[j] = s;
+                }
+                if (!POLY || j < 2) tot[j] = s;
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < nsum) {
+                const int j = threadIdx.x;
+                float s = tot[j];
+                if (POLY) {
+                    if (j < 2) {                     // sum G s(u) = sum_k w_k sum G f(B_k)
+                        float gys = 0.0f;
+                        for (int k = 0; k < a.K; ++k) gys += sw[k] * tot[2 + k];
+                        s = j == 0 ? s - inv * gys : gys;
+                    } else {
+                        s *= 1.0f - sw[j - 2] * sw[j - 2];
+                    }
+                }
+                part[(r * a.NS + j) * gridDim.x + blockIdx.x] = s;
+            }
+        }
+    }
+}
+
+// a row's partial sums -> the parameter gradients (double, fixed order); the row-channels' mean input gradient
+__global__ __launch_bounds__(256) void ws_bwd_finish_kernel(const float* __restrict__ part, const float* __restrict__ dcpart,
+                                                            float* __restrict__ gmean, float* __restrict__ g_pre,
+                                                            float* __restrict__ g_post, float* __restrict__ g_p0,
+                                                            float* __restrict__ g_p1, int64_t R, int C, int64_t L, int NS,
+                                                            int bx, int mode, int K) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    if (part) {
+        for (int64_t i = tid; i < R * NS; i += nthr) {
+            const int64_t r = i / NS;
+            const int j = (int)(i - r * NS);
+            float* dst = nullptr;
+            if (j == 0) dst = g_pre ? g_pre + r : nullptr;
+            else if (j == 1) dst = g_post ? g_post + r : nullptr;
+            else if (mode == GFX_WS_TANH) dst = (g_p0 && j == 2) ? g_p0 + r : nullptr;
+            else if (mode == GFX_WS_PIECEWISE) dst = j < 4 ? (g_p0 ? g_p0 + 2 * r + (j - 2) : nullptr) : (g_p1 ? g_p1 + 2 * r + (j - 4) : nullptr);
+            else dst = g_p0 ? g_p0 + r * K + (j - 2) : nullptr;
+            if (!dst) continue;
+            double s = 0.0;
+            for (int b = 0; b < bx; ++b) s += (double)part[i * bx + b];
+            *dst = (float)s;
+        }
+    }
+    if (dcpart) {
+        for (int64_t i = tid; i < R * C; i += nthr) {
+            double s = 0.0;
+            for (int b = 0; b < bx; ++b) s += (double)dcpart[i * bx + b];
+            gmean[i] = (float)(s / (double)L);
+        }
+    }
+}
+
+// the adjoint of the centring x - mean(x): gx -= mean(gx) per row-channel
+__global__ __launch_bounds__(256) void ws_sub_mean_kernel(float* __restrict__ gx, gfx_rowmap_t omap,
+                                                          const float* __restrict__ gmean, int64_t R, int C, int64_t L,
+                                                          int vec) {
+    for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
+        for (int c = 0; c < C; ++c) {
+            const float m = gmean[r * C + c];
+            float* outr = gx + nrow_off(omap, r, c);
+            const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+            int64_t n0 = tid;
+            if (vec) {
+                using f4 = float __attribute__((ext_vector_type(4)));
+                for (int64_t i = tid; i < L / 4; i += nthr) reinterpret_cast<f4*>(outr)[i] -= m;
+                n0 = (L & ~int64_t(3)) + tid;
+            }
+            for (int64_t n = n0; n < L; n += nthr) outr[n] -= m;
+        }
+    }
+}
+
+// [lo, hi) in floats that a mapped (R, C, L) signal covers (strides >= 0)
+static inline void map_span(const float* p, const gfx_rowmap_t& m, int64_t R, int64_t C, int64_t L, const float*& lo,
+                            const float*& hi) {
+    const int64_t nin = R < m.inner ? R : m.inner;
+    lo = p;
+    hi = p + ((R - 1) / m.inner) * m.stride_outer + (nin - 1) * m.stride_inner + (C - 1) * m.stride_ch + L;
+}
+
+// Is `delta` a sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on (strides sorted, largest first)?
+static bool ws_reachable(int64_t delta, const int64_t (*dims)[2], int nd, int i) {
+    if (i == nd) return delta == 0;
+    const int64_t st = dims[i][0], n = dims[i][1], qd = delta / st;
+    for (int64_t c = qd; c <= qd + 1; ++c) {
+        if (c >= n) continue;
+        const int64_t rest = delta - c * st;
+        if (ws_reachable(rest < 0 ? -rest : rest, dims, nd, i + 1)) return true;
+    }
+    return false;
+}
+
+// Do two mapped signals share an element?  Exact for two views with the same positive strides (two node ranges of one
+// render buffer interleave in memory without touching), the covered ranges otherwise.
+static bool ws_overlap(const float* a, const gfx_rowmap_t& am, const float* b, const gfx_rowmap_t& bm, int64_t R, int64_t C,
+                       int64_t L) {
+    const float *alo, *ahi, *blo, *bhi;
+    map_span(a, am, R, C, L, alo, ahi);
+    map_span(b, bm, R, C, L, blo, bhi);
+    if (!(alo < bhi && blo < ahi)) return false;
+    const int64_t nin = R < am.inner ? R : am.inner, nout = (R + am.inner - 1) / am.inner;
+    const bool same = am.inner == bm.inner && am.stride_outer == bm.stride_outer && am.stride_inner == bm.stride_inner &&
+                      am.stride_ch == bm.stride_ch && (nout == 1 || am.stride_outer > 0) &&
+                      (nin == 1 || am.stride_inner > 0) && (C == 1 || am.stride_ch > 0) && R % am.inner == 0;
+    if (!same) return true;
+    int64_t dims[4][2] = {{am.stride_outer, nout}, {am.stride_inner, nin}, {am.stride_ch, C}, {1, L}};
+    int nd = 0;
+    for (int i = 0; i < 4; ++i)
+        if (dims[i][1] > 1) { dims[nd][0] = dims[i][0]; dims[nd][1] = dims[i][1]; ++nd; }
+    for (int i = 1; i < nd; ++i)                       // insertion sort, largest stride first
+        for (int j = i; j > 0 && dims[j][0] > dims[j - 1][0]; --j) {
+            const int64_t s0 = dims[j][0], s1 = dims[j][1];
+            dims[j][0] = dims[j - 1][0]; dims[j][1] = dims[j - 1][1];
+            dims[j - 1][0] = s0; dims[j - 1][1] = s1;
+        }
+    const int64_t delta = a > b ? a - b : b - a;
+    return ws_reachable(delta, dims, nd, 0);
+}
+
+}  // namespace gfx
+
+extern "C" {
+
+size_t gfx_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K) {
+    if (R <= 0 || C <= 0 || L <= 0 || K < 0 || K > WS_MAX_K) return 0;
+    const size_t bx = (size_t)ws_blocks(L);
+    return sizeof(float) * ((size_t)R * (size_t)ws_nsums(K) * bx + (size_t)R * (size_t)C * bx + (size_t)R * (size_t)C);
+}
+
+int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R, int64_t C,
+                           int64_t L, int mode, int use_tanh, int inverse_post_gain, const float* log_pre_gain,
+                           const float* log_post_gain, const float* p0, const float* p1, int64_t K, const float* dc,
+                           float* gx, gfx_rowmap_t omap, float* g_log_pre_gain, float* g_log_post_gain, float* g_p0,
+                           float* g_p1, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !gy || R <= 0 || C <= 0 || L <= 0 || R > 0x7fffffffLL || xmap.inner <= 0 || gmap.inner <= 0) return GFX_EINVAL;
+    if (mode < GFX_WS_TANH || mode > GFX_WS_CHEBYSHEV) return GFX_EINVAL;
+    if (inverse_post_gain && !log_pre_gain) return GFX_EINVAL;
+    if (mode == GFX_WS_PIECEWISE && (!p0 || !p1)) return GFX_EINVAL;
+    const bool poly = mode == GFX_WS_POWER || mode == GFX_WS_CHEBYSHEV;
+    if (poly && (!p0 || K < 1 || K > WS_MAX_K)) return GFX_EINVAL;
+    if (!poly) K = 0;
+    const bool want_par = g_log_pre_gain || g_log_post_gain || g_p0 || g_p1;
+    if (!gx && !want_par) return GFX_EINVAL;
+    // a gradient of something that is not there (or, for the post gain under inverse_post_gain, not used)
+    if ((g_log_pre_gain && !log_pre_gain) || (g_log_post_gain && (!log_post_gain || inverse_post_gain)) || (g_p0 && !p0) ||
+        (g_p1 && mode != GFX_WS_PIECEWISE))
+        return GFX_EINVAL;
+    if (gx) {
+        if (omap.inner <= 0) return GFX_EINVAL;
+        if (xmap.stride_outer < 0 || xmap.stride_inner < 0 || xmap.stride_ch < 0 || gmap.stride_outer < 0 ||
+            gmap.stride_inner < 0 || gmap.stride_ch < 0 || omap.stride_outer < 0 || omap.stride_inner < 0 || omap.stride_ch < 0)
+            return GFX_EINVAL;
+        if (ws_overlap(gx, omap, x, xmap, R, C, L) || ws_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
+    }
+    const bool center = dc && gx;
+    const int64_t bx = ws_blocks(L);
+    const int NS = ws_nsums(K);
+    float *part = nullptr, *dcpart = nullptr, *gmean = nullptr;
+    if (want_par || center) {
+        if (!ws) return GFX_EINVAL;
+        if (ws_bytes < gfx_waveshaper_bwd_ws_bytes(R, C, L, K)) return GFX_ENOSPC;
+        float* w = static_cast<float*>(ws);
+        if (want_par) part = w;
+        if (center) {
+            dcpart = w + (size_t)R * NS * bx;
+            gmean = dcpart + (size_t)R * C * bx;
+        }
+    }
+    WsBwdArgs a;
+    a.xmap = xmap; a.gmap = gmap; a.omap = gx ? omap : xmap; a.R = R; a.L = L; a.C = (int)C; a.K = (int)K; a.NS = NS;
+    a.use_tanh = use_tanh; a.inverse_post = inverse_post_gain; a.want_par = want_par;
+    const int vec = aligned16(x) && aligned16(gy) && map_vec(xmap) && map_vec(gmap) && (!gx || (aligned16(gx) && map_vec(omap)));
+    const dim3 grid((unsigned)bx, (unsigned)(R > 65535 ? 65535 : R));
+    hipStream_t st = (hipStream_t)stream;
+    switch (mode) {
+        case GFX_WS_TANH:
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_TANH>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            break;
+        case GFX_WS_PIECEWISE:
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_PIECEWISE>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            break;
+        case GFX_WS_POWER:
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_POWER>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            break;
+        default:
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_CHEBYSHEV>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            break;
+    }
+    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    if (part || dcpart) {
+        const int64_t items = R * (NS > (int)C ? NS : (int)C);
+        const int64_t nb = (items + 255) / 256;
+        hipLaunchKernelGGL(ws_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, st, part, dcpart,
+                           gmean, g_log_pre_gain, g_log_post_gain, g_p0, g_p1, R, (int)C, L, NS, (int)bx, mode, (int)K);
+        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    }
+    if (center) {
+        hipLaunchKernelGGL(ws_sub_mean_kernel, grid, dim3(256), 0, st, gx, omap, gmean, R, (int)C, L,
+                           (int)(aligned16(gx) && map_vec(omap)));
+        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    }
+    return GFX_OK;
 }
 
 }  // extern "C"

@@ -1304,9 +1304,11 @@ def row_mean(x):
 
 @_on_device
 def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None, use_tanh=False,
-               inverse_post_gain=False, remove_dc=False, out=None):
-    """Memoryless distortion of every row (see gfx_waveshaper_f32 in the header for the modes)."""
-    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out)
+               inverse_post_gain=False, remove_dc=False, out=None, dc=None, return_dc=False):
+    """Memoryless distortion of every row (see gfx_waveshaper_f32 in the header for the modes).
+    ``dc``: the row-channel means of x when the caller already has them (``remove_dc``); ``return_dc``: -> (out, dc), the
+    means this call subtracted (None without ``remove_dc``) -- what waveshaper_bwd needs of them."""
+    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
     xmap, R, C, L = rowmap(x)
     if out is None:
         out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
@@ -1314,14 +1316,71 @@ def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None,
     c = lambda t: None if t is None else t.contiguous().view(R, -1)  # noqa: E731
     log_pre_gain, log_post_gain, p0, p1 = c(log_pre_gain), c(log_post_gain), c(p0), c(p1)
     K = p0.shape[1] if (p0 is not None and mode in (WS_POWER, WS_CHEBYSHEV)) else 0
-    dc = row_mean(x) if remove_dc else None
+    if not remove_dc:
+        dc = None
+    elif dc is None:
+        dc = row_mean(x)
+    else:
+        _expect(dc, (R * C,), "waveshaper: dc")
+        dc = dc.contiguous()
     with _timed("waveshaper_kernel", 8 * R * C * L):
         check(
             lib().gfx_waveshaper_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, mode, int(use_tanh), int(inverse_post_gain),
                                      _ptr(log_pre_gain), _ptr(log_post_gain), _ptr(p0), _ptr(p1), K, _ptr(dc), _stream()),
             "gfx_waveshaper_f32",
         )
-    return out
+    return (out, dc) if return_dc else out
+
+
+WS_GRADS = ("x", "log_pre_gain", "log_post_gain", "p0", "p1")
+
+
+@_on_device
+def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None, use_tanh=False,
+                   inverse_post_gain=False, remove_dc=False, dc=None, out=None, want=WS_GRADS):
+    """Backward of :func:`waveshaper` in one streaming pass (gfx_waveshaper_bwd_f32) -> (gx, grads).
+
+    ``x``, ``gy``: (R,C,L) or strided (B,n,C,L) views; ``want``: which of WS_GRADS to compute (a parameter that was not
+    given is skipped).  ``gx`` is None unless "x" is wanted, else ``out`` (any view of the signal's shape that shares no
+    element with x or gy) or a new (R,C,L) tensor.  ``grads``: {name: (R, n) gradient} of the wanted parameters.
+    ``dc``: the means the forward subtracted (``waveshaper(..., return_dc=True)``); recomputed when missing."""
+    _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
+    xmap, R, C, L = rowmap(x)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L) or (out is not None and rowmap(out)[1:] != (R, C, L)):
+        raise ValueError(f"waveshaper_bwd: gradient / output shapes do not match the input {tuple(x.shape)}")
+    unknown = set(want) - set(WS_GRADS)
+    if unknown:
+        raise ValueError(f"waveshaper_bwd: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
+    c = lambda t: None if t is None else t.contiguous().view(R, -1)  # noqa: E731
+    params = {"log_pre_gain": c(log_pre_gain), "log_post_gain": c(log_post_gain), "p0": c(p0), "p1": c(p1)}
+    poly = mode in (WS_POWER, WS_CHEBYSHEV)
+    K = params["p0"].shape[1] if (params["p0"] is not None and poly) else 0
+    if not remove_dc:
+        dc = None
+    elif dc is None:
+        dc = row_mean(x)
+    else:
+        _expect(dc, (R * C,), "waveshaper_bwd: dc")
+        dc = dc.contiguous()
+    gx = None
+    if "x" in want:
+        gx = torch.empty((R, C, L), dtype=torch.float32, device=x.device) if out is None else out
+    grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
+    ws = None
+    if grads or (gx is not None and dc is not None):
+        ws = torch.empty(lib().gfx_waveshaper_bwd_ws_bytes(R, C, L, K), dtype=torch.uint8, device=x.device)
+    with _timed("waveshaper_bwd_kernel", (8 if gx is None else 12) * R * C * L):
+        check(
+            lib().gfx_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, mode, int(use_tanh),
+                                         int(inverse_post_gain), _ptr(params["log_pre_gain"]),
+                                         _ptr(params["log_post_gain"]), _ptr(params["p0"]), _ptr(params["p1"]), K, _ptr(dc),
+                                         _ptr(gx), xmap if gx is None else rowmap(gx)[0], _ptr(grads.get("log_pre_gain")),
+                                         _ptr(grads.get("log_post_gain")), _ptr(grads.get("p0")), _ptr(grads.get("p1")),
+                                         _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+            "gfx_waveshaper_bwd_f32",
+        )
+    return gx, grads
 
 
 # ----------------------------------------------------------------------------------------- reverb IR

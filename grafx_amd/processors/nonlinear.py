@@ -1,14 +1,16 @@
 """Memoryless distortions (mirrors grafx.processors.nonlinear — reference nonlinear.py:6-309).
 
 Inference runs one streaming HIP pass per processor (`gfx_waveshaper_f32`, plus `gfx_row_mean_f32` when
-`remove_dc` is set); when a gradient is requested the same formulas are evaluated with torch ops so that
-autograd differentiates them (elementwise, no custom backward needed)."""
+`remove_dc` is set).  When a gradient is requested the same pass runs as the forward of one autograd node
+(`autograd.WaveshaperFn`) whose backward is one more streaming pass (`gfx_waveshaper_bwd_f32`): nothing full-size is kept
+but the input.  Every class keeps its formula as torch ops in `torch_forward` (any device, any dtype): the float64
+reference of the tests, and what the native backward is measured against."""
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..autograd import needs_grad
-from .core._buffer_io import BufferIO
+from ..autograd import WaveshaperFn, needs_grad
+from .core._buffer_io import BufferIO, write_rows
 
 
 def _center(x, remove_dc):
@@ -16,6 +18,8 @@ def _center(x, remove_dc):
 
 
 class _Waveshaper(BufferIO, nn.Module):
+    accepts_strided_rows = True   # forward() also takes a strided (B, n, C, L) view (under grad it then returns (B, n, C, L))
+
     def stream_check(self):
         if self.remove_dc:
             raise ValueError(f"{type(self).__name__}: remove_dc=True subtracts the mean of the whole signal, which a block "
@@ -23,7 +27,7 @@ class _Waveshaper(BufferIO, nn.Module):
 
     def render_into(self, x4, out4, **params):
         if needs_grad(x4, *params.values()):
-            return super().render_into(x4, out4, **params)
+            return write_rows(out4, self.forward(x4, **params))
         return self.forward(x4, _out=out4, **params)
 
 
@@ -41,15 +45,23 @@ class TanhDistortion(_Waveshaper):
         post = log_post_gain if (self.pre_post_gain and not self.inverse_post_gain) else None
         b = bias if self.use_bias else None
         if needs_grad(input_signals, pre, post, b):
-            u = _center(input_signals, self.remove_dc)
-            g = torch.exp(pre).unsqueeze(-1) if pre is not None else None
-            u = u * g if g is not None else u
-            y = torch.tanh(u + b.unsqueeze(-1)) - torch.tanh(b.unsqueeze(-1)) if b is not None else torch.tanh(u)
-            if inverse:
-                return y / g
-            return y * torch.exp(post).unsqueeze(-1) if post is not None else y
+            return WaveshaperFn.apply(input_signals, pre, post, b, None, ops.WS_TANH, False, inverse, self.remove_dc)
         return ops.waveshaper(input_signals, ops.WS_TANH, pre, post, p0=b, inverse_post_gain=inverse,
                               remove_dc=self.remove_dc, out=_out)
+
+    def torch_forward(self, input_signals, log_pre_gain=None, log_post_gain=None, bias=None):
+        """forward() as torch ops."""
+        pre = log_pre_gain if self.pre_post_gain else None
+        inverse = self.pre_post_gain and self.inverse_post_gain
+        post = log_post_gain if (self.pre_post_gain and not self.inverse_post_gain) else None
+        b = bias if self.use_bias else None
+        u = _center(input_signals, self.remove_dc)
+        g = torch.exp(pre).unsqueeze(-1) if pre is not None else None
+        u = u * g if g is not None else u
+        y = torch.tanh(u + b.unsqueeze(-1)) - torch.tanh(b.unsqueeze(-1)) if b is not None else torch.tanh(u)
+        if inverse:
+            return y / g
+        return y * torch.exp(post).unsqueeze(-1) if post is not None else y
 
     def parameter_size(self):
         size = {}
@@ -74,15 +86,23 @@ class PiecewiseTanhDistortion(_Waveshaper):
         inverse = self.pre_post_gain and self.inverse_post_gain
         post = log_post_gain if (self.pre_post_gain and not self.inverse_post_gain) else None
         if needs_grad(input_signals, log_hardness, z_threshold, pre, post):
-            u = _center(input_signals, self.remove_dc)
-            g = torch.exp(pre).unsqueeze(-1) if pre is not None else None
-            u = u * g if g is not None else u
-            y = self.apply_distortion(u, torch.exp(log_hardness), torch.sigmoid(z_threshold))
-            if inverse:
-                return y / g
-            return y * torch.exp(post).unsqueeze(-1) if post is not None else y
+            return WaveshaperFn.apply(input_signals, pre, post, log_hardness, z_threshold, ops.WS_PIECEWISE, False, inverse,
+                                      self.remove_dc)
         return ops.waveshaper(input_signals, ops.WS_PIECEWISE, pre, post, p0=log_hardness, p1=z_threshold,
                               inverse_post_gain=inverse, remove_dc=self.remove_dc, out=_out)
+
+    def torch_forward(self, input_signals, log_hardness, z_threshold, log_pre_gain=None, log_post_gain=None):
+        """forward() as torch ops."""
+        pre = log_pre_gain if self.pre_post_gain else None
+        inverse = self.pre_post_gain and self.inverse_post_gain
+        post = log_post_gain if (self.pre_post_gain and not self.inverse_post_gain) else None
+        u = _center(input_signals, self.remove_dc)
+        g = torch.exp(pre).unsqueeze(-1) if pre is not None else None
+        u = u * g if g is not None else u
+        y = self.apply_distortion(u, torch.exp(log_hardness), torch.sigmoid(z_threshold))
+        if inverse:
+            return y / g
+        return y * torch.exp(post).unsqueeze(-1) if post is not None else y
 
     @staticmethod
     def apply_distortion(u, hardness, threshold):
@@ -122,13 +142,19 @@ class _PolynomialDistortion(_Waveshaper):
     def forward(self, input_signals, basis_weights, log_pre_gain=None, _out=None):
         pre = log_pre_gain if self.pre_gain else None
         if needs_grad(input_signals, basis_weights, pre):
-            u = _center(input_signals, self.remove_dc)
-            u = u * torch.exp(pre).unsqueeze(-1) if pre is not None else u
-            terms = self.basis(u)                                   # (K, R, C, L)
-            terms = torch.tanh(terms) if self.use_tanh else terms
-            return (terms * torch.tanh(basis_weights).T[:, :, None, None]).sum(0)
+            return WaveshaperFn.apply(input_signals, pre, None, basis_weights, None, self.mode, self.use_tanh, False,
+                                      self.remove_dc)
         return ops.waveshaper(input_signals, self.mode, pre, None, p0=basis_weights, use_tanh=self.use_tanh,
                               remove_dc=self.remove_dc, out=_out)
+
+    def torch_forward(self, input_signals, basis_weights, log_pre_gain=None):
+        """forward() as torch ops (materialises the K basis terms, as upstream does)."""
+        pre = log_pre_gain if self.pre_gain else None
+        u = _center(input_signals, self.remove_dc)
+        u = u * torch.exp(pre).unsqueeze(-1) if pre is not None else u
+        terms = self.basis(u)                                   # (K, R, C, L)
+        terms = torch.tanh(terms) if self.use_tanh else terms
+        return (terms * torch.tanh(basis_weights).T[:, :, None, None]).sum(0)
 
     def parameter_size(self):
         size = {"basis_weights": self.max_order}

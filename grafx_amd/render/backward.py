@@ -28,7 +28,8 @@ def _tape_safe_types():
     """Exact processor classes whose output is linear in their one native autograd node (see the stage-wise backward)."""
     from .. import processors as P
 
-    return (P.ParametricEqualizer, P.Compressor, P.NoiseGate, P.STFTMaskedNoiseReverb, P.BiquadFilter)
+    return (P.ParametricEqualizer, P.Compressor, P.NoiseGate, P.STFTMaskedNoiseReverb, P.BiquadFilter,
+            P.TanhDistortion, P.PiecewiseTanhDistortion, P.PowerDistortion, P.ChebyshevDistortion)
 
 
 def _flatten_tree(tree, leaves):

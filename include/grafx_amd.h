@@ -668,6 +668,22 @@ int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t
                        int mode, int use_tanh, int inverse_post_gain, const float* log_pre_gain,
                        const float* log_post_gain, const float* p0, const float* p1, int64_t K, const float* dc,
                        void* stream);
+/* Backward of gfx_waveshaper_f32 in one streaming pass over x and gy (same configuration, parameters and dc -- the
+ * array gfx_row_mean_f32 produced for the forward; null without remove_dc).  With G = gy * post, s the shape before the
+ * post gain:  gx = G s'(u) pre  (with dc: minus its own mean over time per row-channel, the adjoint of the centring),
+ *   g_log_pre_gain (R)  = sum G (s'(u) u - [inverse_post_gain] s(u)),    g_log_post_gain (R) = sum G s(u),
+ *   g_p0: (R) bias / (R,2) log_hardness / (R,K) basis weights,           g_p1: (R,2) z_threshold,
+ * every sum over the row's C * L samples.  Each output may be null (not computed), not all of them; gx (addressed through
+ * its own row map) must not share an element with x or gy.  A gradient may only be asked for a parameter that was given
+ * (g_log_post_gain: and used, i.e. not under inverse_post_gain).  Row sums are stored per workgroup in `ws`
+ * (gfx_waveshaper_bwd_ws_bytes; K = 0 for the two tanh modes) and added in double in a fixed order: no atomics, results
+ * are bit-identical from run to run.  ws may be null when only gx is asked and dc is null. */
+size_t gfx_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K);
+int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R, int64_t C,
+                           int64_t L, int mode, int use_tanh, int inverse_post_gain, const float* log_pre_gain,
+                           const float* log_post_gain, const float* p0, const float* p1, int64_t K, const float* dc,
+                           float* gx, gfx_rowmap_t omap, float* g_log_pre_gain, float* g_log_post_gain, float* g_p0,
+                           float* g_p1, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
