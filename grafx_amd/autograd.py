@@ -673,7 +673,7 @@ class BallisticsFn(torch.autograd.Function):
 
 class BallisticsStateFn(torch.autograd.Function):
     """(y, zf) = the recursion of BallisticsFn started from y[-1] = zi (R,) instead of 1, zf = y[:, L-1]
-    (gfx_ballistics_state_f32 / gfx_ballistics_bwd_state_f32).  Differentiable in x, z_alpha and zi; either output's cotangent
+    (zi / zf of gfx_ballistics_f32 / gfx_ballistics_bwd_f32).  Differentiable in x, z_alpha and zi; either output's cotangent
     may be missing.  A cotangent of zf is one of y[:, L-1]; dL/dzi is the adjoint carry that leaves sample 0."""
 
     @staticmethod

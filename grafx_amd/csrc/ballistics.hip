@@ -429,33 +429,16 @@ extern "C" {
 
 size_t gfx_ballistics_ws_bytes(int64_t R) { return R <= 0 ? 0 : (size_t)R * sizeof(unsigned); }
 
-int gfx_ballistics_f32(const float* u, const float* z_alpha, float* y, int64_t R, int64_t L, void* stream) {
-    gfx_rowmap_t none = {1, 0, 0, 0};
-    return ballistics_run<0>(u, none, 1, z_alpha, 0, y, R, L, nullptr, 0, (hipStream_t)stream);
-}
-
-int gfx_ballistics_ws_f32(const float* u, const float* z_alpha, int is_coef, float* y, int64_t R, int64_t L, void* ws,
-                          size_t ws_bytes, void* stream) {
-    return gfx_ballistics_state_f32(u, z_alpha, is_coef, nullptr, nullptr, y, R, L, ws, ws_bytes, stream);
-}
-
-int gfx_ballistics_state_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
-                             int64_t L, void* ws, size_t ws_bytes, void* stream) {
+int gfx_ballistics_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
+                       int64_t L, void* ws, size_t ws_bytes, void* stream) {
     gfx_rowmap_t none = {1, 0, 0, 0};
     return ballistics_run<0>(u, none, 1, z_alpha, is_coef, y, R, L, ws, ws_bytes, (hipStream_t)stream, nullptr, zi, zf);
 }
 
 int gfx_dynamics_ballistics_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
                                 const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                int64_t R, int64_t C, int64_t L, int knee, int gate, void* ws, size_t ws_bytes, void* stream) {
-    return gfx_dynamics_ballistics_state_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L,
-                                             knee, gate, nullptr, nullptr, ws, ws_bytes, stream);
-}
-
-int gfx_dynamics_ballistics_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                                      const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                      int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
-                                      size_t ws_bytes, void* stream) {
+                                int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
+                                size_t ws_bytes, void* stream) {
     if (!log_threshold || !log_ratio || knee < 0 || knee > 2 || (knee != 0 && !log_knee)) return GFX_EINVAL;
     if (param_rows < 1 || param_rows > R || xmap.inner <= 0 || ymap.inner <= 0) return GFX_EINVAL;
     BlArgs g;
@@ -464,14 +447,9 @@ int gfx_dynamics_ballistics_state_f32(const float* x, gfx_rowmap_t xmap, float* 
     return ballistics_run<1, 1>(x, xmap, (int)C, z_alpha, 0, y, R, L, ws, ws_bytes, (hipStream_t)stream, &g, zi, zf);
 }
 
-int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef, float* env,
-                              int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
-    return gfx_ballistics_energy_state_f32(x, xmap, C, z_alpha, is_coef, nullptr, nullptr, env, R, L, ws, ws_bytes, stream);
-}
-
-int gfx_ballistics_energy_state_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
-                                    const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
-                                    void* stream) {
+int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
+                              const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
+                              void* stream) {
     return ballistics_run<1>(x, xmap, (int)C, z_alpha, is_coef, env, R, L, ws, ws_bytes, (hipStream_t)stream, nullptr, zi, zf);
 }
 

@@ -21,8 +21,8 @@ constexpr int BROWS = 64;   // (columns per tile: a template parameter of the ke
 // 2048 samples (c_min >= BWD_CMIN).  A group with a slower row (wave vote) takes the exact two-pass form of a linear scan
 // instead: chunk aggregates, a chain over the chunks, then the walk with the true carries.  Per-chunk sums of the two coefficient gradients go to `part` (chunks x R x 2) and are
 // added in chunk order by ballistics_bwd_finish_kernel: the same bits from run to run.  part == nullptr: one chunk, gz
-// written directly (gfx_ballistics_bwd_f32).
-// With a state (gfx_ballistics_bwd_state_f32) y[-1] = zi[row] instead of 1 -- the comparison at n = 0 is x[0] < zi and the
+// written directly (gfx_ballistics_bwd_f32 without a workspace).
+// With a state (zi) y[-1] = zi[row] instead of 1 -- the comparison at n = 0 is x[0] < zi and the
 // coefficient-gradient term there lambda[0] (x[0] - zi) -- and the carry that LEAVES sample 0, (1 - c[0]) lambda[0], is
 // dL/dzi: written to gzi by whichever workgroup walks sample 0 with the true carry.
 constexpr float BWD_CMIN = 0.0103f;   // (1 - 0.0103)^2048 = 6e-10
@@ -186,11 +186,6 @@ using namespace gfx;
 
 extern "C" {
 
-int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
-                           int64_t R, int64_t L, void* stream) {
-    return gfx_ballistics_bwd_state_f32(x, y, g, z_alpha, nullptr, gx, gz, nullptr, R, L, nullptr, 0, stream);
-}
-
 // chunks of the chunked adjoint: enough workgroups for ~16 waves per CU, chunks of at least 4096 samples (the 2048-sample
 // warm-up is walked on top of every chunk), a multiple of the 64-sample tile
 static int64_t ballistics_bwd_chunk(int64_t R, int64_t L, int* chunks) {
@@ -213,18 +208,8 @@ size_t gfx_ballistics_bwd_ws_bytes(int64_t R, int64_t L) {
     return (size_t)chunks * R * 4 * sizeof(float);   // partial sums and chunk aggregates, (chunks, R, 2) each
 }
 
-int gfx_ballistics_bwd_ws_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
-                              int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !y || !g || !z_alpha || !gx || !gz || R <= 0 || L <= 0) return GFX_EINVAL;
-    int chunks;
-    ballistics_bwd_chunk(R, L, &chunks);
-    if (chunks > 1 && !ws) return GFX_ENOSPC;
-    // (one chunk: the whole-row walk, whatever the workspace)
-    return gfx_ballistics_bwd_state_f32(x, y, g, z_alpha, nullptr, gx, gz, nullptr, R, L, chunks > 1 ? ws : nullptr, ws_bytes, stream);
-}
-
-int gfx_ballistics_bwd_state_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
-                                 float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
+int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
+                           float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || !g || !z_alpha || !gx || !gz || R <= 0 || L <= 0) return GFX_EINVAL;
     int chunks;
     const int64_t chunk = ballistics_bwd_chunk(R, L, &chunks);

@@ -50,7 +50,7 @@ const float2* tile_twiddle_table(hipStream_t stream) {
 
 extern "C" {
 
-int gfx_abi_version(void) { return 1; }
+int gfx_abi_version(void) { return GFX_ABI_VERSION; }
 
 int gfx_device_info(int* n_cu, size_t* lds_bytes) {
     int dev = 0;

@@ -363,14 +363,11 @@ int gfx_odd_alias_plan_f32(void* plan, int64_t P, void* ws, size_t ws_bytes, voi
 }
 
 int gfx_odd_alias_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                      const void* plan, void* ws, size_t ws_bytes, void* stream) {
-    return czt_alias<float>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream, false);
-}
-
-int gfx_odd_alias_rows_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo, int64_t len,
-                           int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes, void* stream) {
+                      const void* plan, void* ws, size_t ws_bytes, const gfx_rowmap_t* ymap, int64_t C, int64_t row0,
+                      void* stream) {
+    if (!ymap) return czt_alias<float>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream, false);
     if (C < 1 || C > 0x7fffffffLL) return GFX_EINVAL;
-    return czt_alias<float>(z, y, len, lo, len, rows, P, plan, ws, ws_bytes, stream, false, &ymap, (int)C, row0);
+    return czt_alias<float>(z, y, len, lo, len, rows, P, plan, ws, ws_bytes, stream, false, ymap, (int)C, row0);
 }
 
 // Transpose of gfx_odd_alias_f32 (the gradient of the aliasing step): with G'[k] = sum_n gy[n] e^{+2 pi i k n / Q},

@@ -41,7 +41,7 @@ struct CztGeom {
     int64_t P, Q, K, NFFT;   // NFFT = S * C * 8192
     int C, S;                // C <= 32 columns per sub-transform; S = 4^levels sub-transforms under `levels` outer radix-4 levels
     int levels;
-    // where the real output rows go: row r of the call at y + r * ldy (yC == 0), or -- gfx_odd_alias_rows_f32 -- row
+    // where the real output rows go: row r of the call at y + r * ldy (yC == 0), or -- the entries' ymap -- row
     // (row0 + r) of a (rows / yC, yC, len) signal addressed through a row map (a strided view of the render's buffer)
     int yC;
     int64_t row0;

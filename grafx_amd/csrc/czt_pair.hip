@@ -770,7 +770,7 @@ static int czt_pair_alias(const float* z, float* y, int64_t ldy, int64_t lo, int
     static const bool scaled = [] { const char* e = getenv("GRAFX_ALIAS_PAIR_SCALE"); return !(e && e[0] == '0'); }();
     uint32_t* rmax = nullptr;
     if (scaled && rows > 1 && given_max) {
-        rmax = const_cast<uint32_t*>(given_max);     // the producer of z left them (gfx_fftconv_rowmax_f32)
+        rmax = const_cast<uint32_t*>(given_max);     // the producer of z left them (gfx_fftconv_f32's rowmax)
     } else if (scaled && rows > 1) {
         // max |z| of every row, behind the transforms' own workspace
         rmax = (uint32_t*)((T2*)ws + pairs * g.NFFT);
@@ -840,26 +840,11 @@ int gfx_odd_alias_pair_plan_f32(void* plan, int64_t P, void* ws, size_t ws_bytes
 }
 
 int gfx_odd_alias_pair_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                           const void* plan, void* ws, size_t ws_bytes, void* stream) {
-    return czt_pair_alias<float>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream);
-}
-
-int gfx_odd_alias_pair_rows_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo, int64_t len,
-                                int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes, void* stream) {
+                           const void* plan, void* ws, size_t ws_bytes, const gfx_rowmap_t* ymap, int64_t C, int64_t row0,
+                           const uint32_t* rowmax, void* stream) {
+    if (!ymap) return czt_pair_alias<float>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream, nullptr, 0, 0, rowmax);
     if (C < 1 || C > 0x7fffffffLL || (row0 & 1)) return GFX_EINVAL;
-    return czt_pair_alias<float>(z, y, len, lo, len, rows, P, plan, ws, ws_bytes, stream, &ymap, (int)C, row0);
-}
-
-int gfx_odd_alias_pair_max_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                               const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, void* stream) {
-    return czt_pair_alias<float>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream, nullptr, 0, 0, rowmax);
-}
-
-int gfx_odd_alias_pair_rows_max_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo, int64_t len,
-                                    int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes,
-                                    const uint32_t* rowmax, void* stream) {
-    if (C < 1 || C > 0x7fffffffLL || (row0 & 1)) return GFX_EINVAL;
-    return czt_pair_alias<float>(z, y, len, lo, len, rows, P, plan, ws, ws_bytes, stream, &ymap, (int)C, row0, rowmax);
+    return czt_pair_alias<float>(z, y, len, lo, len, rows, P, plan, ws, ws_bytes, stream, ymap, (int)C, row0, rowmax);
 }
 
 #else
@@ -873,13 +858,8 @@ int gfx_odd_alias_pair_precise_plan_f32(void* plan, int64_t P, void* ws, size_t 
 }
 
 int gfx_odd_alias_pair_precise_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                                   const void* plan, void* ws, size_t ws_bytes, void* stream) {
-    return czt_pair_alias<double>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream);
-}
-
-int gfx_odd_alias_pair_precise_max_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                                       const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, int relu,
-                                       void* stream) {
+                                   const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, int relu,
+                                   void* stream) {
     return czt_pair_alias<double>(z, y, ldy, lo, len, rows, P, plan, ws, ws_bytes, stream, nullptr, 0, 0, rowmax, relu);
 }
 

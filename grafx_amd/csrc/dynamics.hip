@@ -25,7 +25,7 @@ namespace gfx {
 // start at the row start is exact if its scans start N samples early from a zero state: tiles [t_warm, t_lo) are
 // scanned without producing output, and samples before `s0 = t_warm * DTILE` count as zero for both scans.
 // u1row (training forward, whole rows only): also store (1-a) x the UN-truncated scan of the energy, which is what the
-// backward pass needs (gfx_dynamics_bwd_u1_f32) -- one extra 4-byte store per sample here instead of a pass over x there.
+// backward pass needs (gfx_dynamics_bwd_f32, u1_is_scratch = 0) -- one extra 4-byte store per sample here instead of a pass over x there.
 template <bool TRUNC>
 __device__ __forceinline__ void dyn_stream(const DynArgs& a, const OnePole& p, const Knee& q, const float* x0,
                                            const float* x1, float* y0, float* y1, float* slots, int t,
@@ -748,29 +748,6 @@ using namespace gfx;
 
 extern "C" {
 
-int gfx_dynamics_fused_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                           const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t R, int64_t C,
-                           int64_t L, int smoother, int64_t iir_len, int knee, int gate, void* stream) {
-    return gfx_dynamics_fused_ex_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, R, R, C, L, smoother,
-                                     iir_len, knee, gate, stream);
-}
-
-int gfx_dynamics_fused_ex_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                              const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                              int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
-                              void* stream) {
-    return gfx_dynamics_fused_u1_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L,
-                                     smoother, iir_len, knee, gate, nullptr, stream);
-}
-
-int gfx_dynamics_fused_u1_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                              const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                              int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
-                              float* u1, void* stream) {
-    return gfx_dynamics_fused_ws_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L,
-                                     smoother, iir_len, knee, gate, u1, nullptr, 0, stream);
-}
-
 size_t gfx_dynamics_ws_bytes(int64_t param_rows) {
     return param_rows <= 0 ? 0 : (size_t)param_rows * DP_TAB * sizeof(float);
 }
@@ -899,10 +876,10 @@ static int dynamics_fused_launch(const float* x, gfx_rowmap_t xmap, float* y, gf
 
 const char* gfx_dynamics_last_kernel(void) { return t_dyn_last_kernel; }
 
-int gfx_dynamics_fused_ws_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                              const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                              int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
-                              float* u1, void* ws, size_t ws_bytes, void* stream) {
+int gfx_dynamics_fused_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
+                           const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
+                           int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
+                           float* u1, void* ws, size_t ws_bytes, void* stream) {
     return dynamics_fused_launch(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L, smoother,
                                  iir_len, knee, gate, u1, ws, ws_bytes, stream, nullptr);
 }
@@ -912,18 +889,7 @@ int gfx_dynamics_fused_mix_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_
                                int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
                                float* u1, void* ws, size_t ws_bytes, const int64_t* sched, int64_t inner, int64_t n_acc,
                                float* mix, int64_t mix_sb, int64_t mix_sv, int64_t mix_sc, const int64_t* extras,
-                               int64_t n_pre, int64_t n_post, void* stream) {
-    return gfx_dynamics_fused_mix_flags_f32(x, xmap, y, ymap, log_threshold, log_ratio, log_knee, z_alpha, param_rows, R, C, L,
-                                            smoother, iir_len, knee, gate, u1, ws, ws_bytes, sched, inner, n_acc, mix, mix_sb,
-                                            mix_sv, mix_sc, extras, n_pre, n_post, 0, stream);
-}
-
-int gfx_dynamics_fused_mix_flags_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                                     const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                     int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
-                                     float* u1, void* ws, size_t ws_bytes, const int64_t* sched, int64_t inner, int64_t n_acc,
-                                     float* mix, int64_t mix_sb, int64_t mix_sv, int64_t mix_sc, const int64_t* extras,
-                                     int64_t n_pre, int64_t n_post, int flags, void* stream) {
+                               int64_t n_pre, int64_t n_post, int flags, void* stream) {
     if (!sched || !mix || inner < 1 || inner > 65535 || n_acc < 1 || n_acc > 4 || R % inner != 0 || !ws || smoother != 1)
         return GFX_EINVAL;
     if (n_pre < 0 || n_post < 0 || n_pre + n_post > 65535 || (n_pre + n_post > 0 && !extras)) return GFX_EINVAL;

@@ -70,7 +70,7 @@ __device__ __forceinline__ KneeGrad log_gain_grad(const Knee& q, float G) {
 // ---- fused backward of the compressor / gate with the one-pole energy smoother ------------------------------
 // Two passes, one workgroup per row.  The first (dyn_bwd_u1_kernel, forward in time) scans the energy of x into
 //   u1[n] = (1-a) * (untruncated scan of the energy)   (R, L)
-// -- or the training forward has stored it already (gfx_dynamics_fused_u1_f32) and the pass is not run.  The second
+// -- or the training forward has stored it already (gfx_dynamics_fused_f32's u1) and the pass is not run.  The second
 // (dyn_bwd_c_kernel) walks BACKWARD in time: it recomputes the gain and denv = dL/d(smoothed energy), relu-masked, from
 // (x, gy, u1) with env = relu(u1[m] - a^N u1[m-N]), runs the smoother's adjoint de[m] = sum_{k<N} h[k] denv[m+k] (the same
 // scan on the reversed sequence), writes gx = gain * gy + (2/C) * de * x and sums the parameter gradients of the row.
@@ -687,13 +687,14 @@ size_t gfx_dynamics_bwd_ws_bytes(int64_t R, int64_t L) {   // the pole table + f
     return (((size_t)R * DP_TAB + 1) & ~(size_t)1) * sizeof(float) + (size_t)R * (size_t)((L + OS_GTILE - 1) / OS_GTILE) * 4 * sizeof(double);
 }
 
-// `rescan`: u1 is SCRATCH (R x L floats) -- one-shot rows rebuild the scan inside their tiles and never touch it, the rows of
-// the row kernel get theirs from dyn_bwd_u1_kernel first
-static int dyn_bwd_launch(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                          const float* log_threshold, const float* log_ratio, const float* log_knee,
-                          const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                          float* gx, gfx_rowmap_t gxmap, float* gparams, float* u1, float* dalpha, void* ws,
-                          size_t ws_bytes, void* stream, bool rescan) {
+// u1_is_scratch = 0: u1 is the scan the forward pass kept.  u1_is_scratch != 0: u1 is SCRATCH (R x L floats) -- one-shot rows
+// rebuild the scan inside their tiles and never touch it, the rows of the row kernel get theirs from dyn_bwd_u1_kernel first
+int gfx_dynamics_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
+                         const float* log_threshold, const float* log_ratio, const float* log_knee,
+                         const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
+                         float* gx, gfx_rowmap_t gxmap, float* gparams, float* u1, int u1_is_scratch, float* dalpha, void* ws,
+                         size_t ws_bytes, void* stream) {
+    const bool rescan = u1_is_scratch != 0;
     if (!x || !gy || !log_threshold || !log_ratio || !z_alpha || !gx || !gparams || !u1) return GFX_EINVAL;
     if (R <= 0 || L <= 0 || (C != 1 && C != 2) || iir_len < 1 || knee < 0 || knee > 2 || (knee != 0 && !log_knee))
         return GFX_EINVAL;
@@ -707,7 +708,7 @@ static int dyn_bwd_launch(const float* x, gfx_rowmap_t xmap, const float* gy, gf
     const int64_t ngroups = (L + OS_GTILE - 1) / OS_GTILE;
     const bool vec = L % 4 == 0 && al16(x, xmap) && al16(gy, gmap) && al16(gx, gxmap) && ((uintptr_t)u1 & 15) == 0;
     if (ws && vec && L > OS_WTILE && R * ngroups <= 0x7ffffff0LL && ws_bytes >= gfx_dynamics_bwd_ws_bytes(R, L)) {
-        // rows with a short smoother memory (chosen on the device, as in gfx_dynamics_fused_ws_f32) run as one-shot tiles
+        // rows with a short smoother memory (chosen on the device, as in gfx_dynamics_fused_f32) run as one-shot tiles
         // whose workgroups leave partial sums behind the pole table; the row kernel writes the other rows
         float* t = (float*)ws;
         double* partial = reinterpret_cast<double*>(t + (((size_t)R * DP_TAB + 1) & ~(size_t)1));
@@ -729,44 +730,6 @@ static int dyn_bwd_launch(const float* x, gfx_rowmap_t xmap, const float* gy, gf
     hipLaunchKernelGGL(dyn_bwd_c_kernel, dim3((unsigned)R), dim3(DT), 0, st, x, gy, gmap, log_threshold,
                        log_ratio, log_knee, z_alpha, u1, dalpha, gparams, gx, a, tab);
     return GFX_LAUNCH_OK();
-}
-
-// The row-kernel backward on its own: scans x into `u1` (R x L floats of scratch, overwritten), then the one backward pass
-// over (x, gy, u1).  `denv` is accepted and ignored (the two-pass form that wrote it is gone).
-int gfx_dynamics_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                         const float* log_threshold, const float* log_ratio, const float* log_knee,
-                         const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                         float* gx, gfx_rowmap_t gxmap, float* gparams, float* denv, float* u1, float* dalpha,
-                         void* stream) {
-    (void)denv;
-    return dyn_bwd_launch(x, xmap, gy, gmap, log_threshold, log_ratio, log_knee, z_alpha, R, C, L, iir_len, knee, gate, gx, gxmap,
-                          gparams, u1, dalpha, nullptr, 0, stream, true);
-}
-
-int gfx_dynamics_bwd_u1_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                            const float* log_threshold, const float* log_ratio, const float* log_knee,
-                            const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                            float* gx, gfx_rowmap_t gxmap, float* gparams, const float* u1, float* dalpha, void* stream) {
-    return gfx_dynamics_bwd_u1_ws_f32(x, xmap, gy, gmap, log_threshold, log_ratio, log_knee, z_alpha, R, C, L, iir_len, knee,
-                                      gate, gx, gxmap, gparams, u1, dalpha, nullptr, 0, stream);
-}
-
-int gfx_dynamics_bwd_u1_ws_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                               const float* log_threshold, const float* log_ratio, const float* log_knee,
-                               const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                               float* gx, gfx_rowmap_t gxmap, float* gparams, const float* u1, float* dalpha, void* ws,
-                               size_t ws_bytes, void* stream) {
-    return dyn_bwd_launch(x, xmap, gy, gmap, log_threshold, log_ratio, log_knee, z_alpha, R, C, L, iir_len, knee, gate, gx, gxmap,
-                          gparams, const_cast<float*>(u1), dalpha, ws, ws_bytes, stream, false);
-}
-
-int gfx_dynamics_bwd_rescan_ws_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                                   const float* log_threshold, const float* log_ratio, const float* log_knee,
-                                   const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                                   float* gx, gfx_rowmap_t gxmap, float* gparams, float* u1_scratch, float* dalpha, void* ws,
-                                   size_t ws_bytes, void* stream) {
-    return dyn_bwd_launch(x, xmap, gy, gmap, log_threshold, log_ratio, log_knee, z_alpha, R, C, L, iir_len, knee, gate, gx, gxmap,
-                          gparams, u1_scratch, dalpha, ws, ws_bytes, stream, true);
 }
 
 int gfx_onepole_dz_f32(const float* g, const float* U, const float* D, const float* coef, float* da, int64_t R,

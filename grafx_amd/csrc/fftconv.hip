@@ -253,7 +253,7 @@ __device__ __forceinline__ void store_valid(const cx (&v)[32], float* __restrict
 
 
 // max |y| over what store_valid has just stored of this tile (positions O <= q < room of the tile), into rowmax[rco]: the
-// by-product for the odd-length aliasing's pair scaling (round 6; gfx_fftconv_rowmax_f32).  Non-negative floats order like
+// by-product for the odd-length aliasing's pair scaling (round 6; gfx_fftconv_f32's rowmax).  Non-negative floats order like
 // their bit patterns: a wave reduction and one atomic maximum per wave and tile.
 __device__ __forceinline__ void tile_rowmax(const cx (&v)[32], uint32_t* __restrict__ rowmax, unsigned rco, int64_t n0, int64_t O,
                                             int64_t Lout, int t) {
@@ -859,20 +859,14 @@ int64_t gfx_fftconv_part_len(int64_t N, int64_t Lout) {
 }
 
 
-size_t gfx_fir_spectrum_bytes(int64_t RCf, int64_t N) { return gfx_fir_spectrum_bytes_ex(RCf, N, 0); }
-
-size_t gfx_fir_spectrum_bytes_ex(int64_t RCf, int64_t N, int64_t part_len) {
+size_t gfx_fir_spectrum_bytes(int64_t RCf, int64_t N, int64_t part_len) {
     if (RCf <= 0 || N <= 0) return 0;
     const ConvGeom g = conv_geom(N, 1, part_len);
     return g.ok ? (size_t)RCf * g.nparts * H_TILE_F4 * sizeof(float4) : 0;
 }
 
-size_t gfx_fftconv_workspace_bytes(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N) {
-    return gfx_fftconv_workspace_bytes_ex(R, C_in, L, Lout, off, N, 0);
-}
-
-size_t gfx_fftconv_workspace_bytes_ex(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                                      int64_t part_len) {
+size_t gfx_fftconv_workspace_bytes(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N,
+                                   int64_t part_len) {
     (void)L;
     (void)off;
     if (R <= 0 || N <= 0 || Lout <= 0) return 0;
@@ -882,12 +876,7 @@ size_t gfx_fftconv_workspace_bytes_ex(int64_t R, int64_t C_in, int64_t L, int64_
 }
 
 int gfx_fir_spectrum_f32(const float* h, const float* gain, int64_t gain_div, void* Hs, int64_t RCf, int64_t N,
-                         void* stream) {
-    return gfx_fir_spectrum_ex_f32(h, gain, gain_div, Hs, RCf, N, 0, stream);
-}
-
-int gfx_fir_spectrum_ex_f32(const float* h, const float* gain, int64_t gain_div, void* Hs, int64_t RCf, int64_t N,
-                            int64_t part_len, void* stream) {
+                         int64_t part_len, void* stream) {
     if (!h || !Hs || RCf <= 0 || N <= 0 || (gain && gain_div <= 0)) return GFX_EINVAL;
     const ConvGeom g = conv_geom(N, 1, part_len);
     if (!g.ok) return GFX_EINVAL;
@@ -946,52 +935,20 @@ int gfx_fir_grad_f32(const float* x, gfx_rowmap_t xmap, const float* g, gfx_rowm
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
-int gfx_fftconv_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, float* y, gfx_rowmap_t ymap, int64_t R,
-                    int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws,
-                    size_t ws_bytes, void* stream) {
-    const gfx_rowmap_t none = {1, 0, 0, 0};
-    return gfx_fftconv_ex_f32(x, xmap, Hs, R, 0, y, ymap, nullptr, none, R, C_in, C_f, L, Lout, off, N, ws, ws_bytes,
-                              stream);
-}
-
-int gfx_fftconv_tee_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, float* y, gfx_rowmap_t ymap, float* xcopy,
-                        gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off,
-                        int64_t N, void* ws, size_t ws_bytes, void* stream) {
-    if (!xcopy) return GFX_EINVAL;
-    return gfx_fftconv_ex_f32(x, xmap, Hs, R, 0, y, ymap, xcopy, cmap, R, C_in, C_f, L, Lout, off, N, ws, ws_bytes,
-                              stream);
-}
-
-int gfx_fftconv_ex_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
-                       gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
-                       int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, void* stream) {
-    return gfx_fftconv_sched_f32(x, xmap, Hs, h_rows, part_len, y, ymap, xcopy, cmap, R, C_in, C_f, L, Lout, off, N, ws,
-                                 ws_bytes, GFX_SCHED_AUTO, stream);
-}
-
-
 static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
                          gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
                          int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, int schedule,
                          void* stream, uint32_t* rowmax, int* rowmax_written, bool state_call = false,
                          const float* zi = nullptr);
 
-int gfx_fftconv_sched_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
-                          gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
-                          int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, int schedule,
-                          void* stream) {
+int gfx_fftconv_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
+                    gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f, int64_t L,
+                    int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, int schedule, uint32_t* rowmax,
+                    int* rowmax_written, void* stream) {
+    if (!rowmax != !rowmax_written || (rowmax && schedule != GFX_SCHED_AUTO)) return GFX_EINVAL;
+    if (rowmax_written) *rowmax_written = 0;
     return fftconv_sched(x, xmap, Hs, h_rows, part_len, y, ymap, xcopy, cmap, R, C_in, C_f, L, Lout, off, N, ws, ws_bytes,
-                         schedule, stream, nullptr, nullptr);
-}
-
-int gfx_fftconv_rowmax_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,
-                           gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap, int64_t R, int64_t C_in, int64_t C_f,
-                           int64_t L, int64_t Lout, int64_t off, int64_t N, void* ws, size_t ws_bytes, uint32_t* rowmax,
-                           int* rowmax_written, void* stream) {
-    if (!rowmax || !rowmax_written) return GFX_EINVAL;
-    *rowmax_written = 0;
-    return fftconv_sched(x, xmap, Hs, h_rows, part_len, y, ymap, xcopy, cmap, R, C_in, C_f, L, Lout, off, N, ws, ws_bytes,
-                         GFX_SCHED_AUTO, stream, rowmax, rowmax_written);
+                         schedule, stream, rowmax, rowmax_written);
 }
 
 static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len, float* y,

@@ -653,48 +653,26 @@ int gfx_istft_basis_f32(const float* window, float* basis, int64_t n_fft, void* 
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
-size_t gfx_stft_reverb_workspace_bytes(int64_t R, int64_t n_fft, int64_t num_frames) {
-    if (R <= 0 || n_fft <= 0 || num_frames <= 0) return 0;
+size_t gfx_stft_reverb_workspace_bytes(int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
+                                       int schedule) {
+    if (R <= 0 || ir_len <= 0 || n_fft <= 0 || num_frames <= 0) return 0;
+    if (n_fft == 384 && hop == 192 && schedule != GFX_ISTFT_GEMM)   // the FFT form: one energy partial per workgroup
+        return (size_t)R * (size_t)(((ir_len + 191) / 192 + 14) / 15) * sizeof(float);
     // the frames, then one energy partial per 256 impulse-response samples and row (ir_len < num_frames * hop <= num_frames * n_fft)
     return ((size_t)R * 2 * num_frames * n_fft + (size_t)R * ((num_frames * n_fft + 255) / 256)) * sizeof(float);
 }
 
-size_t gfx_stft_reverb_workspace_bytes_sched(int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
-                                             int schedule) {
-    if (R <= 0 || ir_len <= 0 || n_fft <= 0 || num_frames <= 0) return 0;
-    if (n_fft == 384 && hop == 192 && schedule != GFX_ISTFT_GEMM)   // the FFT form: one energy partial per workgroup
-        return (size_t)R * (size_t)(((ir_len + 191) / 192 + 14) / 15) * sizeof(float);
-    return gfx_stft_reverb_workspace_bytes(R, n_fft, num_frames);
-}
-
-int gfx_stft_reverb_ir_f32(const float* noise_stft, const float* init_log_magnitude, const float* delta_log_magnitude,
-                           const float* gain_env_log_magnitude, const float* window, const float* basis, float* ir,
-                           float* row_gain, int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
-                           int ms_to_lr, void* ws, size_t ws_bytes, void* stream) {
-    return gfx_stft_reverb_ir_ex_f32(noise_stft, 1, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, window,
-                                     basis, ir, row_gain, R, ir_len, n_fft, hop, num_frames, ms_to_lr, ws, ws_bytes, stream);
-}
-
-int gfx_stft_reverb_ir_ex_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
-                              const float* delta_log_magnitude, const float* gain_env_log_magnitude, const float* window,
-                              const float* basis, float* ir, float* row_gain, int64_t R, int64_t ir_len, int64_t n_fft,
-                              int64_t hop, int64_t num_frames, int ms_to_lr, void* ws, size_t ws_bytes, void* stream) {
-    return gfx_stft_reverb_ir_sched_f32(noise_stft, noise_rows, init_log_magnitude, delta_log_magnitude,
-                                        gain_env_log_magnitude, window, basis, ir, row_gain, R, ir_len, n_fft, hop,
-                                        num_frames, ms_to_lr, ws, ws_bytes, GFX_ISTFT_AUTO, stream);
-}
-
-int gfx_stft_reverb_ir_sched_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
-                                 const float* delta_log_magnitude, const float* gain_env_log_magnitude,
-                                 const float* window, const float* basis, float* ir, float* row_gain, int64_t R,
-                                 int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames, int ms_to_lr, void* ws,
-                                 size_t ws_bytes, int schedule, void* stream) {
+int gfx_stft_reverb_ir_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
+                           const float* delta_log_magnitude, const float* gain_env_log_magnitude,
+                           const float* window, const float* basis, float* ir, float* row_gain, int64_t R,
+                           int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames, int ms_to_lr, void* ws,
+                           size_t ws_bytes, int schedule, void* stream) {
     if (noise_rows != 1 && noise_rows != R) return GFX_EINVAL;
     if (!noise_stft || !init_log_magnitude || !delta_log_magnitude || !window || !basis || !ir || !row_gain)
         return GFX_EINVAL;
     if (R <= 0 || ir_len <= 0 || n_fft < 2 || (n_fft & 1) || hop < 1 || hop > n_fft || num_frames < 1) return GFX_EINVAL;
     if (R * 2 > 65535) return GFX_EINVAL;
-    const size_t need = gfx_stft_reverb_workspace_bytes_sched(R, ir_len, n_fft, hop, num_frames, schedule);
+    const size_t need = gfx_stft_reverb_workspace_bytes(R, ir_len, n_fft, hop, num_frames, schedule);
     if (!ws || ws_bytes < need) return GFX_ENOSPC;
     IstftArgs a;
     a.R = R;

@@ -145,9 +145,9 @@ def fir_spectrum(h, gain=None, gain_div=1, part_len=0):
     _require_gpu(h, gain)
     h = h.contiguous()
     RCf, N = h.shape
-    Hs = torch.empty(lib().gfx_fir_spectrum_bytes_ex(RCf, N, part_len), dtype=torch.uint8, device=h.device)
-    check(lib().gfx_fir_spectrum_ex_f32(_ptr(h), _ptr(gain), gain_div, _ptr(Hs), RCf, N, part_len, _stream()),
-          "gfx_fir_spectrum_ex_f32")
+    Hs = torch.empty(lib().gfx_fir_spectrum_bytes(RCf, N, part_len), dtype=torch.uint8, device=h.device)
+    check(lib().gfx_fir_spectrum_f32(_ptr(h), _ptr(gain), gain_div, _ptr(Hs), RCf, N, part_len, _stream()),
+          "gfx_fir_spectrum_f32")
     return Hs
 
 
@@ -157,7 +157,7 @@ def fir_spectrum_reversed(x, part_len=0):
     ``fir_spectrum(x.flip(-1).reshape(R * C, L), part_len=part_len)`` returns, without the flipped copy."""
     _require_gpu(x)
     xmap, R, C, L = rowmap(x)
-    Hs = torch.empty(lib().gfx_fir_spectrum_bytes_ex(R * C, L, part_len), dtype=torch.uint8, device=x.device)
+    Hs = torch.empty(lib().gfx_fir_spectrum_bytes(R * C, L, part_len), dtype=torch.uint8, device=x.device)
     check(lib().gfx_fir_spectrum_rev_f32(_ptr(x), xmap, R, C, L, part_len, _ptr(Hs), _stream()),
           "gfx_fir_spectrum_rev_f32")
     return Hs
@@ -180,7 +180,7 @@ def fir_grad(x, g, N, off):
 
 
 def fftconv_can_tee(Cin, Cf, L, Lout, off, N):
-    """Whether :func:`fftconv` can also write a copy of its input (gfx_fftconv_tee_f32's conditions)."""
+    """Whether :func:`fftconv` can also write a copy of its input (the conditions of gfx_fftconv_f32's xcopy)."""
     return off == 0 and Lout >= L and Cin >= Cf and lib().gfx_fftconv_nparts(N) == 1
 
 
@@ -205,10 +205,10 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
     ``h_rows``: number of filters in ``Hs`` when fewer than the signal rows (rows are batch-major, so
     ``h_rows = nodes`` shares one filter per node across the batch); default: one filter per row.
     ``schedule``: "auto" (the library picks), "tile" (one tile per workgroup, compiler-scheduled) or "pipe" (the
-    hand-scheduled persistent kernel, N <= 8193); see gfx_fftconv_sched_f32.
+    hand-scheduled persistent kernel, N <= 8193); see gfx_fftconv_f32.
     ``rowmax`` (with schedule "auto"): a dict that receives ``rowmax["words"]`` -- an int32 tensor of R * max(C, Cf) words,
     the bits of max |y| of every output row-channel -- when the kernel that ran leaves them as a by-product
-    (gfx_fftconv_rowmax_f32: the compiler-built tile kernels, one partition or many); untouched otherwise.  For odd_alias(rowmax=).
+    (gfx_fftconv_f32's rowmax: the compiler-built tile kernels, one partition or many); untouched otherwise.  For odd_alias(rowmax=).
     ``zi`` / ``return_state``: block-wise processing, see :func:`fftconv_state` (causal only: ``off`` = 0, ``Lout`` = L; no
     ``tee``, ``rowmax`` or ``part_len``); with ``return_state`` the result is ``(y, zf)``.
     """
@@ -242,41 +242,36 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
     ymap, Ry, Cy, Ly = rowmap(out)
     if (Ry, Cy) != (R, Cout) or Ly < Lout:
         raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={Lout}")
-    if Hs.numel() != lib().gfx_fir_spectrum_bytes_ex(h_rows * Cf, N, part_len):
+    if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, part_len):
         raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
-    nbytes = lib().gfx_fftconv_workspace_bytes_ex(R, Cin, L, Lout, off, N, part_len)
+    nbytes = lib().gfx_fftconv_workspace_bytes(R, Cin, L, Lout, off, N, part_len)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
     cmap = RowMap(1, 0, 0, 0)
     if tee is not None:
         cmap, Rc, Cc, Lc = rowmap(tee)
         if (Rc, Cc, Lc) != (R, Cin, L):
             raise ValueError(f"tee shape {tuple(tee.shape)} does not match the input {tuple(x.shape)}")
-    def launch(sched):
-        return lib().gfx_fftconv_sched_f32(_ptr(x), xmap, _ptr(Hs), h_rows, part_len, _ptr(out), ymap, _ptr(tee), cmap, R, Cin,
-                                           Cf, L, Lout, off, N, _ptr(ws), nbytes, SCHEDULES[sched], _stream())
+    want_max = rowmax is not None and schedule == "auto" and FFTCONV_SCHEDULE == "auto" and ROWMAX_BYPRODUCT
+    words = torch.zeros(R * Cout, dtype=torch.int32, device=x.device) if want_max else None
+    written = ctypes.c_int(0)
 
-    if rowmax is not None and schedule == "auto" and FFTCONV_SCHEDULE == "auto" and ROWMAX_BYPRODUCT:
-        words = torch.zeros(R * Cout, dtype=torch.int32, device=x.device)
-        written = ctypes.c_int(0)
-        with _timed("fftconv", 4 * R * ((2 if tee is not None else 1) * Cin * L + Cout * Lout)) as t:
-            check(lib().gfx_fftconv_rowmax_f32(_ptr(x), xmap, _ptr(Hs), h_rows, part_len, _ptr(out), ymap, _ptr(tee), cmap, R,
-                                               Cin, Cf, L, Lout, off, N, _ptr(ws), nbytes, words.data_ptr(),
-                                               ctypes.byref(written), _stream()), "gfx_fftconv_rowmax_f32")
-            if t.rec is not None:
-                t.name = lib().gfx_fftconv_last_kernel().decode()
-        if written.value:
-            rowmax["words"] = words
-        return out
+    def launch(sched):
+        return lib().gfx_fftconv_f32(_ptr(x), xmap, _ptr(Hs), h_rows, part_len, _ptr(out), ymap, _ptr(tee), cmap, R, Cin, Cf,
+                                     L, Lout, off, N, _ptr(ws), nbytes, SCHEDULES[sched], _ptr(words),
+                                     ctypes.byref(written) if want_max else None, _stream())
+
     with _timed("fftconv", 4 * R * ((2 if tee is not None else 1) * Cin * L + Cout * Lout)) as t:
         rc = GFX_EINVAL
         if schedule == "auto" and FFTCONV_SCHEDULE == "pipe":
             rc = launch("pipe")
             if rc not in (0, GFX_EINVAL):  # only "not covered by the persistent kernel" falls back to the library's choice;
-                check(rc, "gfx_fftconv_sched_f32 (pipe)")   # a failed launch / code-object load must not be masked
+                check(rc, "gfx_fftconv_f32 (pipe)")   # a failed launch / code-object load must not be masked
         if rc != 0:
-            check(launch(schedule), "gfx_fftconv_sched_f32")
+            check(launch(schedule), "gfx_fftconv_f32")
         if t.rec is not None:             # the record is keyed by the kernel's own name, as a profile prints it
             t.name = lib().gfx_fftconv_last_kernel().decode()
+    if written.value:
+        rowmax["words"] = words
     return out
 
 
@@ -317,7 +312,7 @@ def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=Tru
     ymap, Ry, Cy, Ly = rowmap(out)
     if (Ry, Cy) != (R, Cout) or Ly < L:
         raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={L}")
-    if Hs.numel() != lib().gfx_fir_spectrum_bytes_ex(h_rows * Cf, N, 0):
+    if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, 0):
         raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
     shape = (R, Cin, N - 1)
     zi = _fir_state(zi, shape, "fftconv_state", "zi")
@@ -327,7 +322,7 @@ def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=Tru
     if zi is not None and zf is not None and _overlap(zi, zf):
         raise ValueError("fftconv_state: zf must not share memory with zi (the state is written while the history may "
                          "still be read)")
-    nbytes = lib().gfx_fftconv_workspace_bytes_ex(R, Cin, L, L, 0, N, 0)
+    nbytes = lib().gfx_fftconv_workspace_bytes(R, Cin, L, L, 0, N, 0)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
     with _timed("fftconv", 4 * R * (Cin * (L + 2 * (N - 1)) + Cout * L)) as t:
         check(lib().gfx_fftconv_state_f32(_ptr(x), xmap, _ptr(Hs), h_rows, _ptr(out), ymap, _ptr(zi), _ptr(zf), R, Cin, Cf, L,
@@ -443,7 +438,7 @@ def odd_alias_supported(P):
 # P = 8 388 607 and every adjoint take).
 ALIAS_PAIRS = os.environ.get("GRAFX_ALIAS_PAIRS", "1") != "0"
 ALIAS_ROWS_PER_CHUNK = int(os.environ.get("GRAFX_ALIAS_ROWS", "1024"))   # rows of one launch chain (and ALIAS_WS_CAP bytes at most)
-ALIAS_ONE_ROW_MAX = 16383    # rows one call of gfx_odd_alias_f32 / _rows_f32 / _adjoint_f32 accepts (csrc/czt.hip: czt_alias)
+ALIAS_ONE_ROW_MAX = 16383    # rows one call of gfx_odd_alias_f32 / _adjoint_f32 accepts (csrc/czt.hip: czt_alias)
 
 
 def _alias_fns(precise, pairs=False):
@@ -545,47 +540,29 @@ def odd_alias(z, lo=0, length=None, rows_per_chunk=None, precise=False, out=None
         rowmax = None
     if relu and not (pairs and precise and out is None):
         raise ValueError("odd_alias: relu is fused into the two-rows-per-transform double-precision form only")
-    if out is not None:
+    into, omap, Co = out is not None, None, 0
+    if into:
         # ``out``: a (R, C, length) tensor or a strided (B, n, C, length) view whose rows, channels flattened, are z's
-        # rows: the last column pass writes them in place (gfx_odd_alias_rows_f32; float transforms only)
+        # rows: the last column pass writes them in place (the entries' ymap; float transforms only)
         _require_gpu(out)
-        omap, Ro, Co, Lo = rowmap(out)
+        rmap, Ro, Co, Lo = rowmap(out)
         if precise or Ro * Co != rows or Lo != length:
             raise ValueError(f"odd_alias: out {tuple(out.shape)} does not take {rows} rows of {length} samples")
-        name = ("czt_pair_in_kernel+czt_rows_kernel+czt_pair_mid_kernel+czt_pair_out_kernel<float>" if pairs
-                else "czt_cols_fwd_kernel+czt_rows_kernel+czt_cols_inv_kernel<float>")
-        rows_fn = lib().gfx_odd_alias_pair_rows_f32 if pairs else lib().gfx_odd_alias_rows_f32
-        for i in range(0, rows, chunk):
-            n = min(chunk, rows - i)
-            with _timed(name, 4 * n * (P + length)):
-                if rowmax is not None:
-                    check(lib().gfx_odd_alias_pair_rows_max_f32(_ptr(flat[i : i + n]), _ptr(out), omap, Co, i, lo, length, n, P,
-                                                                _ptr(plan), _ptr(ws), ws.numel(), rowmax[i : i + n].data_ptr(),
-                                                                _stream()), "gfx_odd_alias_pair_rows_max_f32")
-                else:
-                    check(rows_fn(_ptr(flat[i : i + n]), _ptr(out), omap, Co, i, lo, length, n, P, _ptr(plan), _ptr(ws),
-                                  ws.numel(), _stream()), tag + "rows_f32")
-        return out
-    out = torch.empty((rows, length), dtype=torch.float32, device=z.device)
+        omap = ctypes.byref(rmap)
+    else:
+        out = torch.empty((rows, length), dtype=torch.float32, device=z.device)
     # one record per chunk: the column / tile / column passes of the two chirp-z transforms (czt.hip), read z + write y
     name = (("czt_pair_in_kernel+czt_rows_kernel+czt_pair_mid_kernel+czt_pair_out_kernel" if pairs
              else "czt_cols_fwd_kernel+czt_rows_kernel+czt_cols_inv_kernel") + ("<double>" if precise else "<float>"))
     for i in range(0, rows, chunk):
         n = min(chunk, rows - i)
+        rm = None if rowmax is None else rowmax[i : i + n].data_ptr()
+        # what follows the workspace in the entry's list: the double forms take no row map, the one-row forms no maxima
+        tail = ((rm, int(relu)) if pairs else ()) if precise else (omap, Co, i) + ((rm,) if pairs else ())
         with _timed(name, 4 * n * (P + length)):
-            if precise and pairs and (rowmax is not None or relu):
-                check(lib().gfx_odd_alias_pair_precise_max_f32(_ptr(flat[i : i + n]), _ptr(out[i : i + n]), length, lo, length, n, P,
-                                                               _ptr(plan), _ptr(ws), ws.numel(),
-                                                               None if rowmax is None else rowmax[i : i + n].data_ptr(),
-                                                               int(relu), _stream()), "gfx_odd_alias_pair_precise_max_f32")
-            elif rowmax is not None:
-                check(lib().gfx_odd_alias_pair_max_f32(_ptr(flat[i : i + n]), _ptr(out[i : i + n]), length, lo, length, n, P,
-                                                       _ptr(plan), _ptr(ws), ws.numel(), rowmax[i : i + n].data_ptr(), _stream()),
-                      "gfx_odd_alias_pair_max_f32")
-            else:
-                check(fwd(_ptr(flat[i : i + n]), _ptr(out[i : i + n]), length, lo, length, n, P, _ptr(plan), _ptr(ws), ws.numel(),
-                          _stream()), tag + "f32")
-    return out.view(*z.shape[:-1], length)
+            check(fwd(_ptr(flat[i : i + n]), _ptr(out if into else out[i : i + n]), length, lo, length, n, P, _ptr(plan),
+                      _ptr(ws), ws.numel(), *tail, _stream()), tag + "f32")
+    return out if into else out.view(*z.shape[:-1], length)
 
 
 @_on_device
@@ -728,11 +705,11 @@ def _rowvec(p, R):
 
 # Default schedule of dynamics_fused: "oneshot" hands the library a workspace, with which the smoothed configuration runs
 # as dependency-free 1024-sample tiles for every row whose smoother memory is short (decided per row on the device,
-# gfx_dynamics_fused_ws_f32) and as one workgroup per row for the others; "rows" forces one workgroup per row.
+# gfx_dynamics_fused_f32) and as one workgroup per row for the others; "rows" forces one workgroup per row.
 MIX_FUSION = True          # dynamics stages take the routing sum that follows them (see dynamics_fused(mix=))
 DYN_SCHEDULE = "oneshot"
-# the compressor backward without a kept scan rebuilds it inside its tiles (gfx_dynamics_bwd_rescan_ws_f32); False: a pass
-# over every row writes it out first (gfx_dynamics_bwd_f32, rounds 2-5)
+# the compressor backward without a kept scan rebuilds it inside its tiles (gfx_dynamics_bwd_f32 with a workspace); False: a
+# pass over every row writes it out first (the same entry without one, rounds 2-5)
 DYN_BWD_RESCAN = True
 # rows with a long smoother memory stay on the tile grid (gfx_dynamics_ws_bytes_ex); False: round 4
 DYN_LOOKBACK = True
@@ -817,9 +794,9 @@ def dynamics_fused(x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir
                 n_ex = 0 if ex is None else ex.shape[0]
                 n_pre = mix.get("n_pre", 0)
                 # mix["skip_rows"]: nobody but these sums reads the stage's rows (an output-only render): do not store them
-                rc = lib().gfx_dynamics_fused_mix_flags_f32(*args[:-1], _ptr(sched), n, mix["n_acc"], _ptr(mo), mo.stride(0),
-                                                            mo.stride(1), mo.stride(2) if C == 2 else 0, _ptr(ex), n_pre,
-                                                            n_ex - n_pre, 1 if mix.get("skip_rows") else 0, _stream())
+                rc = lib().gfx_dynamics_fused_mix_f32(*args[:-1], _ptr(sched), n, mix["n_acc"], _ptr(mo), mo.stride(0),
+                                                      mo.stride(1), mo.stride(2) if C == 2 else 0, _ptr(ex), n_pre,
+                                                      n_ex - n_pre, 1 if mix.get("skip_rows") else 0, _stream())
                 if rc == 0 and t.rec is not None:    # keyed by the kernel's own name, as a profile prints it
                     t.name = lib().gfx_dynamics_last_kernel().decode()
             if rc == 0:
@@ -828,7 +805,7 @@ def dynamics_fused(x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir
             if rc != -1:   # GFX_EINVAL: not a configuration of the fused kernel
                 check(rc, "gfx_dynamics_fused_mix_f32")
     with _timed("dyn_fused_kernel", 8 * R * C * L + (4 * R * L if u1_out is not None else 0)) as t:
-        check(lib().gfx_dynamics_fused_ws_f32(*args), "gfx_dynamics_fused_ws_f32")
+        check(lib().gfx_dynamics_fused_f32(*args), "gfx_dynamics_fused_f32")
         if t.rec is not None:
             t.name = lib().gfx_dynamics_last_kernel().decode()
     return out
@@ -872,7 +849,8 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     gp = torch.empty((R, 3), dtype=torch.float32, device=x.device)
     da = torch.empty(R, dtype=torch.float32, device=x.device) if pole else None
     pin = _Pin()
-    # three paths: the kept scan (with or without the tiles' workspace), the rescan inside the tiles, the plain two passes
+    # the kept scan (with or without the tiles' workspace), or a scratch the scan is rebuilt into (inside the tiles with a
+    # workspace, by a pass of its own over every row without)
     kept = u1 is not None
     if kept:
         _require_gpu(u1)
@@ -880,19 +858,12 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
         need_ws = (DYN_SCHEDULE if schedule is None else schedule) == "oneshot"   # one-shot tiles for the short-memory rows
     else:
         u1 = torch.empty((R, L), dtype=torch.float32, device=x.device)
-        need_ws = rescan = bool(DYN_BWD_RESCAN if rescan is None else rescan)   # (the rescan entry always takes a workspace)
+        need_ws = bool(DYN_BWD_RESCAN if rescan is None else rescan)
     ws = torch.empty(lib().gfx_dynamics_bwd_ws_bytes(R, L), dtype=torch.uint8, device=x.device) if need_ws else None
-    args = (_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)), pin(_rowvec(log_ratio, R)),
-            pin(_rowvec(log_knee, R)), pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee], int(gate), _ptr(gx),
-            rowmap(gx)[0], _ptr(gp))
-    if kept:
-        check(lib().gfx_dynamics_bwd_u1_ws_f32(*args, pin(u1), _ptr(da), _ptr(ws), 0 if ws is None else ws.numel(),
-                                               _stream()), "gfx_dynamics_bwd_u1_ws_f32")
-    elif rescan:
-        check(lib().gfx_dynamics_bwd_rescan_ws_f32(*args, _ptr(u1), _ptr(da), _ptr(ws), ws.numel(), _stream()),
-              "gfx_dynamics_bwd_rescan_ws_f32")
-    else:
-        check(lib().gfx_dynamics_bwd_f32(*args, None, _ptr(u1), _ptr(da), _stream()), "gfx_dynamics_bwd_f32")
+    check(lib().gfx_dynamics_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)), pin(_rowvec(log_ratio, R)),
+                                     pin(_rowvec(log_knee, R)), pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee],
+                                     int(gate), _ptr(gx), rowmap(gx)[0], _ptr(gp), pin(u1), 0 if kept else 1, _ptr(da),
+                                     _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "gfx_dynamics_bwd_f32")
     return gx, gp, da
 
 
@@ -973,7 +944,7 @@ def onepole_fir(z_alpha, iir_len):
     return h
 
 
-BALLISTICS_SCHEDULE = "chunks"   # "chunks": rows cut into verified chunks (gfx_ballistics_ws_f32); "rows": whole rows only
+BALLISTICS_SCHEDULE = "chunks"   # "chunks": rows cut into verified chunks (gfx_ballistics_f32 with a workspace); "rows": whole rows only
 
 
 def _overlap(a, b):
@@ -1038,13 +1009,8 @@ def ballistics(u, z_alpha, coefficients=False, schedule=None, flags=None, zi=Non
     zi = _ballistics_state(zi, R, "ballistics")
     zf = torch.empty(R, dtype=torch.float32, device=u.device) if return_state else None
     with _timed("ballistics_walk_kernel", 8 * R * L):
-        if zi is None and zf is None:
-            check(lib().gfx_ballistics_ws_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(y), R, L, _ptr(ws),
-                                              0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_ws_f32")
-        else:
-            check(lib().gfx_ballistics_state_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(y), R, L,
-                                                 _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-                  "gfx_ballistics_state_f32")
+        check(lib().gfx_ballistics_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(y), R, L, _ptr(ws),
+                                       0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_f32")
     if flags is not None and ws is not None:
         flags.append(ws.view(torch.int32))
     return (y, zf) if return_state else y
@@ -1078,17 +1044,10 @@ def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, ga
     zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     pin = _Pin()
     with _timed("ballistics_walk_kernel", 8 * R * C * L):
-        if zi is None and zf is None:
-            check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
-                                                    pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P, R, C, L,
-                                                    KNEES[knee], int(gate), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-                  "gfx_dynamics_ballistics_f32")
-        else:
-            check(lib().gfx_dynamics_ballistics_state_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
-                                                          pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P,
-                                                          R, C, L, KNEES[knee], int(gate), _ptr(zi), _ptr(zf), _ptr(ws),
-                                                          0 if ws is None else ws.numel(), _stream()),
-                  "gfx_dynamics_ballistics_state_f32")
+        check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
+                                                pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P, R, C, L,
+                                                KNEES[knee], int(gate), _ptr(zi), _ptr(zf), _ptr(ws),
+                                                0 if ws is None else ws.numel(), _stream()), "gfx_dynamics_ballistics_f32")
     return (out, zf) if return_state else out
 
 
@@ -1110,21 +1069,17 @@ def ballistics_energy(x, z_alpha, coefficients=False, schedule=None, zi=None, re
     zi = _ballistics_state(zi, R, "ballistics_energy")
     zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     with _timed("ballistics_walk_kernel", 4 * R * (C + 1) * L):
-        if zi is None and zf is None:
-            check(lib().gfx_ballistics_energy_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(env), R, L, _ptr(ws),
-                                                  0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_energy_f32")
-        else:
-            check(lib().gfx_ballistics_energy_state_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf),
-                                                        _ptr(env), R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-                  "gfx_ballistics_energy_state_f32")
+        check(lib().gfx_ballistics_energy_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(env),
+                                              R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+              "gfx_ballistics_energy_f32")
     return (env, zf) if return_state else env
 
 
 @_on_device
 def ballistics_bwd(x, y, g, z_alpha, schedule="chunks", zi=None):
     """Adjoint of :func:`ballistics`: -> (dL/dx (R,L), dL/dz_alpha (R,2)).  ``schedule``: "chunks" (rows cut into chunks
-    with a 2048-sample warm-up, gfx_ballistics_bwd_ws_f32) or "rows" (every row walked whole by one lane).  ``zi`` (R,): the
-    state the forward entered with; -> (gx, gz, dL/dzi (R,)) (gfx_ballistics_bwd_state_f32).  A cotangent of the final state
+    with a 2048-sample warm-up, gfx_ballistics_bwd_f32 with a workspace) or "rows" (every row walked whole by one lane).
+    ``zi`` (R,): the state the forward entered with; -> (gx, gz, dL/dzi (R,)).  A cotangent of the final state
     is a cotangent of y[:, L-1]: add it to ``g`` there."""
     _require_gpu(x, y, g, z_alpha)
     x, y, g, z_alpha = x.contiguous(), y.contiguous(), g.contiguous(), z_alpha.contiguous()
@@ -1133,24 +1088,14 @@ def ballistics_bwd(x, y, g, z_alpha, schedule="chunks", zi=None):
     _expect(g, (R, L), "ballistics_bwd: g")
     _expect(z_alpha, (R, 2), "ballistics_bwd: z_alpha")
     gx, gz = torch.empty_like(x), torch.empty((R, 2), dtype=torch.float32, device=x.device)
-    if zi is not None:
-        zi = _ballistics_state(zi, R, "ballistics_bwd")
-        gzi = torch.empty(R, dtype=torch.float32, device=x.device)
-        ws = None
-        if schedule != "rows":
-            ws = torch.empty(max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4), dtype=torch.uint8, device=x.device)
-        check(lib().gfx_ballistics_bwd_state_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(zi), _ptr(gx), _ptr(gz), _ptr(gzi),
-                                                 R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-              "gfx_ballistics_bwd_state_f32")
-        return gx, gz, gzi
-    if schedule == "rows":
-        check(lib().gfx_ballistics_bwd_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(gx), _ptr(gz), R, L, _stream()),
-              "gfx_ballistics_bwd_f32")
-        return gx, gz
-    ws = torch.empty(max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4), dtype=torch.uint8, device=x.device)
-    check(lib().gfx_ballistics_bwd_ws_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(gx), _ptr(gz), R, L, _ptr(ws),
-                                          ws.numel(), _stream()), "gfx_ballistics_bwd_ws_f32")
-    return gx, gz
+    zi = _ballistics_state(zi, R, "ballistics_bwd")
+    gzi = None if zi is None else torch.empty(R, dtype=torch.float32, device=x.device)
+    ws = None
+    if schedule != "rows":
+        ws = torch.empty(max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4), dtype=torch.uint8, device=x.device)
+    check(lib().gfx_ballistics_bwd_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(zi), _ptr(gx), _ptr(gz), _ptr(gzi), R, L,
+                                       _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_bwd_f32")
+    return (gx, gz) if zi is None else (gx, gz, gzi)
 
 
 @_on_device
@@ -1434,16 +1379,16 @@ def stft_reverb_ir(noise_stft, init_lm, delta_lm, gain_env, window, basis, ir_le
     ROWS = 32767                                        # rows per launch (the kernels' grids index rows in 16 bits)
     for r0 in range(0, R, ROWS):
         n = min(ROWS, R - r0)
-        nbytes = lib().gfx_stft_reverb_workspace_bytes_sched(n, ir_len, n_fft, hop, T, sched)
+        nbytes = lib().gfx_stft_reverb_workspace_bytes(n, ir_len, n_fft, hop, T, sched)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=init_lm.device)
         pin = _Pin()
         check(
-            lib().gfx_stft_reverb_ir_sched_f32(_ptr(nz[r0:r0 + n] if noise_rows != 1 else nz), noise_rows if noise_rows == 1 else n,
-                                               pin(init_lm[r0:r0 + n]), pin(delta_lm[r0:r0 + n]),
-                                               pin(None if gain_env is None else gain_env[r0:r0 + n]), pin(window), pin(basis),
-                                               _ptr(ir[r0:r0 + n]), _ptr(row_gain[r0:r0 + n]), n, ir_len, n_fft, hop, T,
-                                               int(ms_to_lr), _ptr(ws), nbytes, sched, _stream()),
-            "gfx_stft_reverb_ir_sched_f32",
+            lib().gfx_stft_reverb_ir_f32(_ptr(nz[r0:r0 + n] if noise_rows != 1 else nz), noise_rows if noise_rows == 1 else n,
+                                         pin(init_lm[r0:r0 + n]), pin(delta_lm[r0:r0 + n]),
+                                         pin(None if gain_env is None else gain_env[r0:r0 + n]), pin(window), pin(basis),
+                                         _ptr(ir[r0:r0 + n]), _ptr(row_gain[r0:r0 + n]), n, ir_len, n_fft, hop, T,
+                                         int(ms_to_lr), _ptr(ws), nbytes, sched, _stream()),
+            "gfx_stft_reverb_ir_f32",
         )
     return ir, row_gain
 

@@ -47,7 +47,7 @@ class TruncatedOnePoleIIRFilter(nn.Module):
         compressors' envelope when this smoother's convolve() aliases (upstream's default tap counts, dynamics.py:390 +
         envelope.py:34-49) in three passes instead of six -- the energy is formed inside the scan
         (gfx_onepole_energy_f32), which also leaves the rows' maxima the aliasing scales its pairs by, and the relu rides
-        on the aliasing's last pass (gfx_odd_alias_pair_precise_max_f32)."""
+        on the aliasing's last pass (gfx_odd_alias_pair_precise_f32)."""
         L = signal.shape[-1]
         if not reference_aliases(L, self.iir_len, self.flashfftconv):
             return ops.onepole_energy(signal, z_alpha, self.iir_len, Lout=L, relu=True)

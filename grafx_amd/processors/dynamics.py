@@ -174,7 +174,7 @@ class _Dynamics(BufferIO, nn.Module):
             if _out is not None:
                 _out.copy_(y.view(_out.shape))
                 y = _out
-        elif not post:   # the one-pass kernel (gfx_dynamics_ballistics_state_f32)
+        elif not post:   # the one-pass kernel (gfx_dynamics_ballistics_f32)
             y, zf = ops.dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha_pre, self.knee, self._gate, out=_out,
                                             zi=s_pre, return_state=True)
             out.append(zf)

@@ -11,7 +11,7 @@ from .stage import StageArguments, stage_input
 
 # Training forward: keep the dynamics stages' smoother scan (R x L floats per stage) for their backward.  Rounds 2-5 kept it
 # (the alternative was a pass of its own over every row); since round 6 the backward tiles rebuild the scan from the
-# samples they read anyway (gfx_dynamics_bwd_rescan_ws_f32), which takes 4 bytes per sample out of the forward AND the
+# samples they read anyway (gfx_dynamics_bwd_f32 with a scratch u1), which takes 4 bytes per sample out of the forward AND the
 # backward kernel and 4.8 GB at 256 graphs out of the step's peak: off by default (True: round 5's path).
 KEEP_SMOOTHER_SCAN = False
 # Where the parameter-only work of the later stages (filter design, the reverb's impulse response and spectra) runs:

@@ -54,7 +54,10 @@ typedef struct {
     int64_t stride_ch;
 } gfx_rowmap_t;
 
-/* library / device sanity: returns the ABI version (>0); fills *n_cu if non-null (host ptr). */
+/* library / device sanity: gfx_abi_version returns GFX_ABI_VERSION of the header the library was built from -- entries keep
+ * their names when their argument lists change, so a binding compares it before the first call (version 1 had one entry per
+ * argument list: INTEGRATION.md maps its names to these); gfx_device_info fills *n_cu, *lds_bytes if non-null (host ptrs). */
+#define GFX_ABI_VERSION 2
 int gfx_abi_version(void);
 int gfx_device_info(int* n_cu, size_t* lds_bytes);
 
@@ -74,43 +77,21 @@ int gfx_device_info(int* n_cu, size_t* lds_bytes);
  * tile spectra `Hs` (private layout, gfx_fir_spectrum_bytes bytes).  `gain` (nullable) scales
  * row-channel rc by gain[rc / gain_div].
  * Step 2: gfx_fftconv_f32 streams x through the tiles.
- */
-int64_t gfx_fftconv_nparts(int64_t N);
-size_t gfx_fir_spectrum_bytes(int64_t RCf, int64_t N);
-size_t gfx_fftconv_workspace_bytes(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N);
-int gfx_fir_spectrum_f32(const float* h, const float* gain, int64_t gain_div, void* Hs,
-                         int64_t RCf, int64_t N, void* stream);
-int gfx_fftconv_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, float* y, gfx_rowmap_t ymap,
-                    int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                    void* ws, size_t ws_bytes, void* stream);
-/* Same, and additionally copies the input rows to `xcopy` (rows addressed by `cmap`, same R x C_in x L) from
- * the registers that already hold them.  render_grafx keeps every node's signal in one buffer
- * (render/graph.py:104-106: `signal_buffer[:, :num_sources] = input_signals`); when the first stage is a
- * convolution this folds that copy into the stage's kernel.  Only for the causal single-partition case
- * (off == 0, Lout >= L -- the full-length convolution the odd-length aliasing starts from included --, C_in == max(C_in, C_f),
- * N <= 8193); anything else returns GFX_EINVAL. */
-int gfx_fftconv_tee_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, float* y, gfx_rowmap_t ymap,
-                        float* xcopy, gfx_rowmap_t cmap,
-                        int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                        void* ws, size_t ws_bytes, void* stream);
-
-/* The general form of the two above.  `h_rows` <= R: row r convolves with filter (r % h_rows) -- rows are
- * batch-major (r = b * nodes + node), so h_rows = nodes shares one filter per node across the batch, which is
- * what render_grafx's 4-D path means by un-batched parameters (render/graph.py:68-75 expands them B times;
- * here the spectra are built once per node and every batch row reads them).  xcopy may be null (no tee).
  * `part_len`: 0 for the default filter partitioning, or the value of gfx_fftconv_part_len(N, Lout) -- longer
  * partitions (fewer of them, fewer signal windows) for "long filter, short output" problems such as the filter
- * gradient of a training step (N = signal length taps, Lout = filter taps); the spectra must then come from
- * gfx_fir_spectrum_ex_f32 with the same part_len, sizes from the *_ex queries. */
+ * gradient of a training step (N = signal length taps, Lout = filter taps); the spectra, both size queries and the
+ * convolution must then be given the same part_len.
+ */
+int64_t gfx_fftconv_nparts(int64_t N);
 int64_t gfx_fftconv_part_len(int64_t N, int64_t Lout);
-size_t gfx_fir_spectrum_bytes_ex(int64_t RCf, int64_t N, int64_t part_len);
-size_t gfx_fftconv_workspace_bytes_ex(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                                      int64_t part_len);
-int gfx_fir_spectrum_ex_f32(const float* h, const float* gain, int64_t gain_div, void* Hs,
-                            int64_t RCf, int64_t N, int64_t part_len, void* stream);
+size_t gfx_fir_spectrum_bytes(int64_t RCf, int64_t N, int64_t part_len);
+size_t gfx_fftconv_workspace_bytes(int64_t R, int64_t C_in, int64_t L, int64_t Lout, int64_t off, int64_t N,
+                                   int64_t part_len);
+int gfx_fir_spectrum_f32(const float* h, const float* gain, int64_t gain_div, void* Hs,
+                         int64_t RCf, int64_t N, int64_t part_len, void* stream);
 /* Spectra of the time-reversed signal rows: filter (r, c) has the L taps x[r, c, L-1-k], read in place through
  * `xmap` -- the "filter" of the filter-gradient correlation (autograd of convolve(): grad_h[k] = sum_n g[n] x[n+off-k])
- * without materialising x.flip(-1).  Buffer size: gfx_fir_spectrum_bytes_ex(R * C, L, part_len). */
+ * without materialising x.flip(-1).  Buffer size: gfx_fir_spectrum_bytes(R * C, L, part_len). */
 int gfx_fir_spectrum_rev_f32(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, int64_t part_len,
                              void* Hs, void* stream);
 /* Filter gradient of a short-filter convolve() (autograd of core/convolution.py:119-134), N <= 8193 taps:
@@ -118,41 +99,43 @@ int gfx_fir_spectrum_rev_f32(const float* x, gfx_rowmap_t xmap, int64_t R, int64
  * (channels broadcast 1 <-> 2; gh is (R, max(C_x, C_g), N) contiguous).  One pass over x and g, no workspace. */
 int gfx_fir_grad_f32(const float* x, gfx_rowmap_t xmap, const float* g, gfx_rowmap_t gmap, float* gh,
                      int64_t R, int64_t C_x, int64_t C_g, int64_t L, int64_t Lg, int64_t N, int64_t off, void* stream);
-int gfx_fftconv_ex_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len,
-                       float* y, gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap,
-                       int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                       void* ws, size_t ws_bytes, void* stream);
 
-/* gfx_fftconv_ex_f32 with an explicit kernel schedule for filters of N <= 8193 taps (same results to rounding):
+/* The convolution.  `h_rows` <= R: row r convolves with filter (r % h_rows) -- rows are batch-major
+ * (r = b * nodes + node), so h_rows = nodes shares one filter per node across the batch, which is what render_grafx's
+ * 4-D path means by un-batched parameters (render/graph.py:68-75 expands them B times; here the spectra are built once
+ * per node and every batch row reads them); h_rows = R is one filter per row.
+ * `xcopy` (nullable: no tee) additionally receives a copy of the input rows (rows addressed by `cmap`, same
+ * R x C_in x L) from the registers that already hold them.  render_grafx keeps every node's signal in one buffer
+ * (render/graph.py:104-106: `signal_buffer[:, :num_sources] = input_signals`); when the first stage is a convolution
+ * this folds that copy into the stage's kernel.  Only for the causal single-partition case (off == 0, Lout >= L -- the
+ * full-length convolution the odd-length aliasing starts from included --, C_in == max(C_in, C_f), N <= 8193); anything
+ * else returns GFX_EINVAL.
+ * `schedule`, for filters of N <= 8193 taps (same results to rounding):
  *   GFX_SCHED_TILE  one 16384-sample tile per 256-thread workgroup (fftconv1_kernel, compiler-scheduled).
  *   GFX_SCHED_PIPE  the hand-scheduled persistent form of the same tile (generated gfx950 assembly, explicit register
  *                   allocation: the next tile's window, the filter spectrum and the output stores are interleaved
  *                   with the arithmetic of the running tile).  GFX_EINVAL where it does not apply.
- *   GFX_SCHED_AUTO  what gfx_fftconv_f32 / _tee_f32 / _ex_f32 use: the faster of the two for the shape at hand.
+ *   GFX_SCHED_AUTO  the faster of the two for the shape at hand.
  * For longer filters (partitioned convolution: xspec_kernel + a product kernel) GFX_SCHED_TILE selects one output tile per
  * 256-thread workgroup (macinv_kernel) and GFX_SCHED_AUTO two consecutive ones per 512-thread workgroup (macinv_pair_kernel:
  * each window spectrum and filter partition fetched once per pair; equal to a few units in the last place of the largest
  * output); GFX_SCHED_PIPE: GFX_EINVAL.
- * (Round-2 experiments -- ping-pong, half-size exchanges, 512-thread tile -- live in tools/experiments/r2_schedules.) */
-#define GFX_SCHED_AUTO 0
-#define GFX_SCHED_TILE 1
-#define GFX_SCHED_PIPE 2
-int gfx_fftconv_sched_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len,
-                          float* y, gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap,
-                          int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                          void* ws, size_t ws_bytes, int schedule, void* stream);
-
-/* gfx_fftconv_sched_f32(GFX_SCHED_AUTO) that may also leave the bits of max |y| of every output row-channel in `rowmax`
+ * (Round-2 experiments -- ping-pong, half-size exchanges, 512-thread tile -- live in tools/experiments/r2_schedules.)
+ * `rowmax`, `rowmax_written`: both NULL, or both given under GFX_SCHED_AUTO (one of them alone, or another schedule with
+ * them: GFX_EINVAL).  Given, the call may leave the bits of max |y| of every output row-channel in `rowmax`
  * (R * max(C_in, C_f) words, zeroed by the caller, row-major (row, channel)): the compiler-built tile kernels (one
  * partition, and the partitioned convolution's product kernels) take them as a by-product of their stores (one atomic
  * maximum per wave and tile) and set *rowmax_written = 1; the hand-scheduled kernel and the one-output-tile form leave the
- * words alone and *rowmax_written = 0.  For the full-length convolution
- * that feeds the odd-length aliasing (core/convolution.py:119-134), whose two-rows-per-transform form scales the second
- * row of a pair by these maxima (gfx_odd_alias_pair_max_f32): the separate pass over z is not needed then. */
-int gfx_fftconv_rowmax_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len,
-                           float* y, gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap,
-                           int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
-                           void* ws, size_t ws_bytes, uint32_t* rowmax, int* rowmax_written, void* stream);
+ * words alone and *rowmax_written = 0.  For the full-length convolution that feeds the odd-length aliasing
+ * (core/convolution.py:119-134), whose two-rows-per-transform form scales the second row of a pair by these maxima
+ * (gfx_odd_alias_pair_f32's rowmax): the separate pass over z is not needed then. */
+#define GFX_SCHED_AUTO 0
+#define GFX_SCHED_TILE 1
+#define GFX_SCHED_PIPE 2
+int gfx_fftconv_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, int64_t part_len,
+                    float* y, gfx_rowmap_t ymap, float* xcopy, gfx_rowmap_t cmap,
+                    int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t Lout, int64_t off, int64_t N,
+                    void* ws, size_t ws_bytes, int schedule, uint32_t* rowmax, int* rowmax_written, void* stream);
 
 /* State across calls: one block of a streamed CAUSAL convolution (Lout = L, off = 0, default partition geometry).
  *   y[r, c, n] = sum_k h[r % h_rows, c_f, k] xx[r, c_x, n - k],  n in [0, L),  xx = zi || x
@@ -163,10 +146,10 @@ int gfx_fftconv_rowmax_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, in
  * (fftconv1_state_kernel, xspec_state_kernel, winmac_state_kernel): no concatenated copy of the signal, no allocation.
  * Blocks of a signal cut anywhere, each entering with the zf of the block before, concatenate to the linear convolution
  * of the whole.  zi and zf must not overlap: GFX_EINVAL.  N = 1 has an empty state (zi, zf ignored).  Workspace:
- * gfx_fftconv_workspace_bytes_ex(R, C_in, L, L, 0, N, 0).  schedule: GFX_SCHED_AUTO or GFX_SCHED_TILE (which product kernel
- * a partitioned convolution takes, as in gfx_fftconv_sched_f32); a call with state never takes the hand-scheduled
+ * gfx_fftconv_workspace_bytes(R, C_in, L, L, 0, N, 0).  schedule: GFX_SCHED_AUTO or GFX_SCHED_TILE (which product kernel
+ * a partitioned convolution takes, as in gfx_fftconv_f32); a call with state never takes the hand-scheduled
  * kernels: GFX_SCHED_PIPE is GFX_EINVAL.  Everything else (row maps, channel broadcast, h_rows, row-count limits) as
- * gfx_fftconv_sched_f32. */
+ * gfx_fftconv_f32. */
 int gfx_fftconv_state_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int64_t h_rows, float* y, gfx_rowmap_t ymap,
                           const float* zi, float* zf, int64_t R, int64_t C_in, int64_t C_f, int64_t L, int64_t N,
                           void* ws, size_t ws_bytes, int schedule, void* stream);
@@ -178,7 +161,7 @@ int gfx_fftconv_state_f32(const float* x, gfx_rowmap_t xmap, const void* Hs, int
 const char* gfx_fftconv_last_kernel(void);
 
 /* Short filters (N <= gfx_fir_direct_max_taps() = 512) as batched Toeplitz GEMMs on the fp32 matrix cores, taps given
- * directly (no spectra): the direct-form counterpart of gfx_fftconv_ex_f32 with the same meaning of every argument
+ * directly (no spectra): the direct-form counterpart of gfx_fftconv_f32 with the same meaning of every argument
  *   y[r, c, n] = sum_k h[r % h_rows, c_f, k] x[r, c_x, n + off - k],  n in [0, Lout),  x zero outside [0, L)
  * h is (h_rows * C_f, N) contiguous.  Replaces convolve() / FIRConvolution for short FIRs (core/convolution.py:85-134,
  * filter.py:34-39); exact fp32 (v_mfma_f32_16x16x4_f32).  MFMA-bound above ~64 taps, HBM-bound below. */
@@ -200,13 +183,13 @@ int gfx_fir_direct_f32(const float* x, gfx_rowmap_t xmap, const float* h, int64_
 size_t gfx_odd_alias_plan_bytes(int64_t P);
 size_t gfx_odd_alias_workspace_bytes(int64_t rows, int64_t P);
 int gfx_odd_alias_plan_f32(void* plan, int64_t P, void* ws, size_t ws_bytes, void* stream);
+/* `ymap` (nullable): the output rows are written straight into a signal addressed through a row map instead of y + r * ldy
+ * (ldy is ignored then): row q = row0 + r of the call is row q / C, channel q % C of `y` (a strided (B, n, C, len) view of
+ * render_grafx's signal buffer, render/core.py:80-98), so that a stage on the aliasing path needs no copy of its result
+ * into the buffer.  `z` holds `rows` rows of this call.  ymap == NULL: C and row0 are ignored. */
 int gfx_odd_alias_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                      const void* plan, void* ws, size_t ws_bytes, void* stream);
-/* The same with the output rows written straight into a signal addressed through a row map: row q = row0 + r of the call is
- * row q / C, channel q % C of `y` (a strided (B, n, C, len) view of render_grafx's signal buffer, render/core.py:80-98), so
- * that a stage on the aliasing path needs no copy of its result into the buffer.  `z` holds `rows` rows of this call. */
-int gfx_odd_alias_rows_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo, int64_t len,
-                           int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes, void* stream);
+                      const void* plan, void* ws, size_t ws_bytes, const gfx_rowmap_t* ymap, int64_t C, int64_t row0,
+                      void* stream);
 int gfx_odd_alias_adjoint_f32(const float* gy, int64_t ldg, int64_t lo, int64_t len, float* gz, int64_t rows, int64_t P,
                               const void* plan, void* ws, size_t ws_bytes, void* stream);
 /* The same maps with the transforms carried in double precision (fp32 data in and out, own plan and workspace, both
@@ -225,34 +208,25 @@ int gfx_odd_alias_precise_adjoint_f32(const float* gy, int64_t ldg, int64_t lo, 
  * A z1 + i A z2 -- 2P - 1 points per pair instead of (3P - 1) / 2 per row, a third fewer bytes through each of the same
  * passes.  Rows 2r and 2r + 1 of a call form a pair (an odd row count leaves the last row alone); the second row of a pair
  * goes through scaled by the exact power of two that brings it to the first row's binade (from max |z| of the rows: a pass
- * of the call itself, one word per row behind the workspace, or -- the _max forms -- words the producer of z left:
- * gfx_fftconv_rowmax_f32), so every row keeps an error relative to its own peak.  3 <= P <= 8 388 607 odd (2P - 1 <= 2^24 points), else the size queries return
+ * of the call itself, one word per row behind the workspace, or -- `rowmax` != NULL -- words the producer of z left:
+ * gfx_fftconv_f32's rowmax), so every row keeps an error relative to its own peak.  3 <= P <= 8 388 607 odd (2P - 1 <= 2^24 points), else the size queries return
  * 0 and the calls GFX_EINVAL (use the one-row forms above); own plan (gfx_odd_alias_pair_plan_f32, workspace of
- * gfx_odd_alias_pair_workspace_bytes(1, P)) and workspace (gfx_odd_alias_pair_workspace_bytes(rows, P)); for
- * gfx_odd_alias_pair_rows_f32 row0 must be even.  The `precise` forms carry the transforms in double (plan and
- * workspace twice the size).  Same results as the one-row forms up to rounding (tests/test_gpu_odd_alias_pair.py). */
+ * gfx_odd_alias_pair_workspace_bytes(1, P)) and workspace (gfx_odd_alias_pair_workspace_bytes(rows, P)); `ymap`, C, row0
+ * as in gfx_odd_alias_f32, and row0 must be even.  The `precise` forms carry the transforms in double (plan and
+ * workspace twice the size) and can fuse the envelope smoother's relu (core/envelope.py:48) into the last pass
+ * (`relu` != 0): no separate clamp over the rows.  Same results as the one-row forms up to rounding (tests/test_gpu_odd_alias_pair.py). */
 size_t gfx_odd_alias_pair_plan_bytes(int64_t P);
 size_t gfx_odd_alias_pair_workspace_bytes(int64_t rows, int64_t P);
 int gfx_odd_alias_pair_plan_f32(void* plan, int64_t P, void* ws, size_t ws_bytes, void* stream);
 int gfx_odd_alias_pair_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                           const void* plan, void* ws, size_t ws_bytes, void* stream);
-int gfx_odd_alias_pair_rows_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo, int64_t len,
-                                int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes, void* stream);
-int gfx_odd_alias_pair_max_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                               const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, void* stream);
-int gfx_odd_alias_pair_rows_max_f32(const float* z, float* y, gfx_rowmap_t ymap, int64_t C, int64_t row0, int64_t lo,
-                                    int64_t len, int64_t rows, int64_t P, const void* plan, void* ws, size_t ws_bytes,
-                                    const uint32_t* rowmax, void* stream);
+                           const void* plan, void* ws, size_t ws_bytes, const gfx_rowmap_t* ymap, int64_t C, int64_t row0,
+                           const uint32_t* rowmax, void* stream);
 size_t gfx_odd_alias_pair_precise_plan_bytes(int64_t P);
-/* gfx_odd_alias_pair_precise_f32 with the rows' maxima given (`rowmax`, or NULL: taken by a pass of the call) and the envelope
- * smoother's relu (core/envelope.py:48) fused into the last pass (`relu` != 0): no separate clamp over the rows. */
-int gfx_odd_alias_pair_precise_max_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                                       const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, int relu,
-                                       void* stream);
 size_t gfx_odd_alias_pair_precise_workspace_bytes(int64_t rows, int64_t P);
 int gfx_odd_alias_pair_precise_plan_f32(void* plan, int64_t P, void* ws, size_t ws_bytes, void* stream);
 int gfx_odd_alias_pair_precise_f32(const float* z, float* y, int64_t ldy, int64_t lo, int64_t len, int64_t rows, int64_t P,
-                                   const void* plan, void* ws, size_t ws_bytes, void* stream);
+                                   const void* plan, void* ws, size_t ws_bytes, const uint32_t* rowmax, int relu,
+                                   void* stream);
 
 /* ---- small inverse real DFT (parameter-side front-ends) ---------------------------------------
  * y = irfft(X, n) for any n <= 8192 as a direct sum (twiddles tabulated in LDS), K = n/2 + 1 bins per row, X complex
@@ -328,18 +302,11 @@ int gfx_peq_coeffs_bwd_f32(const float* w0, const float* q_inv, const float* log
  *   gfx_apply_gain_f32   y = (exp_gain ? exp(g) : g)[:,None,:] * x        dynamics.py:405
  *   gfx_stereo_gain_f32  StereoGain.forward                               stereo.py:38-41
  */
-int gfx_dynamics_fused_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap,
-                           const float* log_threshold, const float* log_ratio, const float* log_knee,
-                           const float* z_alpha, int64_t R, int64_t C, int64_t L, int smoother,
-                           int64_t iir_len, int knee, int gate, void* stream);
-/* Same with parameters shared across the batch: row r reads parameter row (r % param_rows). */
-int gfx_dynamics_fused_ex_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap,
-                              const float* log_threshold, const float* log_ratio, const float* log_knee,
-                              const float* z_alpha, int64_t param_rows, int64_t R, int64_t C, int64_t L,
-                              int smoother, int64_t iir_len, int knee, int gate, void* stream);
-/* The same with a workspace of gfx_dynamics_ws_bytes(param_rows) bytes (scratch for this call; may be NULL, which is
- * gfx_dynamics_fused_ex_f32) and an optional `u1` (R, L): the un-truncated smoother scan (1 - a) * U, kept for
- * gfx_dynamics_bwd_u1_f32.  With a workspace the smoothed configuration runs as dependency-free one-shot tiles: every
+/* Parameters may be shared across the batch: row r reads parameter row (r % param_rows); param_rows = R is one set per row.
+ * `ws`: a workspace of gfx_dynamics_ws_bytes(param_rows) bytes (scratch for this call), or NULL: one workgroup per row.
+ * `u1` (R, L), optional: receives the un-truncated smoother scan (1 - a) * U, kept for gfx_dynamics_bwd_f32
+ * (u1_is_scratch = 0) -- one extra 4-byte store per sample.  With a workspace the smoothed configuration runs as
+ * dependency-free one-shot tiles: every
  * 1024-sample tile of every row is its own workgroup, which re-reads the H = ceil(log 1e-12 / log a) most recent
  * samples before the tile to rebuild the smoother state (exact to 1e-12 of the peak energy: the smoother is a FIR with
  * taps (1 - a) a^k) -- the access shape of a plain copy, where one workgroup per row is a set of long scattered
@@ -356,11 +323,11 @@ size_t gfx_dynamics_ws_bytes(int64_t param_rows);
  * started).  Only rows with a LIVE truncation term (a^iir_len > 1e-12) are left to the row kernel.  A workspace of
  * gfx_dynamics_ws_bytes(param_rows) bytes keeps the round-4 behaviour (those rows on the row kernel too). */
 size_t gfx_dynamics_ws_bytes_ex(int64_t param_rows, int64_t R, int64_t L);
-int gfx_dynamics_fused_ws_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap,
-                              const float* log_threshold, const float* log_ratio, const float* log_knee,
-                              const float* z_alpha, int64_t param_rows, int64_t R, int64_t C, int64_t L,
-                              int smoother, int64_t iir_len, int knee, int gate, float* u1,
-                              void* ws, size_t ws_bytes, void* stream);
+int gfx_dynamics_fused_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap,
+                           const float* log_threshold, const float* log_ratio, const float* log_knee,
+                           const float* z_alpha, int64_t param_rows, int64_t R, int64_t C, int64_t L,
+                           int smoother, int64_t iir_len, int knee, int gate, float* u1,
+                           void* ws, size_t ws_bytes, void* stream);
 /* Diagnostic, the twin of gfx_fftconv_last_kernel: the name -- as rocprofv3's kernel trace prints it -- of the kernel that
  * carries the rows of the calling thread's last successful gfx_dynamics_fused_* call: "dyn_oneshot_mix_kernel" (tiles with
  * the routing sums), "dyn_oneshot_kernel" (tiles; rows the pole table rejects ride on dyn_fused_kernel in the same call),
@@ -378,24 +345,18 @@ const char* gfx_dynamics_last_kernel(void);
  * grafx_amd.ops.mix_schedule).  `extras` (nullable; n_pre + n_post pairs of int64) names sources of the sum that are not
  * rows of this call but finished rows of the same buffer: (row offset from `mix` in units of mix_sv, code as in sched);
  * the first n_pre are added before the call's rows, the others after them.  Needs the one-pole smoother, the workspace and
- * 16-byte aligned rows with L % 4 == 0; GFX_EINVAL otherwise (callers run the two stages separately then). */
+ * 16-byte aligned rows with L % 4 == 0; GFX_EINVAL otherwise (callers run the two stages separately then).
+ * `flags`: 0, or GFX_MIX_SKIP_ROWS: the call's own rows are NOT stored by the tile kernels -- for a render whose
+ * caller wants the output node only (grafx_amd.render.render_grafx(keep_signal_buffer=False)) and a stage whose rows
+ * nothing but the fused routing sums reads: the stage then moves 8 instead of 16 bytes per stereo sample plus the sums.
+ * (Rows the pole table leaves to the row kernel are still written: the summing tiles read them back from y.) */
+#define GFX_MIX_SKIP_ROWS 1
 int gfx_dynamics_fused_mix_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
                                const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
                                int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
                                float* u1, void* ws, size_t ws_bytes, const int64_t* sched, int64_t inner, int64_t n_acc,
                                float* mix, int64_t mix_sb, int64_t mix_sv, int64_t mix_sc, const int64_t* extras,
-                               int64_t n_pre, int64_t n_post, void* stream);
-/* The same with flags.  GFX_MIX_SKIP_ROWS: the call's own rows are NOT stored by the tile kernels -- for a render whose
- * caller wants the output node only (grafx_amd.render.render_grafx(keep_signal_buffer=False)) and a stage whose rows
- * nothing but the fused routing sums reads: the stage then moves 8 instead of 16 bytes per stereo sample plus the sums.
- * (Rows the pole table leaves to the row kernel are still written: the summing tiles read them back from y.) */
-#define GFX_MIX_SKIP_ROWS 1
-int gfx_dynamics_fused_mix_flags_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                                     const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                     int64_t R, int64_t C, int64_t L, int smoother, int64_t iir_len, int knee, int gate,
-                                     float* u1, void* ws, size_t ws_bytes, const int64_t* sched, int64_t inner, int64_t n_acc,
-                                     float* mix, int64_t mix_sb, int64_t mix_sv, int64_t mix_sc, const int64_t* extras,
-                                     int64_t n_pre, int64_t n_post, int flags, void* stream);
+                               int64_t n_pre, int64_t n_post, int flags, void* stream);
 int gfx_energy_f32(const float* x, gfx_rowmap_t xmap, float* e, int64_t R, int64_t C, int64_t L, void* stream);
 int gfx_onepole_f32(const float* u, const float* z_alpha, float* out, int64_t R, int64_t L, int64_t Lout,
                     int64_t iir_len, int relu, void* stream);
@@ -407,62 +368,49 @@ int gfx_onepole_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const f
 int gfx_onepole_fir_f32(const float* z_alpha, float* h, int64_t R, int64_t iir_len, void* stream);
 /* Ballistics.forward (core/envelope.py:84-101): at, rt = sigmoid(z_alpha[:, 0]), sigmoid(z_alpha[:, 1]);  y[-1] = 1;
  * c = at if u[n] < y[n-1] else rt;  y[n] = (1 - c) y[n-1] + c u[n], the two products and the sum rounded separately
- * (torchcomp's CPU loop).  u, y: (R, L).  This entry walks every row whole, one lane per row. */
-int gfx_ballistics_f32(const float* u, const float* z_alpha, float* y, int64_t R, int64_t L, void* stream);
-/* The same values, bit for bit, produced from chunks of the rows: with a workspace of gfx_ballistics_ws_bytes(R) bytes
- * (scratch for this call: one flag per row) a row is cut into up to 64 chunks that start from a warmed-up guess and are
- * accepted only if every chunk is entered with exactly the state its left neighbour ends with; rows that fail that
- * check, or whose slower coefficient needs a longer warm-up than a chunk, are walked whole by a second launch in the same
- * call (no host synchronisation).  ws == NULL: gfx_ballistics_f32.  `is_coef` != 0: z_alpha holds at, rt themselves (no
- * sigmoid) -- how the parity tests hand the oracle's coefficients over. */
+ * (torchcomp's CPU loop).  u, y: (R, L).  `is_coef` != 0: z_alpha holds at, rt themselves (no sigmoid) -- how the parity
+ * tests hand the oracle's coefficients over.
+ * ws == NULL: every row is walked whole, one lane per row.  With a workspace of gfx_ballistics_ws_bytes(R) bytes (scratch
+ * for this call: one flag per row) the same values, bit for bit, are produced from chunks of the rows: a row is cut into up
+ * to 64 chunks that start from a warmed-up guess and are accepted only if every chunk is entered with exactly the state
+ * its left neighbour ends with; rows that fail that check, or whose slower coefficient needs a longer warm-up than a
+ * chunk, are walked whole by a second launch in the same call (no host synchronisation).
+ * State across calls: y[-1] = zi[r] instead of 1 for signal row r (zi: (R), NULL = 1; never indexed by param_rows) and
+ * y[L-1] of every row is left in zf ((R), NULL = not wanted), in the sequential recursion's bits whichever schedule
+ * produced them: a signal cut anywhere and processed block by block, each block entering with the zf of the block
+ * before, gives the one-call output bit for bit (gfx_dynamics_ballistics_f32: the one-call ENVELOPE; the gain computer's
+ * output is the same bits when the blocks take the same kernel form, L % 4 == 0 on aligned rows).  Later launches of a
+ * call re-read zi for the rows they walk again, so zi and zf must not overlap: GFX_EINVAL. */
 size_t gfx_ballistics_ws_bytes(int64_t R);
-int gfx_ballistics_ws_f32(const float* u, const float* z_alpha, int is_coef, float* y, int64_t R, int64_t L, void* ws,
-                          size_t ws_bytes, void* stream);
+int gfx_ballistics_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
+                       int64_t L, void* ws, size_t ws_bytes, void* stream);
 /* The same recursion over the energy of a signal, env = ballistics(mean_c x^2) (dynamics.py:390 followed by
  * core/envelope.py:84-101 -- Compressor / NoiseGate with energy_smoother="ballistics"): x (R, C, L) addressed through xmap
  * is read once, the energy never reaches memory.  env: (R, L). */
-int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef, float* env,
-                              int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
+int gfx_ballistics_energy_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
+                              const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
+                              void* stream);
 /* Compressor / NoiseGate with energy_smoother="ballistics" and no gain smoother as ONE pass over the signal
  * (dynamics.py:390-405 with core/envelope.py:84-101 inside): energy -> attack / release recursion (the float32 sequential
  * recursion exactly, as above) -> log -> knee -> exp -> y = gain * x.  x, y: (R, C, L) through their row maps (in-place
- * slices of the render buffer); per-row parameters as gfx_dynamics_fused_ex_f32 (row r reads row r % param_rows),
+ * slices of the render buffer); per-row parameters as gfx_dynamics_fused_f32 (row r reads row r % param_rows),
  * z_alpha: (param_rows, 2); ws: gfx_ballistics_ws_bytes(R) bytes, or NULL for the whole-row walk only. */
 int gfx_dynamics_ballistics_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
                                 const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                int64_t R, int64_t C, int64_t L, int knee, int gate, void* ws, size_t ws_bytes, void* stream);
-/* State across calls.  The three entries above with y[-1] = zi[r] instead of 1 for signal row r (zi: (R), NULL = 1; never
- * indexed by param_rows) and y[L-1] of every row left in zf ((R), NULL = not wanted), in the sequential recursion's bits
- * whichever schedule produced them: a signal cut anywhere and processed block by block, each block entering with the zf of
- * the block before, gives the one-call output bit for bit (gfx_dynamics_ballistics_state_f32: the one-call ENVELOPE; the
- * gain computer's output is the same bits when the blocks take the same kernel form, L % 4 == 0 on aligned rows).  Later
- * launches of a call re-read zi for the rows they walk again, so zi and zf must not overlap: GFX_EINVAL.  With
- * zi = zf = NULL these are the entries above. */
-int gfx_ballistics_state_f32(const float* u, const float* z_alpha, int is_coef, const float* zi, float* zf, float* y, int64_t R,
-                             int64_t L, void* ws, size_t ws_bytes, void* stream);
-int gfx_ballistics_energy_state_f32(const float* x, gfx_rowmap_t xmap, int64_t C, const float* z_alpha, int is_coef,
-                                    const float* zi, float* zf, float* env, int64_t R, int64_t L, void* ws, size_t ws_bytes,
-                                    void* stream);
-int gfx_dynamics_ballistics_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* log_threshold,
-                                      const float* log_ratio, const float* log_knee, const float* z_alpha, int64_t param_rows,
-                                      int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
-                                      size_t ws_bytes, void* stream);
+                                int64_t R, int64_t C, int64_t L, int knee, int gate, const float* zi, float* zf, void* ws,
+                                size_t ws_bytes, void* stream);
 /* Adjoint of the recursion above given the forward input x, output y and g = dL/dy:
- * gx = dL/dx (R, L), gz = dL/dz_alpha (R, 2).  The attack/release choice is treated as locally constant. */
-int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
-                           int64_t R, int64_t L, void* stream);
-/* The same with the rows cut into chunks that different workgroups walk (the adjoint is linear and a contraction: each
- * chunk starts 2048 samples later in time with a zero carry, exact to (1 - c)^2048 <= 6e-10 for coefficients >= 0.0103; a
- * 64-row group with a slower row is walked whole).  ws: gfx_ballistics_bwd_ws_bytes(R, L) bytes (per-chunk partial sums of
- * the two coefficient gradients, added in a fixed order). */
+ * gx = dL/dx (R, L), gz = dL/dz_alpha (R, 2).  The attack/release choice is treated as locally constant.
+ * State: y[-1] = zi[r] (NULL = 1), and gzi (R; NULL = not wanted) receives dL/dzi = (1 - c[0]) lambda[0], the carry that
+ * leaves sample 0.  A cotangent of zf is a cotangent of y[L-1]: the caller adds it to g[:, L-1].
+ * ws == NULL: every row is walked whole by one lane, whatever the geometry (no GFX_ENOSPC for a missing workspace).  With
+ * ws of gfx_ballistics_bwd_ws_bytes(R, L) bytes (per-chunk partial sums of the two coefficient gradients, added in a fixed
+ * order) the rows are cut into chunks that different workgroups walk (the adjoint is linear and a contraction: each chunk
+ * starts 2048 samples later in time with a zero carry, exact to (1 - c)^2048 <= 6e-10 for coefficients >= 0.0103; a
+ * 64-row group with a slower row is walked whole); a geometry of one chunk takes the whole-row walk all the same. */
 size_t gfx_ballistics_bwd_ws_bytes(int64_t R, int64_t L);
-int gfx_ballistics_bwd_ws_f32(const float* x, const float* y, const float* g, const float* z_alpha, float* gx, float* gz,
-                              int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
-/* The adjoint with a state: y[-1] = zi[r] (NULL = 1), and gzi (R; NULL = not wanted) receives dL/dzi = (1 - c[0]) lambda[0],
- * the carry that leaves sample 0.  A cotangent of zf is a cotangent of y[L-1]: the caller adds it to g[:, L-1].  ws == NULL:
- * every row walked whole (gfx_ballistics_bwd_f32); otherwise the chunks of gfx_ballistics_bwd_ws_f32. */
-int gfx_ballistics_bwd_state_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
-                                 float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
+int gfx_ballistics_bwd_f32(const float* x, const float* y, const float* g, const float* z_alpha, const float* zi, float* gx,
+                           float* gz, float* gzi, int64_t R, int64_t L, void* ws, size_t ws_bytes, void* stream);
 int gfx_dyn_gain_f32(const float* env, float* gain, const float* log_threshold, const float* log_ratio,
                      const float* log_knee, int64_t R, int64_t L, int knee, int gate, int log_out, void* stream);
 /* Backward of the gain computer, for the training path (forward: gfx_dynamics_fused_f32).
@@ -478,53 +426,31 @@ int gfx_dyn_gain_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx
                          float* gain, float* denv, float* gparams, void* stream);
 int gfx_dyn_dx_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, const float* gain,
                    const float* de, float* gx, int64_t R, int64_t C, int64_t L, void* stream);
-/* The whole backward of Compressor / NoiseGate with the one-pole energy smoother and no gain smoother, in two
- * passes over the row (forward in time: recompute energy -> smoother -> gain, emit gain, the relu-masked d/d(smoothed
- * energy), the un-truncated scan u1 and the per-row parameter gradients; backward in time: the smoother's adjoint scan
- * and gx = gain * gy + (2/C) * de * x).  gx rows addressed by gxmap (e.g. a slice of the render's gradient buffer);
- * gparams (R,3); denv, u1 (R,L) each (workspace; the second pass recomputes the gain from u1 instead of reading a
- * stored copy).  dalpha (R), optional: dL/d(pole) of the smoother before
- * the sigmoid/clamp chain rule, accumulated by the second pass from u1, denv and its own adjoint scan (the D = dU/da
- * scan of core/envelope.py's truncated filter is moved onto the adjoint side, so no third scan is needed). */
+/* The whole backward of Compressor / NoiseGate with the one-pole energy smoother and no gain smoother (reference: autograd
+ * through dynamics.py:390-405 and core/envelope.py:34-60): one pass backward in time over (x, gy, u1) -- the smoother's
+ * adjoint scan and gx = gain * gy + (2/C) * de * x, the gain computer's derivatives recomputed from u1 where they are
+ * needed.  gx rows addressed by gxmap (e.g. a slice of the render's gradient buffer); gparams (R,3).  dalpha (R),
+ * optional: dL/d(pole) of the smoother before the sigmoid/clamp chain rule, accumulated by the same pass from u1 and its
+ * own adjoint scan (the D = dU/da scan of core/envelope.py's truncated filter is moved onto the adjoint side, so no third
+ * scan is needed).
+ * `u1` (R, L) = (1-a) x the un-truncated one-pole scan of the energy:
+ *   u1_is_scratch = 0  the scan the forward pass kept (gfx_dynamics_fused_f32's u1); it is only read.
+ *   u1_is_scratch = 1  R x L floats of scratch: the scan is rebuilt from x here, so the forward pass of a training step
+ *                      has nothing to store.
+ * `ws`: gfx_dynamics_bwd_ws_bytes(R, L) bytes of scratch for this call, or NULL: every row on the row kernel (with
+ * u1_is_scratch = 1: scan x into u1, then the backward pass).  With a workspace, rows with a short smoother memory --
+ * chosen per row on the device, exactly as in gfx_dynamics_fused_f32 -- run as dependency-free one-shot tiles walking
+ * backward in time, the others on the row kernel.  The tiles' shares of the per-row sums (gparams, dalpha) go through the
+ * workspace and are added in a fixed order: no float atomics, the gradients are the same bits from run to run.  Under
+ * u1_is_scratch = 1 the one-shot tiles rebuild the scan from x inside the tile (in the backward walk it is a suffix scan;
+ * the state entering a tile from its far end is the dot product of the H samples beyond it), so for those rows the
+ * scratch is never touched; the rows of the row kernel get their scan written to the scratch first. */
+size_t gfx_dynamics_bwd_ws_bytes(int64_t R, int64_t L);
 int gfx_dynamics_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
                          const float* log_threshold, const float* log_ratio, const float* log_knee,
                          const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                         float* gx, gfx_rowmap_t gxmap, float* gparams, float* denv, float* u1, float* dalpha,
-                         void* stream);
-/* The same backward when the forward pass has kept the scan: gfx_dynamics_fused_u1_f32 is gfx_dynamics_fused_ex_f32 that
- * also stores u1 (R, L) = (1-a) x the un-truncated one-pole scan of the energy (whole rows, one extra 4-byte store per
- * sample), and gfx_dynamics_bwd_u1_f32 is the second pass of gfx_dynamics_bwd_f32 alone, reading that u1.  Since round 2
- * gfx_dynamics_bwd_f32 itself runs as "scan x into u1" + that pass (the gain computer's derivatives are recomputed where
- * they are needed instead of being written out and read back); its `denv` workspace is no longer used and may be NULL. */
-int gfx_dynamics_fused_u1_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap,
-                              const float* log_threshold, const float* log_ratio, const float* log_knee,
-                              const float* z_alpha, int64_t param_rows, int64_t R, int64_t C, int64_t L, int smoother,
-                              int64_t iir_len, int knee, int gate, float* u1, void* stream);
-int gfx_dynamics_bwd_u1_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                            const float* log_threshold, const float* log_ratio, const float* log_knee,
-                            const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                            float* gx, gfx_rowmap_t gxmap, float* gparams, const float* u1, float* dalpha, void* stream);
-/* The same with a workspace of gfx_dynamics_bwd_ws_bytes(R, L) bytes (scratch for this call; NULL = the call above): rows
- * with a short smoother memory -- chosen per row on the device, exactly as in gfx_dynamics_fused_ws_f32 -- run as
- * dependency-free one-shot tiles walking backward in time, the others on the row kernel.  The tiles' shares of the
- * per-row sums (gparams, dalpha) go through the workspace and are added in a fixed order: no float atomics, the gradients
- * are the same bits from run to run. */
-size_t gfx_dynamics_bwd_ws_bytes(int64_t R, int64_t L);
-int gfx_dynamics_bwd_u1_ws_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                               const float* log_threshold, const float* log_ratio, const float* log_knee,
-                               const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                               float* gx, gfx_rowmap_t gxmap, float* gparams, const float* u1, float* dalpha,
-                               void* ws, size_t ws_bytes, void* stream);
-/* The same WITHOUT a scan kept by the forward pass (round 6): `u1_scratch` is R x L floats of scratch.  The one-shot tiles
- * rebuild the scan from x inside the tile (in the backward walk it is a suffix scan; the state entering a tile from its
- * far end is the dot product of the H samples beyond it), so for rows with a short smoother memory the scratch is never
- * touched and the forward pass of a training step has nothing to store; the rows of the row kernel get their scan written
- * to the scratch first.  Reference: autograd through dynamics.py:390-405 and core/envelope.py:34-60. */
-int gfx_dynamics_bwd_rescan_ws_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap,
-                                   const float* log_threshold, const float* log_ratio, const float* log_knee,
-                                   const float* z_alpha, int64_t R, int64_t C, int64_t L, int64_t iir_len, int knee, int gate,
-                                   float* gx, gfx_rowmap_t gxmap, float* gparams, float* u1_scratch, float* dalpha,
-                                   void* ws, size_t ws_bytes, void* stream);
+                         float* gx, gfx_rowmap_t gxmap, float* gparams, float* u1, int u1_is_scratch, float* dalpha,
+                         void* ws, size_t ws_bytes, void* stream);
 /* Pole gradient of TruncatedOnePoleIIRFilter (core/envelope.py:34-60) from the un-truncated scan U of its input and
  * the scan S of U:  da[r] = sum_n g[r,n] (c0 U[n] + c2 U[n-N]) + g[r,n+1] (c1 S[n] + c3 S[n-N]),  coef = (R, 4). */
 int gfx_onepole_dz_f32(const float* g, const float* U, const float* D, const float* coef, float* da, int64_t R,
@@ -555,47 +481,37 @@ int gfx_stft_f32(const float* x, const float* window, float* out, int64_t rows, 
 /* ---- STFT-masked noise reverb: impulse response ------------------------------------------
  * replaces STFTMaskedNoiseReverb.compute_stft_mask + compute_ir (reverb.py:161-200: mask, torch.istft),
  * ms_to_lr (core/midside.py:4-8) and the energy of normalize_impulse (core/utils.py:14-18).
- * noise_stft: (2, n_fft/2+1, num_frames) complex64 as interleaved floats (the module's buffer);
+ * noise_stft: one noise spectrum shared by all rows (`noise_rows` = 1: (2, n_fft/2+1, num_frames) complex64 as interleaved
+ * floats, the module's buffer) or one per row (`noise_rows` = R: (R, 2, n_fft/2+1, num_frames)) --
+ * STFTMaskedNoiseReverb(fixed_noise=False) draws fresh noise for every row (reverb.py:63, 80-82, 165);
  * init/delta: (R, 2, n_fft/2+1); gain_env (nullable): (R, 2, num_frames); window: (n_fft).
  * Outputs ir (R, 2, ir_len), un-normalised, and row_gain (R) = 1/sqrt(mean_c sum_t ir^2 + 1e-12),
  * to be passed as `gain` (gain_div = 2) to gfx_fir_spectrum_f32.
  * `basis` is a per-(n_fft, window) constant from gfx_istft_basis_f32 (gfx_istft_basis_bytes: the windowed (kpad, n_fft)
  * matrix, the un-windowed half basis (n_fft/2+1, 2, roundup(n_fft/2+1, 16)) that the n_fft <= 384 matrix kernel uses, and
  * the n_fft complex factors e^(2 pi i k / n_fft), e^(2 pi i p / (n_fft/2)) of the FFT form, GFX_ISTFT_FFT below).
- */
-size_t gfx_istft_basis_bytes(int64_t n_fft);
-int gfx_istft_basis_f32(const float* window, float* basis, int64_t n_fft, void* stream);
-size_t gfx_stft_reverb_workspace_bytes(int64_t R, int64_t n_fft, int64_t num_frames);
-int gfx_stft_reverb_ir_f32(const float* noise_stft, const float* init_log_magnitude,
-                           const float* delta_log_magnitude, const float* gain_env_log_magnitude,
-                           const float* window, const float* basis, float* ir, float* row_gain,
-                           int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
-                           int ms_to_lr, void* ws, size_t ws_bytes, void* stream);
-/* The same with one noise spectrum per row (`noise_rows` = R, noise_stft (R, 2, n_fft/2+1, num_frames) complex64) or one
- * shared by all rows (`noise_rows` = 1): STFTMaskedNoiseReverb(fixed_noise=False) draws fresh noise for every row
- * (reverb.py:63, 80-82, 165). */
-int gfx_stft_reverb_ir_ex_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
-                              const float* delta_log_magnitude, const float* gain_env_log_magnitude, const float* window,
-                              const float* basis, float* ir, float* row_gain, int64_t R, int64_t ir_len, int64_t n_fft,
-                              int64_t hop, int64_t num_frames, int ms_to_lr, void* ws, size_t ws_bytes, void* stream);
-/* The same with an explicit choice of how the frames are transformed (same results to rounding):
+ * `schedule`: how the frames are transformed (same results to rounding):
  *   GFX_ISTFT_GEMM  the inverse real DFT of a frame as a matrix product on the fp32 matrix cores (any even n_fft), the frames
  *                   written to the workspace and overlap-added by a second kernel.
  *   GFX_ISTFT_FFT   n_fft = 384 with hop = 192 (the reference's defaults, reverb.py:48-49) only, else GFX_EINVAL: a 192-point
  *                   complex FFT per frame (eight lanes a frame, 8 x 24 points), windowed and overlap-added in LDS; one
  *                   workgroup finishes 31 blocks of 192 samples of both channels of a row -- ~70x less arithmetic, and the
  *                   frames never reach memory.
- *   GFX_ISTFT_AUTO  what gfx_stft_reverb_ir_f32 / _ex_f32 use: FFT where it applies. */
+ *   GFX_ISTFT_AUTO  FFT where it applies.
+ * Workspace: gfx_stft_reverb_workspace_bytes with the same schedule (the FFT form keeps no frames).
+ */
 #define GFX_ISTFT_AUTO 0
 #define GFX_ISTFT_GEMM 1
 #define GFX_ISTFT_FFT 2
-size_t gfx_stft_reverb_workspace_bytes_sched(int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
-                                             int schedule);   /* what _sched_f32 needs: the FFT form keeps no frames */
-int gfx_stft_reverb_ir_sched_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
-                                 const float* delta_log_magnitude, const float* gain_env_log_magnitude,
-                                 const float* window, const float* basis, float* ir, float* row_gain, int64_t R,
-                                 int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames, int ms_to_lr, void* ws,
-                                 size_t ws_bytes, int schedule, void* stream);
+size_t gfx_istft_basis_bytes(int64_t n_fft);
+int gfx_istft_basis_f32(const float* window, float* basis, int64_t n_fft, void* stream);
+size_t gfx_stft_reverb_workspace_bytes(int64_t R, int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames,
+                                       int schedule);
+int gfx_stft_reverb_ir_f32(const float* noise_stft, int64_t noise_rows, const float* init_log_magnitude,
+                           const float* delta_log_magnitude, const float* gain_env_log_magnitude,
+                           const float* window, const float* basis, float* ir, float* row_gain, int64_t R,
+                           int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames, int ms_to_lr, void* ws,
+                           size_t ws_bytes, int schedule, void* stream);
 
 /* ---- routing ----------------------------------------------------------------------------
  * replaces read_single_tensor("index") + aggregate_tensor("sum"/"scatter") + inplace_write_tensor

@@ -9,10 +9,61 @@ import pytest
 from conftest import ROOT
 
 
-def header_symbols():
+def header_text():
     text = open(os.path.join(ROOT, "include", "grafx_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gfx_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def header_symbols():
+    return sorted(set(re.findall(r"\b(gfx_[a-z0-9_]+)\s*\(", header_text())))
+
+
+def header_prototypes():
+    """name -> (return type, [parameter type, ...]) of every prototype of the header, the types as written without the
+    parameter names ("const float*", "gfx_rowmap_t", "int64_t", ...)."""
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(gfx_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_text()):
+        types = []
+        for param in params.split(","):
+            param = " ".join(param.split())
+            if param != "void":
+                types.append(re.sub(r"\s*\b[A-Za-z_][A-Za-z0-9_]*$", "", param).replace(" *", "*"))
+        protos[name] = (" ".join(ret.split()).replace(" *", "*"), types)
+    return protos
+
+
+def ctypes_matches(ctype, ctypes_class, RowMap):
+    """Whether an entry of _lib.SIGNATURES is how ctypes must pass a C type of the header."""
+    import ctypes
+
+    if ctype == "const char*":                       # only as a return type: a static string
+        return ctypes_class is ctypes.c_char_p
+    if ctype.endswith("*"):                          # any pointer: an address, or a typed ctypes pointer
+        return ctypes_class is ctypes.c_void_p or (isinstance(ctypes_class, type) and issubclass(ctypes_class, ctypes._Pointer))
+    exact = {"gfx_rowmap_t": RowMap, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "int": ctypes.c_int,
+             "float": ctypes.c_float}
+    return ctype in exact and ctypes_class is exact[ctype]
+
+
+def test_ctypes_table_matches_the_header_prototypes_type_by_type():
+    """Entries keep their names when their argument lists change, so every row of _lib.SIGNATURES is held to the header's
+    prototype: same number of parameters, each passed as the ctypes class of its C type, same return type."""
+    from grafx_amd import _lib
+
+    protos = header_prototypes()
+    assert sorted(protos) == header_symbols(), "a prototype of the header was not parsed"
+    assert sorted(protos) == sorted(_lib.SIGNATURES)
+    wrong = []
+    for name, (ret, params) in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        if not ctypes_matches(ret, res, _lib.RowMap):
+            wrong.append(f"{name}: returns {ret}, bound as {res.__name__}")
+        if len(params) != len(args):
+            wrong.append(f"{name}: {len(params)} parameters in the header, {len(args)} in the table")
+            continue
+        wrong += [f"{name}: parameter {i} is {c}, bound as {a.__name__}" for i, (c, a) in enumerate(zip(params, args))
+                  if not ctypes_matches(c, a, _lib.RowMap)]
+    assert not wrong, "\n".join(wrong)
 
 
 def test_library_builds_and_exports_every_header_symbol():
@@ -34,12 +85,12 @@ def test_size_queries_need_no_gpu():
     from grafx_amd import _lib
 
     lib = _lib.lib()
-    assert lib.gfx_abi_version() == 1
+    assert lib.gfx_abi_version() == 2 == _lib.ABI_VERSION
     assert lib.gfx_fftconv_nparts(4001) == 1 and lib.gfx_fftconv_nparts(8193) == 1
     assert lib.gfx_fftconv_nparts(8194) == 2 and lib.gfx_fftconv_nparts(60001) == 8
-    assert lib.gfx_fir_spectrum_bytes(3, 4001) == 3 * 17 * 256 * 16
-    assert lib.gfx_fftconv_workspace_bytes(2, 2, 131072, 131072, 0, 4001) == 0
-    assert lib.gfx_fftconv_workspace_bytes(2, 2, 131072, 131072, 0, 60001) == 2 * 2 * (16 + 7) * 17 * 256 * 16
+    assert lib.gfx_fir_spectrum_bytes(3, 4001, 0) == 3 * 17 * 256 * 16
+    assert lib.gfx_fftconv_workspace_bytes(2, 2, 131072, 131072, 0, 4001, 0) == 0
+    assert lib.gfx_fftconv_workspace_bytes(2, 2, 131072, 131072, 0, 60001, 0) == 2 * 2 * (16 + 7) * 17 * 256 * 16
     assert lib.gfx_iir_fsm_plan_bytes(4001) == (8192 + 4096 + 2 * 2052) * 8 and lib.gfx_iir_fsm_plan_bytes(5000) == 0
     assert lib.gfx_istft_basis_bytes(384) == (388 * 384 + 193 * 2 * 208 + 2 * 384) * 4   # full basis, half basis, FFT factors
     # the odd-length aliasing: one row per transform needs (3P - 1) / 2 points (25 tiles at P = 135 071), two rows per
@@ -72,6 +123,18 @@ def test_processors_refuse_cpu_tensors_and_missing_library(monkeypatch):
     monkeypatch.setattr(_lib, "LIB", "/nonexistent/libgrafx_amd.so")
     with pytest.raises(ImportError, match="not built"):
         _lib.lib()
+
+
+def test_library_of_another_abi_version_is_refused(monkeypatch):
+    """Entries keep their names across ABI versions, so a library built from another version of the sources must not load."""
+    from grafx_amd import _lib
+
+    _lib.lib()                                   # (built, and of this version)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
+    with pytest.raises(ImportError, match="ABI version 2.*not built"):
+        _lib.lib()
+    assert _lib._lib is None
 
 
 def test_plain_c_program_links_and_runs_against_the_library(tmp_path):

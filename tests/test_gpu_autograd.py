@@ -347,7 +347,7 @@ def test_fsm_taps_backward_matches_torch_autograd(N):
 
 @pytest.mark.gpu
 def test_compressor_backward_with_and_without_the_kept_scan_agree():
-    """gfx_dynamics_bwd_f32 (scan x again, then the backward-in-time pass) and gfx_dynamics_bwd_u1_f32 (the same pass on
+    """gfx_dynamics_bwd_f32 on a scratch u1 (scan x again, then the backward-in-time pass) and on a kept u1 (the same pass on
     the scan kept in the forward) are the same arithmetic: identical gradients, bit for bit with the row schedule (to rounding
     with the one-shot tiles), including rows with a live truncation term; the forward that keeps the scan returns the plain forward's output."""
     import torch
@@ -386,9 +386,9 @@ def test_compressor_backward_with_and_without_the_kept_scan_agree():
 @pytest.mark.parametrize("gate", [False, True])
 @pytest.mark.parametrize("knee", ["hard", "quadratic", "exponential"])
 def test_backward_tiles_rebuild_the_smoother_scan(knee, gate, C):
-    """gfx_dynamics_bwd_rescan_ws_f32: the one-shot backward tiles rebuild u1 from x (a suffix scan in the backward walk, the
+    """gfx_dynamics_bwd_f32 with a scratch u1 and a workspace: the one-shot backward tiles rebuild u1 from x (a suffix scan in the backward walk, the
     entry state from the H samples beyond the tile's far end, continued over the H positions in front of it) instead of
-    reading the scan the forward kept.  Against the kept scan (gfx_dynamics_bwd_u1_ws_f32) at a length of many tiles: poles
+    reading the scan the forward kept.  Against the kept scan (u1_is_scratch = 0) at a length of many tiles: poles
     from instant to the longest one-shot history (H = 256 taps at a = 0.897), rows that leave the tile grid (slower poles:
     their scan goes through the scratch), rows of silence and a row that ends in silence; every row by its own size."""
     from grafx_amd import ops

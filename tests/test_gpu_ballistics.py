@@ -203,7 +203,7 @@ def test_compressor_with_the_ballistics_smoother_matches_the_oracle(knee, gate):
 
 @pytest.mark.parametrize("R,L", [(130, 40000), (64, 131072), (200, 20001)])
 def test_chunked_adjoint_equals_the_whole_row_adjoint(R, L):
-    """gfx_ballistics_bwd_ws_f32: the adjoint recursion lambda[n] = g[n] + (1 - c[n+1]) lambda[n+1] is linear and a
+    """gfx_ballistics_bwd_f32 with a workspace: the adjoint recursion lambda[n] = g[n] + (1 - c[n+1]) lambda[n+1] is linear and a
     contraction, so chunks that start 2048 samples later with a zero carry reproduce the whole-row walk to (1 - c)^2048;
     groups of 64 rows with a coefficient below 0.0103 are walked whole.  Rows of both kinds, ragged last group, L % 4 != 0;
     the coefficient gradients are sums over the row (per-chunk partials, added in chunk order)."""

@@ -1,5 +1,5 @@
-"""The attack / release envelope state across calls of Ballistics (`gfx_ballistics_state_f32`, `gfx_ballistics_energy_state_f32`,
-`gfx_dynamics_ballistics_state_f32`, `gfx_ballistics_bwd_state_f32`; `ops.ballistics(zi=, return_state=)`, `BallisticsStateFn`,
+"""The attack / release envelope state across calls of Ballistics (`zi` / `zf` of `gfx_ballistics_f32`, `gfx_ballistics_energy_f32`,
+`gfx_dynamics_ballistics_f32`, `gfx_ballistics_bwd_f32`; `ops.ballistics(zi=, return_state=)`, `BallisticsStateFn`,
 `Ballistics / BallisticsEnvelopeFollower / Compressor / NoiseGate(..., state=, return_state=)`): a signal processed in blocks,
 each block entering with the envelope the block before left, is the signal processed in one call.
 
@@ -202,7 +202,7 @@ def test_energy_source_with_state(C, schedule):
 @pytest.mark.parametrize("C", [1, 2])
 @pytest.mark.parametrize("knee,gate", [("hard", False), ("quadratic", True), ("exponential", False)])
 def test_one_pass_compressor_with_state(C, knee, gate):
-    """gfx_dynamics_ballistics_state_f32 never stores the envelope: its zf is the zf of ops.ballistics_energy on the same
+    """gfx_dynamics_ballistics_f32 never stores the envelope: its zf is the zf of ops.ballistics_energy on the same
     input bit for bit; its output in two blocks is the one-call output -- the same bits when both blocks (and the whole) have
     lengths that are multiples of 4 (the same kernel instantiation), within 1e-5 otherwise."""
     from grafx_amd import ops
@@ -544,13 +544,13 @@ def test_bad_states_are_refused():
     stream = torch.cuda.current_stream().cuda_stream
     lib = _lib.lib()
     for zf in (zi, zi[1:]):
-        assert lib.gfx_ballistics_state_f32(u.data_ptr(), z.data_ptr(), 0, zi.data_ptr(), zf.data_ptr(), y.data_ptr(), R, L,
-                                            ws.data_ptr(), ws.numel(), stream) == ops.GFX_EINVAL
-        assert lib.gfx_ballistics_energy_state_f32(x.data_ptr(), ops.rowmap(x)[0], 2, z.data_ptr(), 0, zi.data_ptr(), zf.data_ptr(),
-                                                   y.data_ptr(), R, L, ws.data_ptr(), ws.numel(), stream) == ops.GFX_EINVAL
+        assert lib.gfx_ballistics_f32(u.data_ptr(), z.data_ptr(), 0, zi.data_ptr(), zf.data_ptr(), y.data_ptr(), R, L,
+                                      ws.data_ptr(), ws.numel(), stream) == ops.GFX_EINVAL
+        assert lib.gfx_ballistics_energy_f32(x.data_ptr(), ops.rowmap(x)[0], 2, z.data_ptr(), 0, zi.data_ptr(), zf.data_ptr(),
+                                             y.data_ptr(), R, L, ws.data_ptr(), ws.numel(), stream) == ops.GFX_EINVAL
         out = torch.empty_like(x)
-        assert lib.gfx_dynamics_ballistics_state_f32(x.data_ptr(), ops.rowmap(x)[0], out.data_ptr(), ops.rowmap(out)[0],
-                                                     p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), z.data_ptr(), R, R, 2, L,
-                                                     1, 0, zi.data_ptr(), zf.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     stream) == ops.GFX_EINVAL
+        assert lib.gfx_dynamics_ballistics_f32(x.data_ptr(), ops.rowmap(x)[0], out.data_ptr(), ops.rowmap(out)[0],
+                                               p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), z.data_ptr(), R, R, 2, L,
+                                               1, 0, zi.data_ptr(), zf.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               stream) == ops.GFX_EINVAL
     torch.cuda.synchronize()

@@ -101,7 +101,7 @@ def test_linearity_and_shift_at_full_size():
 @pytest.mark.gpu
 @pytest.mark.parametrize("L,N,Cin,Cf", [(40000, 4001, 2, 1), (16385, 8193, 2, 2), (5000, 33, 1, 1)])
 def test_fftconv_tee_copies_the_input_and_leaves_the_output_unchanged(L, N, Cin, Cf):
-    """gfx_fftconv_tee_f32: same y as gfx_fftconv_f32, plus a bit-exact copy of x (strided destination rows)."""
+    """gfx_fftconv_f32 with xcopy: same y as without, plus a bit-exact copy of x (strided destination rows)."""
     import torch
 
     from grafx_amd import ops
@@ -236,7 +236,7 @@ def test_filter_gradient_correlation_matches_float64(L, Lg, N, off, Cx, Cg):
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("GRAFX_FUZZ_PIPE_SEEDS", 24))))
 def test_pipe_schedule_matches_the_oracle_convolution(seed):
-    """The hand-scheduled persistent kernel (gfx_fftconv_sched_f32, GFX_SCHED_PIPE: generated gfx950 assembly, csrc/asm)
+    """The hand-scheduled persistent kernel (gfx_fftconv_f32, GFX_SCHED_PIPE: generated gfx950 assembly, csrc/asm)
     forced onto small random problems it covers -- tap counts of every overlap it is built for, even lengths around the tile
     boundaries (V = 12288), one to many tiles per row, fewer tiles than workgroups and more, channel broadcasts, shared
     filters, strided buffer views and the input copy -- against the oracle and the compiler-built tile kernel."""

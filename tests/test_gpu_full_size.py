@@ -219,7 +219,7 @@ def test_cfg3_full_batch_512_rows_repeat_the_checked_rows():
 
 @pytest.mark.parametrize("iir_len", [16383, 300, 40])
 def test_oneshot_schedule_of_the_fused_dynamics_equals_the_row_schedule(iir_len):
-    """gfx_dynamics_fused_ws_f32 (dependency-free one-shot tiles that re-read their smoother history, chosen per row on
+    """gfx_dynamics_fused_f32 with a workspace (dependency-free one-shot tiles that re-read their smoother history, chosen per row on
     the device) against the row-streaming kernel: poles from instant to the clamp at 1 - 1e-5 in ONE call, so that rows
     taken by the one-shot grid and rows left to the row kernel (long memory, or a live truncation term at short
     iir_len) sit side by side; ragged length, mono and stereo, shared parameter rows, and the kept scan `u1`."""

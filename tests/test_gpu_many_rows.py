@@ -945,7 +945,7 @@ def test_odd_alias_precise(pairs, rows_per_chunk, monkeypatch, small_alias_works
 @pytest.mark.parametrize("P,R,C,rows_per_chunk", [(101, R_BIG, 1, None), (101, 21867, 3, 70000), (4001, 16403, 1, 70000),
                                                   (4001, 5467, 3, None)])
 def test_odd_alias_rows_form(P, R, C, rows_per_chunk, pairs, monkeypatch, small_alias_workspace):
-    """out=: the rows land in a strided (B, n, C, length) view (gfx_odd_alias_rows_f32 / _pair_rows_f32 with row0 and the
+    """out=: the rows land in a strided (B, n, C, length) view (ymap of gfx_odd_alias_f32 / gfx_odd_alias_pair_f32 with row0 and the
     row map); 65 601 and 16 403 rows (an odd count past the one-row entry's 16 383), a slice of the result."""
     from grafx_amd import ops
 

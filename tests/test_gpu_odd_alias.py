@@ -173,7 +173,7 @@ def test_every_supported_tile_count(C):
 
 @pytest.mark.parametrize("P,C", [(4607, 1), (135071, 2), (191071, 2)])
 def test_odd_alias_writes_strided_buffer_rows_in_place(P, C):
-    """gfx_odd_alias_rows_f32: the aliased rows land directly in a strided (B, n, C, length) view of a signal buffer (the
+    """gfx_odd_alias_f32 with a row map: the aliased rows land directly in a strided (B, n, C, length) view of a signal buffer (the
     stage's output slice in render_grafx) -- same values as the contiguous result, nothing outside the view touched,
     across the chunk boundary (more rows than one launch chain takes)."""
     from grafx_amd import ops

@@ -145,7 +145,7 @@ def _aliased_convolution_f64(x, h):
 
 @pytest.mark.parametrize("L,N", CONV_SHAPES)
 def test_supplied_maxima_of_rows_at_very_different_levels(L, N):
-    """The console's route to gfx_odd_alias_pair_max_f32 / _rows_max_f32: the full-length convolution leaves max |z| of
+    """The console's route to gfx_odd_alias_pair_f32 with given row maxima: the full-length convolution leaves max |z| of
     its rows, the aliasing takes the words.  Per row against the float64 aliasing of the float64 linear convolution;
     into a strided (B, n, C, L) view the same bits; slices are ranges of the full result."""
     from grafx_amd import ops

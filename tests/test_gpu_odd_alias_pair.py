@@ -189,7 +189,7 @@ def test_precise_pairs_are_float64_accurate(P):
 
 @pytest.mark.parametrize("P,C", [(4001, 2), (135071, 2), (9001, 1), (9001, 3), (262145, 2), (1000001, 1)])
 def test_pairs_write_strided_buffer_rows_in_place(P, C):
-    """gfx_odd_alias_pair_rows_f32: rows 2r, 2r + 1 of the call -> row q / C, channel q % C of a strided (B, n, C, len) view
+    """gfx_odd_alias_pair_f32 with a row map: rows 2r, 2r + 1 of the call -> row q / C, channel q % C of a strided (B, n, C, len) view
     (the render's signal buffer); odd C makes pairs straddle signal rows; chunks keep pairs whole.  P = 262 145: the fused
     one-outer-level kernels; 1 000 001: two outer levels on czt.hip's passes."""
     from grafx_amd import ops
@@ -253,9 +253,9 @@ def test_fused_outer_level_equals_the_separate_passes(P, monkeypatch):
 
 
 def test_the_convolution_kernel_leaves_the_rows_maxima_for_the_pair_scaling():
-    """gfx_fftconv_rowmax_f32: the tile kernel of the full-length convolution keeps max |y| per output row-channel as a
+    """gfx_fftconv_f32 with rowmax: the tile kernel of the full-length convolution keeps max |y| per output row-channel as a
     by-product of its stores, and the aliasing's pair form takes the words instead of reading z once more
-    (gfx_odd_alias_pair_max_f32); the partitioned convolution (more than 8193 taps) does the same.  Rows at very different levels, a silent row; with and without the by-product: the same bits."""
+    (gfx_odd_alias_pair_f32's rowmax); the partitioned convolution (more than 8193 taps) does the same.  Rows at very different levels, a silent row; with and without the by-product: the same bits."""
     from grafx_amd import ops
 
     torch.manual_seed(0)
@@ -293,7 +293,7 @@ def test_the_convolution_kernel_leaves_the_rows_maxima_for_the_pair_scaling():
 def test_the_envelope_in_three_passes_equals_the_six_it_replaces(C, L, N, view):
     """A compressor whose smoother's convolve() aliases (upstream's default tap counts): energy -> truncated one-pole (full
     length) -> aliasing in double -> relu.  gfx_onepole_energy_f32 forms the energy inside the scan and leaves the rows'
-    maxima, gfx_odd_alias_pair_precise_max_f32 takes them and clamps in its last pass: the same values as energy_kernel +
+    maxima, gfx_odd_alias_pair_precise_f32 takes them and clamps in its last pass: the same values as energy_kernel +
     onepole_kernel + the aliasing's own pass over the rows + torch.relu (the scan is the same arithmetic; the maxima are those
     of what was stored), poles from fast to the clamp (live truncation term), silence, strided buffer views."""
     from grafx_amd import ops

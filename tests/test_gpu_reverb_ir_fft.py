@@ -1,4 +1,4 @@
-"""The two forms of the STFT-masked-noise impulse response synthesis behind gfx_stft_reverb_ir_sched_f32: frames as matrix
+"""The two forms of the STFT-masked-noise impulse response synthesis behind gfx_stft_reverb_ir_f32: frames as matrix
 products on the fp32 matrix cores (GFX_ISTFT_GEMM) and as 192-point FFTs overlap-added in LDS (GFX_ISTFT_FFT, the
 reference's default n_fft = 384 / hop = 192), against the oracle (reverb.py:161-200) and against each other."""
 import numpy as np

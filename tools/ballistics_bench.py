@@ -52,6 +52,8 @@ for R in a.rows:
         if old is not None:
             vp = ctypes.c_void_p
             s = torch.cuda.current_stream().cuda_stream
+            # `old` is a separately built library of round 4: its gfx_ballistics_f32 is the six-argument entry of that
+            # ABI (u, z_alpha, y, R, L, stream), not the one include/grafx_amd.h declares today
             rows.append(("round-4 kernel", timed(lambda: old.gfx_ballistics_f32(vp(u.data_ptr()), vp(z.data_ptr()), vp(y.data_ptr()),
                                                                               ctypes.c_int64(R), ctypes.c_int64(L), vp(s))),
                          8 * R * L))
