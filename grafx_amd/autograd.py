@@ -372,12 +372,12 @@ _DELAYS = {}
 
 def _fsm_delays(N, device):
     """exp(-j 2 pi d k / N), d = 0..2, k = 0..N//2 with the float32 phase upstream uses (core/iir.py:263-276)."""
-    key = (N, device.type, device.index)
-    if key not in _DELAYS:
+    def build():
         d = torch.arange(3, device=device)
         k = torch.arange(N // 2 + 1, device=device)
-        _DELAYS[key] = torch.exp(-1j * ((d[:, None] * k[None, :]).to(torch.float32) / N * 2 * math.pi))
-    return _DELAYS[key]
+        return torch.exp(-1j * ((d[:, None] * k[None, :]).to(torch.float32) / N * 2 * math.pi))
+
+    return ops.built_once(_DELAYS, (N, device.type, device.index), build, device, f"fsm taps backward (N={N}): the delay table")
 
 
 FSM_BWD_NATIVE = True     # FsmFirFn's backward on gfx_iir_fsm_bwd_f32 (False: the batched torch ops of rounds 4-5)

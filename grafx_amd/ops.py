@@ -478,6 +478,24 @@ def _alias_plan(P, device, precise=False, pairs=False):
     return plan
 
 
+def built_once(cache, key, build, device, what):
+    """``cache[key]`` for a device-side table that is built once and kept (the Bluestein plan of the fsm filters, the
+    inverse-STFT bases and window envelope of the reverb, the delay table of the fsm taps' backward): on a miss ``build()``
+    launches it on the current stream, and that stream is synchronised before the value enters the cache -- as
+    :func:`_alias_plan` does, a cached table is complete before any other stream can pick it up.  A hit is one dict
+    lookup.  A miss under a HIP-graph capture raises: the table would live in the graph's private pool."""
+    if key in cache:
+        return cache[key]
+    on_gpu = device.type == "cuda"      # (a CPU tensor is refused by the entry the table is for, not here)
+    if on_gpu and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what}: not built yet; run the call once outside the HIP-graph capture")
+    value = build()
+    if on_gpu:
+        torch.cuda.current_stream(device).synchronize()
+    cache[key] = value
+    return value
+
+
 ALIAS_WS_CAP = 4 << 30     # bytes of chirp-z workspace per launch chain (rows go through in chunks that fit it; 1 -> 4 GB:
                            # -6 % on the console's 4608 equaliser rows, tools/czt_chunk_ab.py).  Never more than a quarter
                            # of the memory that is free when the call is made, and halved (down to one row) when the

@@ -59,10 +59,8 @@ class IIRFilter(nn.Module):
             raise ValueError(f"Unsupported backend: {backend}")
 
     def _plan(self, device):
-        key = (device.type, device.index)
-        if key not in self._plans:
-            self._plans[key] = ops.iir_fsm_plan(self.fsm_fir_len, device)
-        return self._plans[key]
+        return ops.built_once(self._plans, (device.type, device.index), lambda: ops.iir_fsm_plan(self.fsm_fir_len, device),
+                              device, f"IIRFilter(fsm_fir_len={self.fsm_fir_len}): the taps' plan")
 
     FSM_NATIVE_MAX = 4096  # the Bluestein inverse DFT runs on one 8192-point LDS tile: 2N - 1 <= 8192
 

@@ -52,10 +52,8 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         return spec.view(num_noises, 2, self.num_bins, self.num_frames)
 
     def _istft_basis(self, device):
-        key = (device.type, device.index)
-        if key not in self._basis:
-            self._basis[key] = ops.istft_basis(self.window)
-        return self._basis[key]
+        return ops.built_once(self._basis, (device.type, device.index), lambda: ops.istft_basis(self.window), device,
+                              "STFTMaskedNoiseReverb: the inverse-STFT bases")
 
     def _ir_and_gain(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, ms_lr):
         genv = gain_env_log_magnitude if self.gain_envelope else None
@@ -100,11 +98,11 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
 
         frames = diff.irfft_small(spec.transpose(-1, -2), n_fft) * self.window
         y = self._overlap_add(frames)
-        key = (spec.device.type, spec.device.index, T)
-        if key not in self._envelope:
-            self._envelope[key] = self._overlap_add((self.window * self.window).expand(1, T, n_fft))[0]
+        envelope = ops.built_once(self._envelope, (spec.device.type, spec.device.index, T),
+                                  lambda: self._overlap_add((self.window * self.window).expand(1, T, n_fft))[0], spec.device,
+                                  "STFTMaskedNoiseReverb: the overlap-added squared window")
         a = n_fft // 2
-        return y[:, a : a + self.ir_len] / self._envelope[key][a : a + self.ir_len]
+        return y[:, a : a + self.ir_len] / envelope[a : a + self.ir_len]
 
     def _overlap_add(self, frames):
         """(R, T, n_fft) frames -> (R, n_fft + hop (T - 1)) with n_fft a multiple of hop: the q-th hop-sized piece of
