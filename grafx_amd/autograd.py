@@ -644,6 +644,41 @@ class WaveshaperFn(torch.autograd.Function):
                 like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None)
 
 
+class StftReverbIrFn(torch.autograd.Function):
+    """The taps of STFTMaskedNoiseReverb (reverb.py:161-200, ms_to_lr, normalize_impulse) for n_fft = 384, hop = 192 as one
+    autograd node: forward is the inference kernel (``ops.stft_reverb_ir``, "fft" schedule; times ``row_gain`` when
+    ``normalise`` is set), backward its adjoint ``gfx_stft_reverb_ir_bwd_f32`` -- instead of the mask / irfft / overlap-add
+    chain of torch ops with its (R, 2, 193, T) complex tensors on autograd's tape.  Saved: the parameters, the
+    un-normalised taps, the R gains and the noise (a reference to the module's buffer, or the per-row noise this forward
+    was given: backward sees the noise of the forward).  The noise, window and basis get no gradient.  Other transform
+    sizes have no native backward: STFTMaskedNoiseReverb keeps the torch chain for them."""
+
+    @staticmethod
+    def forward(ctx, init_lm, delta_lm, gain_env, noise_stft, window, basis, ir_len, hop, ms_to_lr, normalise):
+        if window.numel() != 384 or hop != 192:
+            raise ValueError(f"StftReverbIrFn: n_fft = 384 with hop = 192 only, got {window.numel()} / {hop}")
+        ir, row_gain = ops.stft_reverb_ir(noise_stft, init_lm, delta_lm, gain_env, window, basis, ir_len, hop, ms_to_lr,
+                                          schedule="fft")
+        if normalise:
+            ctx.save_for_backward(init_lm, delta_lm, gain_env, noise_stft, window, basis, ir, row_gain)
+        else:
+            ctx.save_for_backward(init_lm, delta_lm, gain_env, noise_stft, window, basis, None, None)
+        ctx.cfg = (hop, bool(ms_to_lr), bool(normalise))
+        return ir * row_gain[:, None, None] if normalise else ir
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gh):
+        init_lm, delta_lm, gain_env, noise_stft, window, basis, ir, row_gain = ctx.saved_tensors
+        hop, ms_to_lr, normalise = ctx.cfg
+        g_init, g_delta, g_env = ops.stft_reverb_ir_bwd(
+            gh, noise_stft, init_lm, delta_lm, gain_env, window, basis, hop, ms_to_lr,
+            ir=ir if normalise else None, row_gain=row_gain if normalise else None,
+            want_gain_env=gain_env is not None and ctx.needs_input_grad[2])
+        return (g_init.view(init_lm.shape), g_delta.view(delta_lm.shape),
+                None if g_env is None else g_env.view(gain_env.shape), None, None, None, None, None, None, None)
+
+
 def truncated_one_pole(u, z_alpha, iir_len, exact=False):
     """core/envelope.py:34-49."""
     from .processors.core.convolution import reference_aliases

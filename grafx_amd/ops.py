@@ -1411,6 +1411,61 @@ def stft_reverb_ir(noise_stft, init_lm, delta_lm, gain_env, window, basis, ir_le
     return ir, row_gain
 
 
+def stft_reverb_ir_bwd_ws_bytes(R, ir_len):
+    """Bytes of workspace one gfx_stft_reverb_ir_bwd_f32 call over R rows needs (no GPU involved)."""
+    return lib().gfx_stft_reverb_ir_bwd_ws_bytes(R, ir_len)
+
+
+@_on_device
+def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window, basis, hop, ms_to_lr, ir=None,
+                       row_gain=None, want_gain_env=True, ws=None):
+    """Backward of :func:`stft_reverb_ir` with the "fft" schedule (n_fft 384 / hop 192 only; gfx_stft_reverb_ir_bwd_f32)
+    -> (g_init (R,2,193), g_delta (R,2,193), g_gain_env (R,2,T) or None).
+
+    ``grad_ir``: dL/dh (R,2,ir_len).  With ``ir`` and ``row_gain`` (the forward's outputs) h = row_gain * ir, the
+    normalised taps; without them h = ir.  The other arguments are the forward's; ``noise_stft`` per row must be the
+    noise the forward used.  ``g_gain_env`` is computed when ``gain_env`` is given and ``want_gain_env`` is set.
+    ``ws``: a uint8 workspace of at least ``stft_reverb_ir_bwd_ws_bytes(min(R, 32767), ir_len)`` bytes to reuse."""
+    _require_gpu(grad_ir, init_lm, delta_lm, gain_env, window, basis, ir, row_gain)
+    R, _, ir_len = grad_ir.shape
+    n_fft = window.numel()
+    T = noise_stft.shape[-1]
+    if (ir is None) != (row_gain is None):
+        raise ValueError("stft_reverb_ir_bwd: ir and row_gain come together (the normalised taps) or not at all")
+    if init_lm.shape[0] != R or (ir is not None and tuple(ir.shape) != tuple(grad_ir.shape)):
+        raise ValueError(f"stft_reverb_ir_bwd: gradient {tuple(grad_ir.shape)} does not match the {init_lm.shape[0]} rows")
+    noise_rows = noise_stft.shape[0] if noise_stft.ndim == 4 else 1
+    if noise_rows not in (1, R):
+        raise ValueError(f"stft_reverb_ir_bwd: {noise_rows} noise spectra for {R} rows")
+    nz = torch.view_as_real(noise_stft.contiguous())
+    grad_ir, init_lm, delta_lm = grad_ir.contiguous(), init_lm.contiguous(), delta_lm.contiguous()
+    gain_env = None if gain_env is None else gain_env.contiguous()
+    ir = None if ir is None else ir.contiguous()
+    row_gain = None if row_gain is None else row_gain.contiguous()
+    g_init, g_delta = torch.empty_like(init_lm), torch.empty_like(delta_lm)
+    g_env = torch.empty_like(gain_env) if (gain_env is not None and want_gain_env) else None
+    ROWS = 32767                                        # rows per launch, as the forward
+    nbytes = lib().gfx_stft_reverb_ir_bwd_ws_bytes(min(R, ROWS), ir_len)
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_ir.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise ValueError(f"stft_reverb_ir_bwd: the workspace must be {nbytes} contiguous uint8")
+    cut = lambda t, r0, n: None if t is None else t[r0:r0 + n]  # noqa: E731
+    for r0 in range(0, R, ROWS):
+        n = min(ROWS, R - r0)
+        pin = _Pin()
+        check(
+            lib().gfx_stft_reverb_ir_bwd_f32(_ptr(grad_ir[r0:r0 + n]), _ptr(cut(ir, r0, n)), _ptr(cut(row_gain, r0, n)),
+                                             _ptr(nz[r0:r0 + n] if noise_rows != 1 else nz),
+                                             noise_rows if noise_rows == 1 else n, pin(init_lm[r0:r0 + n]),
+                                             pin(delta_lm[r0:r0 + n]), pin(cut(gain_env, r0, n)), pin(window), pin(basis),
+                                             _ptr(g_init[r0:r0 + n]), _ptr(g_delta[r0:r0 + n]), _ptr(cut(g_env, r0, n)), n,
+                                             ir_len, n_fft, hop, T, int(ms_to_lr), _ptr(ws), ws.numel(), _stream()),
+            "gfx_stft_reverb_ir_bwd_f32",
+        )
+    return g_init, g_delta, g_env
+
+
 # ----------------------------------------------------------------------------------------- routing
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):

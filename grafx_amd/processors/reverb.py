@@ -67,6 +67,8 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
     def compute_ir(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None):
         """Un-normalised mid/side impulse responses (R,2,ir_len) (reverb.py:161-187)."""
         if needs_grad(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude):
+            if self._native_backward():
+                return self._native_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, False, False)
             return self._compute_ir_differentiable(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
         return self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, False)[0]
 
@@ -77,8 +79,31 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
             logmag = logmag + gain_env_log_magnitude[:, :, None, :]
         return torch.exp(logmag / 8)
 
+    def _native_backward(self):
+        """Whether the taps train on the native node (autograd.StftReverbIrFn: the FFT form, n_fft = 384 with hop = 192, the
+        reference's defaults).  Any other transform size keeps the torch chain of _compute_ir_differentiable under
+        gradients: there is no backward kernel for the matrix-core ("gemm") schedule."""
+        return self.n_fft == 384 and self.hop_length == 192
+
+    def _native_taps(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, ms_lr, normalise):
+        """The taps under autograd, one node: the inference kernel forward, gfx_stft_reverb_ir_bwd_f32 backward."""
+        genv = gain_env_log_magnitude if self.gain_envelope else None
+        noise = self.noise_stft if self.fixed_noise else self.sample_noise(init_log_magnitude.shape[0],
+                                                                          init_log_magnitude.device)
+        return diff.StftReverbIrFn.apply(init_log_magnitude, delta_log_magnitude, genv, noise, self.window,
+                                         self._istft_basis(init_log_magnitude.device), self.ir_len, self.hop_length,
+                                         ms_lr, normalise)
+
+    def _training_taps(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo):
+        """Normalised taps (R, 2, ir_len) with a gradient path to the parameters; left/right when ``pseudo``."""
+        if self._native_backward():
+            return self._native_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo, True)
+        ir = self._compute_ir_differentiable(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
+        return normalize_impulse(ms_to_lr(ir)) if pseudo else normalize_impulse(ir)
+
     def _compute_ir_differentiable(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None):
-        """reverb.py:161-200 with torch ops (mask, istft) for the training path."""
+        """reverb.py:161-200 with torch ops (mask, istft): the formula, and the training path of every transform size
+        but the default one (see _native_backward)."""
         logmag = init_log_magnitude[..., None] - F.softplus(delta_log_magnitude)[..., None] * self.arange
         if self.gain_envelope:
             logmag = logmag + gain_env_log_magnitude[:, :, None, :]
@@ -159,21 +184,20 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
                 expand_shared(t, reps) for t in (init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude))
             _shared_rows = None
         if needs_grad(input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude):
-            # training: mask + istft as torch ops on the GPU (R x 193 x 313), the convolution below is native either way
-            # the impulse responses are synthesised once per parameter row (per node when the batch shares them) and
-            # the native convolution lets every batch row read them; a strided (B, n, C, L) view is read in place
-            ir = self._compute_ir_differentiable(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
+            # training: the taps on one native node (autograd.StftReverbIrFn; other transform sizes: mask + istft as torch
+            # ops), the convolution below is native either way.  The impulse responses are synthesised once per parameter
+            # row (per node when the batch shares them) and the native convolution lets every batch row read them; a
+            # strided (B, n, C, L) view is read in place
+            h = self._training_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
             if pseudo:
-                y = diff.convolve(input_signals, normalize_impulse(ms_to_lr(ir)), "causal", exact=self.flashfftconv,
-                                  final=True)
+                y = diff.convolve(input_signals, h, "causal", exact=self.flashfftconv, final=True)
             elif self.processor_channel == "midside":
                 x = input_signals.reshape(-1, *input_signals.shape[-2:])
-                h = normalize_impulse(ir)
                 if h.shape[0] != x.shape[0]:
                     h = expand_shared(h, x.shape[0] // h.shape[0])
                 y = ms_to_lr(diff.convolve(lr_to_ms(x), h, "causal", exact=self.flashfftconv, final=True))
             else:
-                y = diff.convolve(input_signals, normalize_impulse(ir), "causal", exact=self.flashfftconv, final=True)
+                y = diff.convolve(input_signals, h, "causal", exact=self.flashfftconv, final=True)
             if _out is None:
                 return y
             _out.copy_(y.view(_out.shape))
@@ -198,8 +222,7 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         pseudo = self.processor_channel == "pseudo_midside"
         midside = self.processor_channel == "midside"
         if needs_grad(x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, state):
-            ir = self._compute_ir_differentiable(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
-            h = normalize_impulse(ms_to_lr(ir)) if pseudo else normalize_impulse(ir)
+            h = self._training_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
             xs = x.reshape(-1, *x.shape[-2:]) if midside else x
             if midside:
                 xs = lr_to_ms(xs)

@@ -512,6 +512,25 @@ int gfx_stft_reverb_ir_f32(const float* noise_stft, int64_t noise_rows, const fl
                            const float* window, const float* basis, float* ir, float* row_gain, int64_t R,
                            int64_t ir_len, int64_t n_fft, int64_t hop, int64_t num_frames, int ms_to_lr, void* ws,
                            size_t ws_bytes, int schedule, void* stream);
+/* Backward of gfx_stft_reverb_ir_f32 in its FFT form (n_fft = 384, hop = 192, num_frames = 1 + ir_len / 192; anything else
+ * is GFX_EINVAL): the gradients of the parameters from grad_ir = dL/dh (R, 2, ir_len), h the taps the forward call with the
+ * same noise, parameters, window, basis and ms_to_lr produced.
+ *   ir, row_gain both given: h = row_gain * ir (normalize_impulse applied), `ir` (R, 2, ir_len) and `row_gain` (R) being that
+ *                            forward call's outputs;  both null: h = ir, the un-normalised taps.
+ *   noise_stft / noise_rows, init, delta, gain_env (nullable), window, basis: as in the forward; the noise gets no gradient.
+ * Outputs, each nullable (not computed), not all of them: g_init, g_delta (R, 2, 193); g_gain_env (R, 2, num_frames), which
+ * needs gain_env.  Every element of a given output is written.
+ * One workgroup takes 16 frames of both channels of a row: a 192-point complex FFT per frame, frames and spectra stay in
+ * LDS.  Sums use no atomics: the per-workgroup bin sums and (normalised) the block sums of grad_ir * ir are stored in `ws`
+ * (gfx_stft_reverb_ir_bwd_ws_bytes: R * (ceil(2 ir_len / 4096) + ceil(num_frames / 16) * 4 * 193) floats) and added in
+ * double in a fixed order, so results are bit-identical from run to run.  Nothing is allocated or synchronised.
+ * R <= 32767 per call. */
+size_t gfx_stft_reverb_ir_bwd_ws_bytes(int64_t R, int64_t ir_len);
+int gfx_stft_reverb_ir_bwd_f32(const float* grad_ir, const float* ir, const float* row_gain, const float* noise_stft,
+                               int64_t noise_rows, const float* init_log_magnitude, const float* delta_log_magnitude,
+                               const float* gain_env_log_magnitude, const float* window, const float* basis,
+                               float* g_init, float* g_delta, float* g_gain_env, int64_t R, int64_t ir_len, int64_t n_fft,
+                               int64_t hop, int64_t num_frames, int ms_to_lr, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- routing ----------------------------------------------------------------------------
  * replaces read_single_tensor("index") + aggregate_tensor("sum"/"scatter") + inplace_write_tensor
