@@ -389,6 +389,7 @@ class FsmFirFn(torch.autograd.Function):
 
         h = irfft(resp),  resp = prod_i num_i / den_i,  num_i = sum_d B[i,d] D_d
         dL/dB[i,d] =  Re sum_k conj(G_k) resp_k D_d[k] / num_i[k],   G = (c_k / N) rfft(dL/dh),  c = (1, 2, 2, ...)
+                      (resp / num_i formed as prod_{j != i}(num_j / den_j) / den_i: num_i may be zero at a bin)
         dL/dA[i,d] = -Re sum_k conj(G_k) resp_k D_d[k] / den_i[k]
     """
 
@@ -426,21 +427,29 @@ class FsmFirFn(torch.autograd.Function):
         num = Bs[..., 0:1] * D[0] + Bs[..., 1:2] * D[1] + Bs[..., 2:3] * D[2]   # (R,Cf,K,F)
         den = As[..., 0:1] * D[0] + As[..., 1:2] * D[1] + As[..., 2:3] * D[2]
         sections = num / den
-        resp = sections[..., 0, :]
-        for i in range(1, sections.shape[-2]):
-            resp = resp * sections[..., i, :]
+        K = sections.shape[-2]
+        # others[i] = prod_{j != i} sections[j] (prefix times suffix products): resp / num_i without dividing by a numerator,
+        # which is exactly zero at a sampled bin for a section with a zero on the unit circle there (high-pass at k = 0)
+        one = torch.ones_like(sections[..., 0, :])
+        pre, suf = [one] * K, [one] * K
+        for i in range(1, K):
+            pre[i] = pre[i - 1] * sections[..., i - 1, :]
+            suf[K - 1 - i] = suf[K - i] * sections[..., K - i, :]
+        others = torch.stack([a * b for a, b in zip(pre, suf)], -2)     # (R,Cf,K,F)
+        resp = pre[K - 1] * sections[..., K - 1, :]
         if N > ops.IRDFT_MAX_N and gh.is_cuda:
             ops.fft_library_reached(f"gradient of frequency-sampled taps of {N} points")
         G = (ops.rdft(gh, N) if N <= ops.IRDFT_MAX_N else torch.fft.rfft(gh, n=N, dim=-1)).to(torch.complex128) * (2.0 / N)
         G[..., 0] = G[..., 0] * 0.5
         if N % 2 == 0:
             G[..., -1] = G[..., -1] * 0.5
-        T = (G.conj() * resp).unsqueeze(-2)                # (R,Cf,1,F)
+        Gc = G.conj().unsqueeze(-2)                        # (R,Cf,1,F)
+        T = Gc * resp.unsqueeze(-2)
 
         def contract(Q):  # Re sum_k Q[..., k] D_d[k], d = 0..2  ->  (..., 3)
             return torch.stack([(Q * D[d]).real.sum(-1) for d in range(3)], -1)
 
-        gB = contract(T / num).to(out_dtype) if want_B else None
+        gB = contract(Gc * others / den).to(out_dtype) if want_B else None
         gA = (-contract(T / den)).to(out_dtype) if want_A else None
         return gB, gA, None, None
 

@@ -373,6 +373,7 @@ namespace gfx {
 // 147-152, 263-276); autograd through it is
 //     dL/dB[i, d] =  Re sum_k T_k D_d[k] / num_i[k],     dL/dA[i, d] = -Re sum_k T_k D_d[k] / den_i[k],
 //     T_k = conj(G_k) w_k resp_k,   G = rfft(dL/dh),  w = (1, 2, ..., 2, [1 at N / 2]) / N
+// (T / num_i formed as conj(G) w prod_{j != i}(num_j / den_j) / den_i: num_i may be zero at a bin)
 // -- the sums over the bins cancel to a few 1e-5 of their terms, so everything here is double (as the torch form of rounds
 // 4-5 was: ~40 complex128 kernels per equaliser stage and step; this is one).  One workgroup per (filter row, section i):
 // every thread recomputes the response of its bins (K complex divisions) and keeps six sums.  `delays`: the (3, F)
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(256) void iir_fsm_bwd_kernel(const float* __restric
         double2 D[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) D[d] = make_double2((double)delays[d * F + k].x, (double)delays[d * F + k].y);
-        double2 resp = make_double2(1.0, 0.0), mynum = resp, myden = resp;
+        double2 resp = make_double2(1.0, 0.0), mynum = resp, myden = resp, others = resp;   // others = prod_{j != sec} num_j / den_j
         for (int i = 0; i < K; ++i) {
             double2 num = make_double2(0.0, 0.0), den = num;
 #pragma unroll
@@ -404,13 +405,17 @@ __global__ __launch_bounds__(256) void iir_fsm_bwd_kernel(const float* __restric
             const double2 q = make_double2((num.x * den.x + num.y * den.y) / dd, (num.y * den.x - num.x * den.y) / dd);
             resp = make_double2(resp.x * q.x - resp.y * q.y, resp.x * q.y + resp.y * q.x);
             if (i == sec) { mynum = num; myden = den; }
+            else others = make_double2(others.x * q.x - others.y * q.y, others.x * q.y + others.y * q.x);
         }
         const double w = ((k == 0 || (!(N & 1) && k == N / 2)) ? 1.0 : 2.0) / (double)N;
         const float2 g = G[rc * F + k];
         // T = conj(G) w resp
         const double2 T = make_double2(w * ((double)g.x * resp.x + (double)g.y * resp.y), w * ((double)g.x * resp.y - (double)g.y * resp.x));
-        const double nn = mynum.x * mynum.x + mynum.y * mynum.y, dn = myden.x * myden.x + myden.y * myden.y;
-        const double2 tn = make_double2((T.x * mynum.x + T.y * mynum.y) / nn, (T.y * mynum.x - T.x * mynum.y) / nn);   // T / num
+        // T / num_sec = conj(G) w others / den_sec: never divided by the numerator, which is exactly zero at a sampled bin
+        // for a section with a zero on the unit circle there (high-pass at k = 0, low-pass at N / 2, band-pass at both)
+        const double2 U = make_double2(w * ((double)g.x * others.x + (double)g.y * others.y), w * ((double)g.x * others.y - (double)g.y * others.x));
+        const double dn = myden.x * myden.x + myden.y * myden.y;
+        const double2 tn = make_double2((U.x * myden.x + U.y * myden.y) / dn, (U.y * myden.x - U.x * myden.y) / dn);   // T / num
         const double2 td = make_double2((T.x * myden.x + T.y * myden.y) / dn, (T.y * myden.x - T.x * myden.y) / dn);   // T / den
 #pragma unroll
         for (int d = 0; d < 3; ++d) {

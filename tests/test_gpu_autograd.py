@@ -274,6 +274,8 @@ def test_native_ballistics_backward_matches_torch_autograd_of_the_recursion(L):
 
 @pytest.mark.gpu
 def test_compressor_with_ballistics_smoother_trains():
+    """Finite, non-zero gradients only; their values are held to the reference's in tests/test_gpu_training_paths.py
+    (comp_ballistics_hard_L4099, comp_ballistics_quadratic_L1023)."""
     import torch
 
     import grafx_amd.processors as P
@@ -343,6 +345,38 @@ def test_fsm_taps_backward_matches_torch_autograd(N):
     tB, tA, _, _ = diff.FsmFirFn.backward_torch(Bs.detach(), As.detach(), w, N)
     for g, t, name in zip(got, (tB, tA), ("Bs", "As")):
         assert (g - t).abs().max() <= 2e-6 * t.abs().max(), (name, float((g - t).abs().max() / t.abs().max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [256, 257])
+def test_fsm_taps_backward_with_a_numerator_zero_on_a_sampled_bin(N):
+    """Sections whose numerator vanishes exactly at a sampled bin -- (1 - z^-1)^2 at k = 0 (high-pass), (1 + z^-1)^2 at
+    k = N / 2 (low-pass, even N), 1 - z^-2 at both (band-pass) -- next to an ordinary one: the adjoint must not divide by
+    the numerator (it returned NaN for every such section).  Against torch autograd of core/iir.py:147-150 in float64,
+    and the native launch against the torch form of the same adjoint."""
+    import torch
+
+    from grafx_amd import autograd as diff
+    from grafx_amd.processors import IIRFilter
+
+    torch.manual_seed(N)
+    num = torch.tensor([[1.0, -2.0, 1.0], [1.0, 2.0, 1.0], [0.5, 0.0, -0.5], [1.0, 0.3, 0.2]], device="cuda")
+    K = num.shape[0]
+    for k in (1, K):   # a lone section (no other factor to multiply) and a cascade
+        Bs = num[:k].expand(2, 1, k, 3).clone().requires_grad_(True)
+        As = (torch.tensor([1.0, -1.2, 0.5], device="cuda").expand(2, 1, k, 3) + 0.05 * torch.randn(2, 1, k, 3, device="cuda"))
+        As = As.detach().requires_grad_(True)
+        w = torch.randn(2, 1, N, device="cuda")
+        f = IIRFilter(flashfftconv=False, fsm_fir_len=N).cuda()
+        h = diff.FsmFirFn.apply(Bs, As, N, f._plan(Bs.device))
+        B64, A64 = Bs.detach().double().requires_grad_(True), As.detach().double().requires_grad_(True)
+        got = torch.autograd.grad((h * w).sum(), (Bs, As))
+        want = torch.autograd.grad((diff.fsm_fir(B64, A64, N) * w.double()).sum(), (B64, A64))
+        tB, tA, _, _ = diff.FsmFirFn.backward_torch(Bs.detach(), As.detach(), w, N)
+        for g, wv, t, name in zip(got, want, (tB, tA), ("Bs", "As")):
+            assert torch.isfinite(g).all() and torch.isfinite(t).all(), (name, k)
+            assert_close(g.cpu(), wv.float().cpu(), GRAD_TOL["fsm taps"], f"fsm taps grad {name} N={N} K={k}, zeros on the unit circle")
+            assert (g - t).abs().max() <= 2e-6 * t.abs().max(), (name, float((g - t).abs().max() / t.abs().max()))
 
 
 @pytest.mark.gpu
