@@ -1,0 +1,204 @@
+"""What every wrapper of :mod:`grafx_amd.ops` goes through before its launch: the device and stream plumbing, the
+per-launch timing hook, and the checks of the tensors whose pointers are passed.  The kernels trust their sizes, and a
+RowMap carries strides only, so a destination, a carried state or a workspace is checked or made here, once, and
+nowhere else."""
+import contextvars
+import functools
+
+import torch
+
+from ._lib import RowMap, lib
+
+
+# Per-launch timing hook: `with ops.profiling() as prof:` collects (start_event, end_event, algorithmic_bytes) per kernel
+# launch issued from the current context (bench.py's live roofline measurement).  A ContextVar, not a module global:
+# another thread rendering at the same time neither pays for the events nor pollutes the record.
+_PROFILE = contextvars.ContextVar("grafx_amd_profile", default=None)
+
+
+class profiling:
+    def __enter__(self):
+        self.record = {}
+        self.token = _PROFILE.set(self.record)
+        return self.record
+
+    def __exit__(self, *exc):
+        _PROFILE.reset(self.token)
+        return False
+
+
+class _timed:
+    """``last``: name of the library's ``gfx_*_last_kernel`` entry when the record is keyed by the kernel that ran, as a
+    profile prints it (asked for only under a profile, and only when the block ended without an error; a block that
+    launched nothing of its own sets ``t.last = None``)."""
+
+    def __init__(self, name, nbytes, last=None):
+        self.name, self.nbytes, self.last = name, nbytes, last
+
+    def __enter__(self):
+        self.rec = _PROFILE.get()
+        if self.rec is not None:
+            self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.a.record()
+        return self
+
+    def __exit__(self, *exc):
+        if self.rec is not None:
+            self.b.record()
+            if self.last is not None and exc[0] is None:
+                self.name = getattr(lib(), self.last)().decode()
+            self.rec.setdefault(self.name, []).append((self.a, self.b, self.nbytes))
+
+
+def _require_gpu(*tensors):
+    for t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(
+                "grafx_amd processors run on the MI355X only (got a CPU tensor); there is no CPU fallback. "
+                "Move signals and parameters to the GPU, or use the reference/oracle on CPU."
+            )
+        if t.dtype != torch.float32:
+            raise TypeError(f"grafx_amd kernels compute in float32, got {t.dtype}")
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+class _Pin:
+    """Pointer factory for ONE launch: ``pin(t)`` returns the device address of a contiguous version of ``t`` and
+    keeps that (possibly temporary) tensor referenced until the wrapper returns, i.e. until the launch is enqueued.
+    Taking ``data_ptr()`` of an unnamed ``.contiguous()`` result frees the temporary before the launch; the next
+    same-size temporary then reuses the block and two arguments silently alias (round-1 advisor finding)."""
+
+    def __init__(self):
+        self.keep = []
+        self.ws = None
+
+    def __call__(self, t):
+        if t is None:
+            return 0
+        t = t.contiguous()
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def workspace(self, nbytes, device, zero=False):
+        """The (pointer, byte count) pair of the launch's workspace: ``nbytes`` fresh bytes, kept as ``pin.ws`` until the
+        wrapper returns, or (0, 0) for no workspace (``nbytes`` 0 or False).  ``zero``: zero-filled."""
+        if not nbytes:
+            return 0, 0
+        self.ws = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=device)
+        return self.ws.data_ptr(), nbytes
+
+
+def _on_device(fn):
+    """Run a wrapper with the tensors' device current: the stream handed to the library (``_stream()``) and the
+    library's per-device tables (``hipGetDevice`` in csrc/common.hip) both follow the *current* device, so tensors on
+    cuda:1 under a current device cuda:0 would be launched on the wrong device.  All tensor arguments must share
+    one device."""
+
+    @functools.wraps(fn)
+    def run(*args, **kwargs):
+        dev = None
+        for a in (*args, *kwargs.values()):
+            if isinstance(a, torch.Tensor) and a.is_cuda:
+                if dev is None:
+                    dev = a.device
+                elif a.device != dev:
+                    raise ValueError(f"{fn.__name__}: tensors on different devices ({dev} and {a.device})")
+        if dev is None or dev.index == torch.cuda.current_device():
+            return fn(*args, **kwargs)
+        with torch.cuda.device(dev):
+            return fn(*args, **kwargs)
+
+    return run
+
+
+def _expect(t, shape, what):
+    """The kernels trust their sizes: every secondary tensor's shape is checked here, before its pointer is passed."""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def rowmap(t):
+    """RowMap for a (R, C, L) tensor or a (B, n, C, L) view whose last dim is contiguous.
+
+    Lets kernels address slices of render_grafx's signal buffer in place.
+    Returns (RowMap, R, C, L).
+    """
+    if t.stride(-1) != 1:
+        raise ValueError("last dimension must be contiguous")
+    if t.ndim == 3:
+        R, C, L = t.shape
+        return RowMap(max(R, 1), 0, t.stride(0), t.stride(1)), R, C, L
+    if t.ndim == 4:
+        B, n, C, L = t.shape
+        return RowMap(max(n, 1), t.stride(0), t.stride(1), t.stride(2)), B * n, C, L
+    raise ValueError(f"expected a 3-D or 4-D signal tensor, got {t.ndim}-D")
+
+
+def _overlap(a, b):
+    """Whether two float32 tensors share an element.  Exact for views of one storage with the same shape and (nested)
+    strides -- two node ranges of the render's (B, V, C, L) buffer interleave in memory without touching --, the bounding
+    ranges otherwise."""
+    if a.numel() == 0 or b.numel() == 0 or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+    if a.shape == b.shape and a.stride() == b.stride() and all(st > 0 for st in a.stride()):
+        dims = sorted(((st, n) for n, st in zip(a.shape, a.stride()) if n > 1), reverse=True)
+
+        def reachable(delta, i):      # delta = sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on?
+            if i == len(dims):
+                return delta == 0
+            st, n = dims[i]
+            q = delta // st
+            return any(abs(c) < n and reachable(abs(delta - c * st), i + 1) for c in (q, q + 1))
+
+        return reachable(abs(a.storage_offset() - b.storage_offset()), 0)
+
+    def span(t):
+        lo = t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride()) if st < 0)
+        return lo, lo + 1 + sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride()))
+
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def _output(out, shape, device, what, longer=False, apart=()):
+    """The destination of an entry that writes (R, C, L) = ``shape`` -> (out, its RowMap): a new float32 tensor when
+    ``out`` is None, else the caller's (R, C, L) tensor or strided (B, n, C, L) view -- the same rows and channels, unit
+    last stride, and the same length (``longer``: at least that length).  ``apart``: tensors ``out`` must share no element
+    with, for kernels that read them again after writing.  A RowMap carries strides only: the library cannot see a short
+    destination, so it is refused here, before any pointer is taken."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+        return out, rowmap(out)[0]
+    omap, R, C, L = rowmap(out)
+    if (R, C) != tuple(shape[:2]) or (L < shape[2] if longer else L != shape[2]):
+        raise ValueError(f"{what}: out {tuple(out.shape)} does not match rows={shape[0]}, channels={shape[1]}, "
+                         f"length{'>=' if longer else '='}{shape[2]}")
+    if any(_overlap(t, out) for t in apart):
+        raise ValueError(f"{what}: out must not share memory with the input (the kernel makes more than one pass over it)")
+    return out, omap
+
+
+def _state(z, shape, what, name):
+    """A carried state (``zi`` / ``zf``) of a stateful entry: None, or a contiguous float32 GPU tensor of exactly
+    ``shape`` -- the kernels read and write it in place through plain pointers."""
+    if z is None:
+        return None
+    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or tuple(z.shape) != tuple(shape) \
+            or not z.is_contiguous():
+        got = f"{tuple(z.shape)} {z.dtype} on {z.device}" if isinstance(z, torch.Tensor) else type(z).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous float32 GPU tensor of shape {tuple(shape)}, got {got}")
+    return z
+
+
+def _row_chunks(rows, limit):
+    """(first row, count) of the launches that take ``rows`` rows ``limit`` at a time (rows ride on a grid dimension)."""
+    return ((i, min(limit, rows - i)) for i in range(0, rows, limit))

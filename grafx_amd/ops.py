@@ -5,132 +5,15 @@ stream to libgrafx_amd.so and return torch tensors.  torch is only the memory
 and stream plumbing; all arithmetic happens in the HIP kernels.  CPU tensors are
 rejected: there is no fallback path.
 """
-import contextvars
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
 from ._lib import RowMap, check, lib
-
-
-# Per-launch timing hook: `with ops.profiling() as prof:` collects (start_event, end_event, algorithmic_bytes) per kernel
-# launch issued from the current context (bench.py's live roofline measurement).  A ContextVar, not a module global:
-# another thread rendering at the same time neither pays for the events nor pollutes the record.
-_PROFILE = contextvars.ContextVar("grafx_amd_profile", default=None)
-
-
-class profiling:
-    def __enter__(self):
-        self.record = {}
-        self.token = _PROFILE.set(self.record)
-        return self.record
-
-    def __exit__(self, *exc):
-        _PROFILE.reset(self.token)
-        return False
-
-
-class _timed:
-    def __init__(self, name, nbytes):
-        self.name, self.nbytes = name, nbytes
-
-    def __enter__(self):
-        self.rec = _PROFILE.get()
-        if self.rec is not None:
-            self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.a.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.rec is not None:
-            self.b.record()
-            self.rec.setdefault(self.name, []).append((self.a, self.b, self.nbytes))
-
-
-def _require_gpu(*tensors):
-    for t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(
-                "grafx_amd processors run on the MI355X only (got a CPU tensor); there is no CPU fallback. "
-                "Move signals and parameters to the GPU, or use the reference/oracle on CPU."
-            )
-        if t.dtype != torch.float32:
-            raise TypeError(f"grafx_amd kernels compute in float32, got {t.dtype}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-class _Pin:
-    """Pointer factory for ONE launch: ``pin(t)`` returns the device address of a contiguous version of ``t`` and
-    keeps that (possibly temporary) tensor referenced until the wrapper returns, i.e. until the launch is enqueued.
-    Taking ``data_ptr()`` of an unnamed ``.contiguous()`` result frees the temporary before the launch; the next
-    same-size temporary then reuses the block and two arguments silently alias (round-1 advisor finding)."""
-
-    def __init__(self):
-        self.keep = []
-
-    def __call__(self, t):
-        if t is None:
-            return 0
-        t = t.contiguous()
-        self.keep.append(t)
-        return t.data_ptr()
-
-
-def _on_device(fn):
-    """Run a wrapper with the tensors' device current: the stream handed to the library (``_stream()``) and the
-    library's per-device tables (``hipGetDevice`` in csrc/common.hip) both follow the *current* device, so tensors on
-    cuda:1 under a current device cuda:0 would be launched on the wrong device.  All tensor arguments must share
-    one device."""
-    import functools
-
-    @functools.wraps(fn)
-    def run(*args, **kwargs):
-        dev = None
-        for a in (*args, *kwargs.values()):
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                if dev is None:
-                    dev = a.device
-                elif a.device != dev:
-                    raise ValueError(f"{fn.__name__}: tensors on different devices ({dev} and {a.device})")
-        if dev is None or dev.index == torch.cuda.current_device():
-            return fn(*args, **kwargs)
-        with torch.cuda.device(dev):
-            return fn(*args, **kwargs)
-
-    return run
-
-
-def _expect(t, shape, what):
-    """The kernels trust their sizes: every secondary tensor's shape is checked here, before its pointer is passed."""
-    if t is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-
-
-def rowmap(t):
-    """RowMap for a (R, C, L) tensor or a (B, n, C, L) view whose last dim is contiguous.
-
-    Lets kernels address slices of render_grafx's signal buffer in place.
-    Returns (RowMap, R, C, L).
-    """
-    if t.stride(-1) != 1:
-        raise ValueError("last dimension must be contiguous")
-    if t.ndim == 3:
-        R, C, L = t.shape
-        return RowMap(max(R, 1), 0, t.stride(0), t.stride(1)), R, C, L
-    if t.ndim == 4:
-        B, n, C, L = t.shape
-        return RowMap(max(n, 1), t.stride(0), t.stride(1), t.stride(2)), B * n, C, L
-    raise ValueError(f"expected a 3-D or 4-D signal tensor, got {t.ndim}-D")
+from ._plumbing import (_expect, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks, _state,  # noqa: F401
+                        _stream, _timed, profiling, rowmap)
 
 
 # ----------------------------------------------------------------------------------------- FIR conv
@@ -186,6 +69,7 @@ def fftconv_can_tee(Cin, Cf, L, Lout, off, N):
 
 GFX_EINVAL = -1                                  # include/grafx_amd.h
 GRID_YZ_MAX = 65535                              # workgroups along the second / third dimension of one launch
+GRID_ROWS_I16_MAX = 32767                        # rows per launch of the kernels whose grids index rows in 16 bits (reverb)
 SCHEDULES = {"auto": 0, "tile": 1, "pipe": 2}   # GFX_SCHED_* of include/grafx_amd.h
 # What `schedule="auto"` means to fftconv(): "auto" (the library decides: the persistent hand-scheduled kernel for large
 # launches it covers) or "pipe" (prefer that kernel at every size it covers -- tests and latency experiments).
@@ -237,15 +121,11 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
     Lout = L if Lout is None else Lout
     Cout = max(Cin, Cf)
     h_rows = R if h_rows is None else h_rows
-    if out is None:
-        out = torch.empty((R, Cout, Lout), dtype=torch.float32, device=x.device)
-    ymap, Ry, Cy, Ly = rowmap(out)
-    if (Ry, Cy) != (R, Cout) or Ly < Lout:
-        raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={Lout}")
+    out, ymap = _output(out, (R, Cout, Lout), x.device, "fftconv", longer=True)
     if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, part_len):
         raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
-    nbytes = lib().gfx_fftconv_workspace_bytes(R, Cin, L, Lout, off, N, part_len)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    pin = _Pin()
+    ws = pin.workspace(lib().gfx_fftconv_workspace_bytes(R, Cin, L, Lout, off, N, part_len), x.device)
     cmap = RowMap(1, 0, 0, 0)
     if tee is not None:
         cmap, Rc, Cc, Lc = rowmap(tee)
@@ -257,10 +137,11 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
 
     def launch(sched):
         return lib().gfx_fftconv_f32(_ptr(x), xmap, _ptr(Hs), h_rows, part_len, _ptr(out), ymap, _ptr(tee), cmap, R, Cin, Cf,
-                                     L, Lout, off, N, _ptr(ws), nbytes, SCHEDULES[sched], _ptr(words),
+                                     L, Lout, off, N, *ws, SCHEDULES[sched], _ptr(words),
                                      ctypes.byref(written) if want_max else None, _stream())
 
-    with _timed("fftconv", 4 * R * ((2 if tee is not None else 1) * Cin * L + Cout * Lout)) as t:
+    # the record is keyed by the kernel's own name, as a profile prints it
+    with _timed("fftconv", 4 * R * ((2 if tee is not None else 1) * Cin * L + Cout * Lout), last="gfx_fftconv_last_kernel"):
         rc = GFX_EINVAL
         if schedule == "auto" and FFTCONV_SCHEDULE == "pipe":
             rc = launch("pipe")
@@ -268,24 +149,9 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
                 check(rc, "gfx_fftconv_f32 (pipe)")   # a failed launch / code-object load must not be masked
         if rc != 0:
             check(launch(schedule), "gfx_fftconv_f32")
-        if t.rec is not None:             # the record is keyed by the kernel's own name, as a profile prints it
-            t.name = lib().gfx_fftconv_last_kernel().decode()
     if written.value:
         rowmax["words"] = words
     return out
-
-
-def _fir_state(z, shape, what, name):
-    """A carried input history of the stateful convolution: a contiguous float32 GPU tensor (R, C_in, N - 1), oldest sample
-    first.  The kernels read it in place through plain pointers."""
-    if z is None:
-        return None
-    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or tuple(z.shape) != tuple(shape) \
-            or not z.is_contiguous():
-        got = f"{tuple(z.shape)} {z.dtype} on {z.device}" if isinstance(z, torch.Tensor) else type(z).__name__
-        raise ValueError(f"{what}: {name} must be a contiguous float32 GPU tensor of shape {tuple(shape)} "
-                         f"(rows, input channels, taps - 1; oldest sample first), got {got}")
-    return z
 
 
 @_on_device
@@ -307,28 +173,22 @@ def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=Tru
     xmap, R, Cin, L = rowmap(x)
     Cout = max(Cin, Cf)
     h_rows = R if h_rows is None else h_rows
-    if out is None:
-        out = torch.empty((R, Cout, L), dtype=torch.float32, device=x.device)
-    ymap, Ry, Cy, Ly = rowmap(out)
-    if (Ry, Cy) != (R, Cout) or Ly < L:
-        raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={L}")
+    out, ymap = _output(out, (R, Cout, L), x.device, "fftconv_state", longer=True)
     if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, 0):
         raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
-    shape = (R, Cin, N - 1)
-    zi = _fir_state(zi, shape, "fftconv_state", "zi")
-    zf = _fir_state(zf, shape, "fftconv_state", "zf")
+    shape = (R, Cin, N - 1)      # rows, input channels, taps - 1: the input history, oldest sample first
+    zi = _state(zi, shape, "fftconv_state", "zi")
+    zf = _state(zf, shape, "fftconv_state", "zf")
     if zf is None and return_state:
         zf = torch.empty(shape, dtype=torch.float32, device=x.device)
     if zi is not None and zf is not None and _overlap(zi, zf):
         raise ValueError("fftconv_state: zf must not share memory with zi (the state is written while the history may "
                          "still be read)")
-    nbytes = lib().gfx_fftconv_workspace_bytes(R, Cin, L, L, 0, N, 0)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    with _timed("fftconv", 4 * R * (Cin * (L + 2 * (N - 1)) + Cout * L)) as t:
+    pin = _Pin()
+    ws = pin.workspace(lib().gfx_fftconv_workspace_bytes(R, Cin, L, L, 0, N, 0), x.device)
+    with _timed("fftconv", 4 * R * (Cin * (L + 2 * (N - 1)) + Cout * L), last="gfx_fftconv_last_kernel"):
         check(lib().gfx_fftconv_state_f32(_ptr(x), xmap, _ptr(Hs), h_rows, _ptr(out), ymap, _ptr(zi), _ptr(zf), R, Cin, Cf, L,
-                                          N, _ptr(ws), nbytes, SCHEDULES[schedule], _stream()), "gfx_fftconv_state_f32")
-        if t.rec is not None:
-            t.name = lib().gfx_fftconv_last_kernel().decode()
+                                          N, *ws, SCHEDULES[schedule], _stream()), "gfx_fftconv_state_f32")
     return out, zf
 
 
@@ -345,11 +205,7 @@ def fir_direct(x, h, Lout=None, off=0, out=None, h_rows=None):
         raise ValueError(f"fir_direct: {hr} filter rows given, h_rows={h_rows}")
     Lout = L if Lout is None else Lout
     Cout = max(Cin, Cf)
-    if out is None:
-        out = torch.empty((R, Cout, Lout), dtype=torch.float32, device=x.device)
-    ymap, Ry, Cy, Ly = rowmap(out)
-    if (Ry, Cy) != (R, Cout) or Ly < Lout:
-        raise ValueError(f"output shape {tuple(out.shape)} does not match rows={R}, channels={Cout}, length>={Lout}")
+    out, ymap = _output(out, (R, Cout, Lout), x.device, "fir_direct", longer=True)
     with _timed("fir_mfma_kernel", 4 * R * (Cin * L + Cout * Lout)):
         check(lib().gfx_fir_direct_f32(_ptr(x), xmap, _ptr(h), h_rows, _ptr(out), ymap, R, Cin, Cf, L, Lout, off, N, _stream()),
               "gfx_fir_direct_f32")
@@ -407,8 +263,7 @@ def rdft(x, n=None):
     flat = x.reshape(-1, n).contiguous()
     rows = flat.shape[0]
     X = torch.empty((rows, K, 2), dtype=torch.float32, device=x.device)
-    for i in range(0, rows, 65535):     # rows ride on a grid dimension
-        m = min(65535, rows - i)
+    for i, m in _row_chunks(rows, GRID_YZ_MAX):
         check(lib().gfx_rdft_f32(_ptr(flat[i:]), _ptr(X[i:]), m, K, n, _stream()), "gfx_rdft_f32")
     return torch.view_as_complex(X).view(*x.shape[:-1], K)
 
@@ -441,12 +296,15 @@ ALIAS_ROWS_PER_CHUNK = int(os.environ.get("GRAFX_ALIAS_ROWS", "1024"))   # rows 
 ALIAS_ONE_ROW_MAX = 16383    # rows one call of gfx_odd_alias_f32 / _adjoint_f32 accepts (csrc/czt.hip: czt_alias)
 
 
+_AliasFns = namedtuple("_AliasFns", "plan_bytes workspace_bytes plan forward adjoint tag")
+
+
 def _alias_fns(precise, pairs=False):
-    """(plan_bytes, workspace_bytes, plan, forward, adjoint, tag) of the fp32 or the double-precision transforms; ``pairs``:
-    the two-rows-per-transform forms (forward only: adjoint is None)."""
+    """The entries of the fp32 or the double-precision transforms and the prefix of their names; ``pairs``: the
+    two-rows-per-transform forms (forward only: adjoint is None)."""
     L, tag = lib(), "gfx_odd_alias_" + ("pair_" if pairs else "") + ("precise_" if precise else "")
-    return (getattr(L, tag + "plan_bytes"), getattr(L, tag + "workspace_bytes"), getattr(L, tag + "plan_f32"),
-            getattr(L, tag + "f32"), None if pairs else getattr(L, tag + "adjoint_f32"), tag)
+    return _AliasFns(getattr(L, tag + "plan_bytes"), getattr(L, tag + "workspace_bytes"), getattr(L, tag + "plan_f32"),
+                     getattr(L, tag + "f32"), None if pairs else getattr(L, tag + "adjoint_f32"), tag)
 
 
 def _alias_pairs(P, rows):
@@ -456,7 +314,7 @@ def _alias_pairs(P, rows):
 
 def _alias_plan(P, device, precise=False, pairs=False):
     """The per-P chirp plan of the aliasing kernels (LRU of _ALIAS_PLANS_MAX, built on first use)."""
-    plan_bytes, ws_bytes, build, _, _, tag = _alias_fns(precise, pairs)
+    fns = _alias_fns(precise, pairs)
     key = (P, device.type, device.index, bool(precise), bool(pairs))
     plan = _ALIAS_PLANS.pop(key, None)
     if plan is not None:
@@ -465,9 +323,9 @@ def _alias_plan(P, device, precise=False, pairs=False):
         if torch.cuda.is_current_stream_capturing():
             # a plan built during capture would live in the graph's private pool and be rebuilt on every replay
             raise RuntimeError(f"odd_alias: no plan for P={P} yet; run the call once outside the HIP-graph capture")
-        plan = torch.empty(plan_bytes(P), dtype=torch.uint8, device=device)
-        w1 = torch.empty(ws_bytes(1, P), dtype=torch.uint8, device=device)
-        check(build(_ptr(plan), P, _ptr(w1), w1.numel(), _stream()), tag + "plan_f32")
+        plan = torch.empty(fns.plan_bytes(P), dtype=torch.uint8, device=device)
+        w1 = torch.empty(fns.workspace_bytes(1, P), dtype=torch.uint8, device=device)
+        check(fns.plan(_ptr(plan), P, _ptr(w1), w1.numel(), _stream()), fns.tag + "plan_f32")
         torch.cuda.current_stream(device).synchronize()   # the cached plan is complete before any stream can pick it up
         _ALIAS_PLANS[key] = plan
         while len(_ALIAS_PLANS) > _ALIAS_PLANS_MAX:
@@ -510,8 +368,7 @@ def set_alias_workspace_cap(nbytes):
     return old
 
 
-def _alias_chunks(rows, P, rows_per_chunk, device, precise, pairs=False):
-    ws_bytes = _alias_fns(precise, pairs)[1]
+def _alias_chunks(rows, P, rows_per_chunk, device, ws_bytes, pairs=False):
     cap = ALIAS_WS_CAP
     if not torch.cuda.is_current_stream_capturing():
         # free to this process = what the driver has left + what torch's caching allocator holds without using it
@@ -552,8 +409,8 @@ def odd_alias(z, lo=0, length=None, rows_per_chunk=None, precise=False, out=None
     rows_per_chunk = ALIAS_ROWS_PER_CHUNK if rows_per_chunk is None else rows_per_chunk
     pairs = _alias_pairs(P, rows)
     plan = _alias_plan(P, z.device, precise, pairs)
-    fwd, tag = _alias_fns(precise, pairs)[3], _alias_fns(precise, pairs)[5]
-    chunk, ws = _alias_chunks(rows, P, rows_per_chunk, z.device, precise, pairs)
+    fns = _alias_fns(precise, pairs)
+    chunk, ws = _alias_chunks(rows, P, rows_per_chunk, z.device, fns.workspace_bytes, pairs)
     if rowmax is not None and (not pairs or rowmax.numel() != rows or rowmax.dtype != torch.int32 or not rowmax.is_cuda):
         rowmax = None
     if relu and not (pairs and precise and out is None):
@@ -572,14 +429,13 @@ def odd_alias(z, lo=0, length=None, rows_per_chunk=None, precise=False, out=None
     # one record per chunk: the column / tile / column passes of the two chirp-z transforms (czt.hip), read z + write y
     name = (("czt_pair_in_kernel+czt_rows_kernel+czt_pair_mid_kernel+czt_pair_out_kernel" if pairs
              else "czt_cols_fwd_kernel+czt_rows_kernel+czt_cols_inv_kernel") + ("<double>" if precise else "<float>"))
-    for i in range(0, rows, chunk):
-        n = min(chunk, rows - i)
+    for i, n in _row_chunks(rows, chunk):
         rm = None if rowmax is None else rowmax[i : i + n].data_ptr()
         # what follows the workspace in the entry's list: the double forms take no row map, the one-row forms no maxima
         tail = ((rm, int(relu)) if pairs else ()) if precise else (omap, Co, i) + ((rm,) if pairs else ())
         with _timed(name, 4 * n * (P + length)):
-            check(fwd(_ptr(flat[i : i + n]), _ptr(out if into else out[i : i + n]), length, lo, length, n, P, _ptr(plan),
-                      _ptr(ws), ws.numel(), *tail, _stream()), tag + "f32")
+            check(fns.forward(_ptr(flat[i : i + n]), _ptr(out if into else out[i : i + n]), length, lo, length, n, P,
+                              _ptr(plan), _ptr(ws), ws.numel(), *tail, _stream()), fns.tag + "f32")
     return out if into else out.view(*z.shape[:-1], length)
 
 
@@ -590,20 +446,18 @@ def odd_alias_adjoint(gy, P, lo=0, rows_per_chunk=1024, precise=False):
     _require_gpu(gy)
     length = gy.shape[-1]
     plan = _alias_plan(P, gy.device, precise)
-    adj, tag = _alias_fns(precise)[4], _alias_fns(precise)[5]
+    fns = _alias_fns(precise)
     flat = gy.reshape(-1, length).contiguous()
     rows = flat.shape[0]
     out = torch.empty((rows, P), dtype=torch.float32, device=gy.device)
-    chunk, ws = _alias_chunks(rows, P, rows_per_chunk, gy.device, precise)
-    for i in range(0, rows, chunk):
-        n = min(chunk, rows - i)
-        check(adj(_ptr(flat[i : i + n]), length, lo, length, _ptr(out[i : i + n]), n, P, _ptr(plan), _ptr(ws), ws.numel(),
-                  _stream()), tag + "adjoint_f32")
+    chunk, ws = _alias_chunks(rows, P, rows_per_chunk, gy.device, fns.workspace_bytes)
+    for i, n in _row_chunks(rows, chunk):
+        check(fns.adjoint(_ptr(flat[i : i + n]), length, lo, length, _ptr(out[i : i + n]), n, P, _ptr(plan), _ptr(ws),
+                          ws.numel(), _stream()), fns.tag + "adjoint_f32")
     return out.view(*gy.shape[:-1], P)
 
 
 # ----------------------------------------------------------------------------------------- IIR (FSM)
-@_on_device
 def iir_fsm_native(N):
     """Whether the library has a native tap kernel for fsm_fir_len = N (1..4096, 8192, 16384)."""
     return bool(lib().gfx_iir_fsm_native(N))
@@ -721,6 +575,11 @@ def _rowvec(p, R):
     return p
 
 
+def _curve(pin, log_threshold, log_ratio, log_knee, P):
+    """The pointers of the compressor curve's three per-row parameters (P rows each), in the entries' order."""
+    return pin(_rowvec(log_threshold, P)), pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P))
+
+
 # Default schedule of dynamics_fused: "oneshot" hands the library a workspace, with which the smoothed configuration runs
 # as dependency-free 1024-sample tiles for every row whose smoother memory is short (decided per row on the device,
 # gfx_dynamics_fused_f32) and as one workgroup per row for the others; "rows" forces one workgroup per row.
@@ -767,6 +626,27 @@ def mix_schedule(dest_sources, n):
             list(zip(post, codes[len(pre) + n :])))
 
 
+_Mix = namedtuple("_Mix", "out sched n_acc extras n_pre n_post skip_rows")
+
+
+def _read_mix(mix, B, n, C, L):
+    """The ``mix`` dictionary of :func:`dynamics_fused` / :func:`stereo_gain` behind a (B, n, ., L) stage that writes C
+    channels -> its values (``n_post``: the extras behind the stage's rows), or None when ``mix["out"]`` is no (B, J, C, L)
+    view with a unit last stride or the schedule does not hold n codes."""
+    mo, sched, ex = mix["out"], mix["sched"], mix.get("extras")
+    if mo.shape != (B, mo.shape[1], C, L) or mo.stride(-1) != 1 or sched.numel() != n:
+        return None
+    n_pre = mix.get("n_pre", 0)
+    return _Mix(mo, sched, mix["n_acc"], ex, n_pre, (0 if ex is None else ex.shape[0]) - n_pre, bool(mix.get("skip_rows")))
+
+
+def _mix_args(m, n):
+    """What the fused-mix entries take of a :func:`_read_mix` result, in their order (a mono sum has no channel stride)."""
+    mo = m.out
+    return (_ptr(m.sched), n, m.n_acc, _ptr(mo), mo.stride(0), mo.stride(1), mo.stride(2) if mo.shape[2] == 2 else 0,
+            _ptr(m.extras), m.n_pre, m.n_post)
+
+
 @_on_device
 def dynamics_fused(x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir_len, knee, gate, out=None,
                    param_rows=None, schedule=None, u1_out=None, mix=None):
@@ -785,47 +665,37 @@ def dynamics_fused(x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir
     _require_gpu(x, out)
     xmap, R, C, L = rowmap(x)
     P = R if param_rows is None else param_rows
-    if out is None:
-        out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
-    ymap = rowmap(out)[0]
+    out, ymap = _output(out, (R, C, L), x.device, "dynamics_fused")
     pin = _Pin()
     if u1_out is not None:
         _require_gpu(u1_out)
         _expect(u1_out, (R, L), "dynamics_fused: u1_out")
         if not u1_out.is_contiguous() or smoother != 1:
             raise ValueError("dynamics_fused: u1_out must be contiguous and needs the one-pole smoother")
-    ws = None
-    if smoother == 1 and schedule == "oneshot":
-        ws = torch.empty(lib().gfx_dynamics_ws_bytes_ex(P, R, L) if DYN_LOOKBACK else lib().gfx_dynamics_ws_bytes(P),
-                         dtype=torch.uint8, device=x.device)
-    args = (_ptr(x), xmap, _ptr(out), ymap, pin(_rowvec(log_threshold, P)), pin(_rowvec(log_ratio, P)),
-            pin(_rowvec(log_knee, P)), pin(_rowvec(z_alpha, P)), P, R, C, L, smoother, iir_len, KNEES[knee], int(gate),
-            _ptr(u1_out), _ptr(ws), 0 if ws is None else ws.numel(), _stream())
-    if mix is not None and ws is not None and MIX_FUSION and x.ndim == 4 and out.ndim == 4:
-        mo, sched = mix["out"], mix["sched"]
-        n, J = x.shape[1], mo.shape[1]
-        if (mo.shape == (x.shape[0], J, C, L) and mo.stride(-1) == 1 and sched.numel() == n and xmap.inner == n
-                and ymap.inner == n):
-            own = 4 if mix.get("skip_rows") else 8
-            with _timed("dyn_fused_kernel", own * R * C * L + 4 * mo.numel() + (4 * R * L if u1_out is not None else 0)) as t:
-                ex = mix.get("extras")
-                n_ex = 0 if ex is None else ex.shape[0]
-                n_pre = mix.get("n_pre", 0)
+    tiled = smoother == 1 and schedule == "oneshot"
+    ws = pin.workspace(tiled and (lib().gfx_dynamics_ws_bytes_ex(P, R, L) if DYN_LOOKBACK else lib().gfx_dynamics_ws_bytes(P)),
+                       x.device)
+    args = (_ptr(x), xmap, _ptr(out), ymap, *_curve(pin, log_threshold, log_ratio, log_knee, P), pin(_rowvec(z_alpha, P)),
+            P, R, C, L, smoother, iir_len, KNEES[knee], int(gate), _ptr(u1_out), *ws, _stream())
+    kept = 4 * R * L if u1_out is not None else 0
+    if mix is not None and tiled and MIX_FUSION and x.ndim == 4 and out.ndim == 4:
+        n = x.shape[1]
+        m = _read_mix(mix, x.shape[0], n, C, L)
+        if m is not None and xmap.inner == n == ymap.inner:
+            # the records are keyed by the kernel's own name, as a profile prints it
+            with _timed("dyn_fused_kernel", (4 if m.skip_rows else 8) * R * C * L + 4 * m.out.numel() + kept,
+                        last="gfx_dynamics_last_kernel") as t:
                 # mix["skip_rows"]: nobody but these sums reads the stage's rows (an output-only render): do not store them
-                rc = lib().gfx_dynamics_fused_mix_f32(*args[:-1], _ptr(sched), n, mix["n_acc"], _ptr(mo), mo.stride(0),
-                                                      mo.stride(1), mo.stride(2) if C == 2 else 0, _ptr(ex), n_pre,
-                                                      n_ex - n_pre, 1 if mix.get("skip_rows") else 0, _stream())
-                if rc == 0 and t.rec is not None:    # keyed by the kernel's own name, as a profile prints it
-                    t.name = lib().gfx_dynamics_last_kernel().decode()
+                rc = lib().gfx_dynamics_fused_mix_f32(*args[:-1], *_mix_args(m, n), int(m.skip_rows), _stream())
+                if rc != 0:
+                    t.last = None
             if rc == 0:
                 mix["done"] = True
                 return out
-            if rc != -1:   # GFX_EINVAL: not a configuration of the fused kernel
+            if rc != GFX_EINVAL:   # not a configuration of the fused kernel
                 check(rc, "gfx_dynamics_fused_mix_f32")
-    with _timed("dyn_fused_kernel", 8 * R * C * L + (4 * R * L if u1_out is not None else 0)) as t:
+    with _timed("dyn_fused_kernel", 8 * R * C * L + kept, last="gfx_dynamics_last_kernel"):
         check(lib().gfx_dynamics_fused_f32(*args), "gfx_dynamics_fused_f32")
-        if t.rec is not None:
-            t.name = lib().gfx_dynamics_last_kernel().decode()
     return out
 
 
@@ -842,9 +712,9 @@ def dyn_gain_bwd(x, gy, env, log_threshold, log_ratio, log_knee, knee, gate):
     gain, denv = torch.empty_like(env), torch.empty_like(env)
     gp = torch.zeros((R, 3), dtype=torch.float32, device=x.device)
     pin = _Pin()
-    check(lib().gfx_dyn_gain_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, _ptr(env), pin(_rowvec(log_threshold, R)),
-                                     pin(_rowvec(log_ratio, R)), pin(_rowvec(log_knee, R)), R, C, L, KNEES[knee],
-                                     int(gate), _ptr(gain), _ptr(denv), _ptr(gp), _stream()), "gfx_dyn_gain_bwd_f32")
+    check(lib().gfx_dyn_gain_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, _ptr(env), *_curve(pin, log_threshold, log_ratio, log_knee, R),
+                                     R, C, L, KNEES[knee], int(gate), _ptr(gain), _ptr(denv), _ptr(gp), _stream()),
+          "gfx_dyn_gain_bwd_f32")
     return gain, denv, gp
 
 
@@ -861,9 +731,9 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     _require_gpu(x, gy, out)
     xmap, R, C, L = rowmap(x)
     gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L) or (out is not None and rowmap(out)[1:] != (R, C, L)):
-        raise ValueError(f"dynamics_bwd: gradient / output shapes do not match the input {tuple(x.shape)}")
-    gx = torch.empty((R, C, L), dtype=torch.float32, device=x.device) if out is None else out
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"dynamics_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gx, gxmap = _output(out, (R, C, L), x.device, "dynamics_bwd")
     gp = torch.empty((R, 3), dtype=torch.float32, device=x.device)
     da = torch.empty(R, dtype=torch.float32, device=x.device) if pole else None
     pin = _Pin()
@@ -877,11 +747,11 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     else:
         u1 = torch.empty((R, L), dtype=torch.float32, device=x.device)
         need_ws = bool(DYN_BWD_RESCAN if rescan is None else rescan)
-    ws = torch.empty(lib().gfx_dynamics_bwd_ws_bytes(R, L), dtype=torch.uint8, device=x.device) if need_ws else None
-    check(lib().gfx_dynamics_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(_rowvec(log_threshold, R)), pin(_rowvec(log_ratio, R)),
-                                     pin(_rowvec(log_knee, R)), pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee],
-                                     int(gate), _ptr(gx), rowmap(gx)[0], _ptr(gp), pin(u1), 0 if kept else 1, _ptr(da),
-                                     _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "gfx_dynamics_bwd_f32")
+    check(lib().gfx_dynamics_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, *_curve(pin, log_threshold, log_ratio, log_knee, R),
+                                     pin(_rowvec(z_alpha, R)), R, C, L, iir_len, KNEES[knee], int(gate), _ptr(gx), gxmap,
+                                     _ptr(gp), pin(u1), 0 if kept else 1, _ptr(da),
+                                     *pin.workspace(need_ws and lib().gfx_dynamics_bwd_ws_bytes(R, L), x.device), _stream()),
+          "gfx_dynamics_bwd_f32")
     return gx, gp, da
 
 
@@ -946,7 +816,7 @@ def onepole_energy(x, z_alpha, iir_len, Lout=None, relu=True, rowmax=None):
     words = torch.empty(R, dtype=torch.int32, device=x.device) if rowmax is not None else None
     pin = _Pin()
     check(lib().gfx_onepole_energy_f32(_ptr(x), xmap, C, pin(_rowvec(z_alpha, R)), _ptr(out), R, L, Lout, iir_len, int(relu),
-                                       None if words is None else words.data_ptr(), _stream()), "gfx_onepole_energy_f32")
+                                       _ptr(words), _stream()), "gfx_onepole_energy_f32")
     if rowmax is not None:
         rowmax["words"] = words
     return out
@@ -963,44 +833,6 @@ def onepole_fir(z_alpha, iir_len):
 
 
 BALLISTICS_SCHEDULE = "chunks"   # "chunks": rows cut into verified chunks (gfx_ballistics_f32 with a workspace); "rows": whole rows only
-
-
-def _overlap(a, b):
-    """Whether two float32 tensors share an element.  Exact for views of one storage with the same shape and (nested)
-    strides -- two node ranges of the render's (B, V, C, L) buffer interleave in memory without touching --, the bounding
-    ranges otherwise."""
-    if a.numel() == 0 or b.numel() == 0 or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
-        return False
-    if a.shape == b.shape and a.stride() == b.stride() and all(st > 0 for st in a.stride()):
-        dims = sorted(((st, n) for n, st in zip(a.shape, a.stride()) if n > 1), reverse=True)
-
-        def reachable(delta, i):      # delta = sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on?
-            if i == len(dims):
-                return delta == 0
-            st, n = dims[i]
-            q = delta // st
-            return any(abs(c) < n and reachable(abs(delta - c * st), i + 1) for c in (q, q + 1))
-
-        return reachable(abs(a.storage_offset() - b.storage_offset()), 0)
-
-    def span(t):
-        lo = t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride()) if st < 0)
-        return lo, lo + 1 + sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride()))
-
-    (a0, a1), (b0, b1) = span(a), span(b)
-    return a0 < b1 and b0 < a1
-
-
-def _ballistics_state(zi, R, what):
-    """The entering state of the ballistics entries: None (y[-1] = 1) or a contiguous float32 GPU tensor (R,), one value per
-    signal row.  The kernels read it in place, more than once per call."""
-    if zi is None:
-        return None
-    if not isinstance(zi, torch.Tensor) or not zi.is_cuda or zi.dtype != torch.float32 or tuple(zi.shape) != (R,) \
-            or not zi.is_contiguous():
-        got = f"{tuple(zi.shape)} {zi.dtype} on {zi.device}" if isinstance(zi, torch.Tensor) else type(zi).__name__
-        raise ValueError(f"{what}: zi must be a contiguous float32 GPU tensor of shape ({R},), got {got}")
-    return zi
 
 
 @_on_device
@@ -1020,17 +852,16 @@ def ballistics(u, z_alpha, coefficients=False, schedule=None, flags=None, zi=Non
     if z_alpha.shape != (R, 2):
         raise ValueError(f"z_alpha must be ({R}, 2), got {tuple(z_alpha.shape)}")
     y = torch.empty_like(u)
-    ws = None
-    if schedule == "chunks":
-        # zeroed: the single-pass schedules (short rows, very many rows) never write the flags this buffer is returned as
-        ws = torch.zeros(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=u.device)
-    zi = _ballistics_state(zi, R, "ballistics")
+    pin = _Pin()
+    # zeroed: the single-pass schedules (short rows, very many rows) never write the flags this buffer is returned as
+    ws = pin.workspace(schedule == "chunks" and lib().gfx_ballistics_ws_bytes(R), u.device, zero=True)
+    zi = _state(zi, (R,), "ballistics", "zi")
     zf = torch.empty(R, dtype=torch.float32, device=u.device) if return_state else None
     with _timed("ballistics_walk_kernel", 8 * R * L):
-        check(lib().gfx_ballistics_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(y), R, L, _ptr(ws),
-                                       0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_f32")
-    if flags is not None and ws is not None:
-        flags.append(ws.view(torch.int32))
+        check(lib().gfx_ballistics_f32(_ptr(u), _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(y), R, L, *ws,
+                                       _stream()), "gfx_ballistics_f32")
+    if flags is not None and schedule == "chunks":      # (no rows, no workspace: no flags either)
+        flags.append(y.new_empty(0, dtype=torch.int32) if pin.ws is None else pin.ws.view(torch.int32))
     return (y, zf) if return_state else y
 
 
@@ -1048,24 +879,16 @@ def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, ga
     z_alpha = z_alpha.contiguous()
     if z_alpha.shape != (P, 2):
         raise ValueError(f"z_alpha must be ({P}, 2), got {tuple(z_alpha.shape)}")
-    if out is None:
-        out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
-    elif rowmap(out)[1:] != (R, C, L):
-        raise ValueError(f"dynamics_ballistics: output {tuple(out.shape)} does not match input rows/channels/length {(R, C, L)}")
-    elif _overlap(x, out):
-        # the chunked schedule writes every row in its first pass and re-reads x for the rows it has to walk again
-        raise ValueError("dynamics_ballistics: out must not share memory with x (the kernel makes more than one pass over x)")
-    ws = None
-    if schedule == "chunks":
-        ws = torch.empty(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=x.device)
-    zi = _ballistics_state(zi, R, "dynamics_ballistics")
+    # the chunked schedule writes every row in its first pass and re-reads x for the rows it has to walk again
+    out, ymap = _output(out, (R, C, L), x.device, "dynamics_ballistics", apart=(x,))
+    zi = _state(zi, (R,), "dynamics_ballistics", "zi")
     zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     pin = _Pin()
     with _timed("ballistics_walk_kernel", 8 * R * C * L):
-        check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
-                                                pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), _ptr(z_alpha), P, R, C, L,
-                                                KNEES[knee], int(gate), _ptr(zi), _ptr(zf), _ptr(ws),
-                                                0 if ws is None else ws.numel(), _stream()), "gfx_dynamics_ballistics_f32")
+        check(lib().gfx_dynamics_ballistics_f32(_ptr(x), xmap, _ptr(out), ymap, *_curve(pin, log_threshold, log_ratio, log_knee, P),
+                                                _ptr(z_alpha), P, R, C, L, KNEES[knee], int(gate), _ptr(zi), _ptr(zf),
+                                                *pin.workspace(schedule == "chunks" and lib().gfx_ballistics_ws_bytes(R), x.device),
+                                                _stream()), "gfx_dynamics_ballistics_f32")
     return (out, zf) if return_state else out
 
 
@@ -1081,15 +904,13 @@ def ballistics_energy(x, z_alpha, coefficients=False, schedule=None, zi=None, re
     if z_alpha.shape != (R, 2):
         raise ValueError(f"z_alpha must be ({R}, 2), got {tuple(z_alpha.shape)}")
     env = torch.empty((R, L), dtype=torch.float32, device=x.device)
-    ws = None
-    if schedule == "chunks":
-        ws = torch.empty(lib().gfx_ballistics_ws_bytes(R), dtype=torch.uint8, device=x.device)
-    zi = _ballistics_state(zi, R, "ballistics_energy")
+    zi = _state(zi, (R,), "ballistics_energy", "zi")
     zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
+    pin = _Pin()
     with _timed("ballistics_walk_kernel", 4 * R * (C + 1) * L):
         check(lib().gfx_ballistics_energy_f32(_ptr(x), xmap, C, _ptr(z_alpha), int(coefficients), _ptr(zi), _ptr(zf), _ptr(env),
-                                              R, L, _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
-              "gfx_ballistics_energy_f32")
+                                              R, L, *pin.workspace(schedule == "chunks" and lib().gfx_ballistics_ws_bytes(R), x.device),
+                                              _stream()), "gfx_ballistics_energy_f32")
     return (env, zf) if return_state else env
 
 
@@ -1106,13 +927,12 @@ def ballistics_bwd(x, y, g, z_alpha, schedule="chunks", zi=None):
     _expect(g, (R, L), "ballistics_bwd: g")
     _expect(z_alpha, (R, 2), "ballistics_bwd: z_alpha")
     gx, gz = torch.empty_like(x), torch.empty((R, 2), dtype=torch.float32, device=x.device)
-    zi = _ballistics_state(zi, R, "ballistics_bwd")
+    zi = _state(zi, (R,), "ballistics_bwd", "zi")
     gzi = None if zi is None else torch.empty(R, dtype=torch.float32, device=x.device)
-    ws = None
-    if schedule != "rows":
-        ws = torch.empty(max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4), dtype=torch.uint8, device=x.device)
+    pin = _Pin()
     check(lib().gfx_ballistics_bwd_f32(_ptr(x), _ptr(y), _ptr(g), _ptr(z_alpha), _ptr(zi), _ptr(gx), _ptr(gz), _ptr(gzi), R, L,
-                                       _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "gfx_ballistics_bwd_f32")
+                                       *pin.workspace(schedule != "rows" and max(int(lib().gfx_ballistics_bwd_ws_bytes(R, L)), 4),
+                                                      x.device), _stream()), "gfx_ballistics_bwd_f32")
     return (gx, gz) if zi is None else (gx, gz, gzi)
 
 
@@ -1124,8 +944,8 @@ def dyn_gain(env, log_threshold, log_ratio, log_knee, knee, gate, log_out):
     g = torch.empty_like(env)
     pin = _Pin()
     check(
-        lib().gfx_dyn_gain_f32(_ptr(env), _ptr(g), pin(_rowvec(log_threshold, R)), pin(_rowvec(log_ratio, R)),
-                               pin(_rowvec(log_knee, R)), R, L, KNEES[knee], int(gate), int(log_out), _stream()),
+        lib().gfx_dyn_gain_f32(_ptr(env), _ptr(g), *_curve(pin, log_threshold, log_ratio, log_knee, R), R, L, KNEES[knee],
+                               int(gate), int(log_out), _stream()),
         "gfx_dyn_gain_f32",
     )
     return g
@@ -1137,11 +957,8 @@ def apply_gain(x, g, exp_gain=False, out=None):
     xmap, R, C, L = rowmap(x)
     _expect(g, (R, L), "apply_gain: gain")
     g = g.contiguous()
-    if out is None:
-        out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
-    elif rowmap(out)[1:] != (R, C, L):
-        raise ValueError(f"apply_gain: output {tuple(out.shape)} does not match input rows/channels/length {(R, C, L)}")
-    check(lib().gfx_apply_gain_f32(_ptr(x), xmap, _ptr(g), _ptr(out), rowmap(out)[0], R, C, L, int(exp_gain), _stream()), "gfx_apply_gain_f32")
+    out, ymap = _output(out, (R, C, L), x.device, "apply_gain")
+    check(lib().gfx_apply_gain_f32(_ptr(x), xmap, _ptr(g), _ptr(out), ymap, R, C, L, int(exp_gain), _stream()), "gfx_apply_gain_f32")
     return out
 
 
@@ -1154,15 +971,11 @@ def dyn_gain_apply(x, env, log_threshold, log_ratio, log_knee, knee, gate, out=N
     _expect(env, (R, L), "dyn_gain_apply: envelope")
     env = env.contiguous()
     P = R if param_rows is None else param_rows
-    if out is None:
-        out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
-    elif rowmap(out)[1:] != (R, C, L):
-        raise ValueError(f"dyn_gain_apply: output {tuple(out.shape)} does not match input rows/channels/length {(R, C, L)}")
+    out, ymap = _output(out, (R, C, L), x.device, "dyn_gain_apply")
     pin = _Pin()
     with _timed("dyn_gain_apply_kernel", 4 * R * L * (2 * C + 1)):
-        check(lib().gfx_dyn_gain_apply_f32(_ptr(x), xmap, _ptr(env), _ptr(out), rowmap(out)[0], pin(_rowvec(log_threshold, P)),
-                                           pin(_rowvec(log_ratio, P)), pin(_rowvec(log_knee, P)), P, R, C, L, KNEES[knee],
-                                           int(gate), _stream()), "gfx_dyn_gain_apply_f32")
+        check(lib().gfx_dyn_gain_apply_f32(_ptr(x), xmap, _ptr(env), _ptr(out), ymap, *_curve(pin, log_threshold, log_ratio, log_knee, P),
+                                           P, R, C, L, KNEES[knee], int(gate), _stream()), "gfx_dyn_gain_apply_f32")
     return out
 
 
@@ -1173,27 +986,19 @@ def stereo_gain(x, log_gain, out=None, mix=None):
     _require_gpu(x, log_gain, out)
     xmap, R, C, L = rowmap(x)
     _expect(log_gain, (R, 2), "stereo_gain: log_gain")
-    if out is None:
-        out = torch.empty((R, 2, L), dtype=torch.float32, device=x.device)
-    elif rowmap(out)[1:] != (R, 2, L):
-        raise ValueError(f"stereo_gain: output {tuple(out.shape)} does not match {(R, 2, L)}")
+    out, ymap = _output(out, (R, 2, L), x.device, "stereo_gain")
     pin = _Pin()
     if mix is not None and MIX_FUSION and x.ndim == 4 and out.ndim == 4:
-        mo, sched = mix["out"], mix["sched"]
         n = x.shape[1]
-        if mo.shape == (x.shape[0], mo.shape[1], 2, L) and mo.stride(-1) == 1 and sched.numel() == n:
-            ex = mix.get("extras")
-            n_ex = 0 if ex is None else ex.shape[0]
-            n_pre = mix.get("n_pre", 0)
-            rc = lib().gfx_stereo_gain_mix_f32(_ptr(x), xmap, pin(log_gain), _ptr(out), rowmap(out)[0], R, C, L, _ptr(sched), n,
-                                               mix["n_acc"], _ptr(mo), mo.stride(0), mo.stride(1), mo.stride(2), _ptr(ex),
-                                               n_pre, n_ex - n_pre, _stream())
+        m = _read_mix(mix, x.shape[0], n, 2, L)
+        if m is not None:
+            rc = lib().gfx_stereo_gain_mix_f32(_ptr(x), xmap, pin(log_gain), _ptr(out), ymap, R, C, L, *_mix_args(m, n), _stream())
             if rc == 0:
                 mix["done"] = True
                 return out
-            if rc != -1:
+            if rc != GFX_EINVAL:
                 check(rc, "gfx_stereo_gain_mix_f32")
-    check(lib().gfx_stereo_gain_f32(_ptr(x), xmap, pin(log_gain), _ptr(out), rowmap(out)[0], R, C, L, _stream()), "gfx_stereo_gain_f32")
+    check(lib().gfx_stereo_gain_f32(_ptr(x), xmap, pin(log_gain), _ptr(out), ymap, R, C, L, _stream()), "gfx_stereo_gain_f32")
     return out
 
 
@@ -1211,22 +1016,14 @@ def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None, zi=None, return_state=F
     if Rb != R or three != 3 or As.shape != Bs.shape:
         raise ValueError(f"coefficients {tuple(Bs.shape)} / {tuple(As.shape)} do not match {R} rows")
     Cout = max(Cin, Cf)
-    if out is None:
-        out = torch.empty((R, Cout, L), dtype=torch.float32, device=x.device)
-    ymap = rowmap(out)[0]
+    out, ymap = _output(out, (R, Cout, L), x.device, "biquad_cascade")
     Bs, As = Bs.contiguous(), As.contiguous()
     if zi is None and not return_state:
         with _timed("biquad_cascade_kernel", 4 * R * (Cin + Cout) * L):
             check(lib().gfx_biquad_cascade_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), R, Cin, Cf, K, L,
                                                int(ssm_quirk), _stream()), "gfx_biquad_cascade_f32")
         return out
-    if zi is not None:
-        if not isinstance(zi, torch.Tensor) or not zi.is_cuda or zi.dtype != torch.float32:
-            raise ValueError(f"biquad_cascade: zi must be a float32 tensor on the GPU, got "
-                             f"{getattr(zi, 'dtype', type(zi).__name__)} on {getattr(zi, 'device', 'the host')}")
-        _expect(zi, (R, Cout, K, 2), "biquad_cascade: zi")
-        if not zi.is_contiguous():
-            raise ValueError("biquad_cascade: zi must be contiguous")
+    zi = _state(zi, (R, Cout, K, 2), "biquad_cascade", "zi")
     zf = torch.empty((R, Cout, K, 2), dtype=torch.float32, device=x.device)
     with _timed("biquad_cascade_state_kernel", 4 * R * (Cin + Cout) * L + 16 * R * Cout * K):
         check(lib().gfx_biquad_cascade_state_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), _ptr(zi), _ptr(zf),
@@ -1265,6 +1062,25 @@ def row_mean(x):
     return mean
 
 
+WS_GRADS = ("x", "log_pre_gain", "log_post_gain", "p0", "p1")
+
+
+def _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc):
+    """What the waveshaper pair reads besides the signal -> ({name: contiguous (R, n) view or None} in WS_GRADS' order, K =
+    number of basis weights of the polynomial modes, dc = the (R * C,) row-channel means to subtract or None)."""
+    params = {"log_pre_gain": log_pre_gain, "log_post_gain": log_post_gain, "p0": p0, "p1": p1}
+    params = {k: None if t is None else t.contiguous().view(R, -1) for k, t in params.items()}
+    K = params["p0"].shape[1] if (params["p0"] is not None and mode in (WS_POWER, WS_CHEBYSHEV)) else 0
+    if not remove_dc:
+        dc = None
+    elif dc is None:
+        dc = row_mean(x)
+    else:
+        _expect(dc, (R * C,), f"{what}: dc")
+        dc = dc.contiguous()
+    return params, K, dc
+
+
 @_on_device
 def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None, use_tanh=False,
                inverse_post_gain=False, remove_dc=False, out=None, dc=None, return_dc=False):
@@ -1273,29 +1089,15 @@ def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None,
     means this call subtracted (None without ``remove_dc``) -- what waveshaper_bwd needs of them."""
     _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
     xmap, R, C, L = rowmap(x)
-    if out is None:
-        out = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
-    ymap = rowmap(out)[0]
-    c = lambda t: None if t is None else t.contiguous().view(R, -1)  # noqa: E731
-    log_pre_gain, log_post_gain, p0, p1 = c(log_pre_gain), c(log_post_gain), c(p0), c(p1)
-    K = p0.shape[1] if (p0 is not None and mode in (WS_POWER, WS_CHEBYSHEV)) else 0
-    if not remove_dc:
-        dc = None
-    elif dc is None:
-        dc = row_mean(x)
-    else:
-        _expect(dc, (R * C,), "waveshaper: dc")
-        dc = dc.contiguous()
+    out, ymap = _output(out, (R, C, L), x.device, "waveshaper")
+    params, K, dc = _waveshaper_args("waveshaper", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
     with _timed("waveshaper_kernel", 8 * R * C * L):
         check(
             lib().gfx_waveshaper_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, mode, int(use_tanh), int(inverse_post_gain),
-                                     _ptr(log_pre_gain), _ptr(log_post_gain), _ptr(p0), _ptr(p1), K, _ptr(dc), _stream()),
+                                     *(_ptr(v) for v in params.values()), K, _ptr(dc), _stream()),
             "gfx_waveshaper_f32",
         )
     return (out, dc) if return_dc else out
-
-
-WS_GRADS = ("x", "log_pre_gain", "log_post_gain", "p0", "p1")
 
 
 @_on_device
@@ -1310,37 +1112,26 @@ def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, 
     _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
     xmap, R, C, L = rowmap(x)
     gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L) or (out is not None and rowmap(out)[1:] != (R, C, L)):
-        raise ValueError(f"waveshaper_bwd: gradient / output shapes do not match the input {tuple(x.shape)}")
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"waveshaper_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
     unknown = set(want) - set(WS_GRADS)
     if unknown:
         raise ValueError(f"waveshaper_bwd: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
-    c = lambda t: None if t is None else t.contiguous().view(R, -1)  # noqa: E731
-    params = {"log_pre_gain": c(log_pre_gain), "log_post_gain": c(log_post_gain), "p0": c(p0), "p1": c(p1)}
-    poly = mode in (WS_POWER, WS_CHEBYSHEV)
-    K = params["p0"].shape[1] if (params["p0"] is not None and poly) else 0
-    if not remove_dc:
-        dc = None
-    elif dc is None:
-        dc = row_mean(x)
-    else:
-        _expect(dc, (R * C,), "waveshaper_bwd: dc")
-        dc = dc.contiguous()
-    gx = None
-    if "x" in want:
-        gx = torch.empty((R, C, L), dtype=torch.float32, device=x.device) if out is None else out
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, C, L), x.device, "waveshaper_bwd")
+        if "x" in want:
+            gx, gxmap = dest
+    params, K, dc = _waveshaper_args("waveshaper_bwd", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
     grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
-    ws = None
-    if grads or (gx is not None and dc is not None):
-        ws = torch.empty(lib().gfx_waveshaper_bwd_ws_bytes(R, C, L, K), dtype=torch.uint8, device=x.device)
+    pin = _Pin()
+    ws = pin.workspace((bool(grads) or (gx is not None and dc is not None)) and lib().gfx_waveshaper_bwd_ws_bytes(R, C, L, K),
+                       x.device)
     with _timed("waveshaper_bwd_kernel", (8 if gx is None else 12) * R * C * L):
         check(
-            lib().gfx_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, mode, int(use_tanh),
-                                         int(inverse_post_gain), _ptr(params["log_pre_gain"]),
-                                         _ptr(params["log_post_gain"]), _ptr(params["p0"]), _ptr(params["p1"]), K, _ptr(dc),
-                                         _ptr(gx), xmap if gx is None else rowmap(gx)[0], _ptr(grads.get("log_pre_gain")),
-                                         _ptr(grads.get("log_post_gain")), _ptr(grads.get("p0")), _ptr(grads.get("p1")),
-                                         _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+            lib().gfx_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, mode, int(use_tanh), int(inverse_post_gain),
+                                         *(_ptr(v) for v in params.values()), K, _ptr(dc), _ptr(gx), gxmap,
+                                         *(_ptr(grads.get(k)) for k in params), *ws, _stream()),
             "gfx_waveshaper_bwd_f32",
         )
     return gx, grads
@@ -1368,13 +1159,22 @@ def stft(x, window, hop):
     frames = 1 + T // hop
     out = torch.empty((rows, n_fft // 2 + 1, frames, 2), dtype=torch.float32, device=x.device)
     pin = _Pin()
-    for i in range(0, rows, 65535):     # rows ride on a grid dimension
-        n = min(65535, rows - i)
+    for i, n in _row_chunks(rows, GRID_YZ_MAX):
         check(lib().gfx_stft_f32(_ptr(x[i:]), pin(window), _ptr(out[i:]), n, T, n_fft, hop, _stream()), "gfx_stft_f32")
     return torch.view_as_complex(out)
 
 
 ISTFT_SCHEDULES = {"auto": 0, "gemm": 1, "fft": 2}   # GFX_ISTFT_* (include/grafx_amd.h)
+
+
+def _reverb_noise(what, noise_stft, R):
+    """The noise of the reverb pair: one spectrum shared by all R rows, or (R,2,K,T) fresh noise per row.  -> cut(r0, n) =
+    (pointer, number of spectra) for rows r0 .. r0 + n of the float32 (...,2,K,T,2) view of the complex64 buffer."""
+    rows = noise_stft.shape[0] if noise_stft.ndim == 4 else 1
+    if rows not in (1, R):
+        raise ValueError(f"{what}: {rows} noise spectra for {R} rows")
+    nz = torch.view_as_real(noise_stft.contiguous())
+    return lambda r0, n: (_ptr(nz), 1) if rows == 1 else (_ptr(nz[r0:r0 + n]), n)
 
 
 @_on_device
@@ -1385,27 +1185,20 @@ def stft_reverb_ir(noise_stft, init_lm, delta_lm, gain_env, window, basis, ir_le
     R = init_lm.shape[0]
     n_fft = window.numel()
     T = noise_stft.shape[-1]
-    noise_rows = noise_stft.shape[0] if noise_stft.ndim == 4 else 1   # (R,2,K,T): fresh noise per row; else shared
-    if noise_rows not in (1, R):
-        raise ValueError(f"stft_reverb_ir: {noise_rows} noise spectra for {R} rows")
-    nz = torch.view_as_real(noise_stft.contiguous())  # (…,2,K,T,2) float32 view of the complex64 buffer
+    noise = _reverb_noise("stft_reverb_ir", noise_stft, R)
     ir = torch.empty((R, 2, ir_len), dtype=torch.float32, device=init_lm.device)
     row_gain = torch.empty((R,), dtype=torch.float32, device=init_lm.device)
     sched = ISTFT_SCHEDULES[schedule]
     init_lm, delta_lm = init_lm.contiguous(), delta_lm.contiguous()
     gain_env = None if gain_env is None else gain_env.contiguous()
-    ROWS = 32767                                        # rows per launch (the kernels' grids index rows in 16 bits)
-    for r0 in range(0, R, ROWS):
-        n = min(ROWS, R - r0)
-        nbytes = lib().gfx_stft_reverb_workspace_bytes(n, ir_len, n_fft, hop, T, sched)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=init_lm.device)
+    for r0, n in _row_chunks(R, GRID_ROWS_I16_MAX):
         pin = _Pin()
+        ws = pin.workspace(lib().gfx_stft_reverb_workspace_bytes(n, ir_len, n_fft, hop, T, sched), init_lm.device)
         check(
-            lib().gfx_stft_reverb_ir_f32(_ptr(nz[r0:r0 + n] if noise_rows != 1 else nz), noise_rows if noise_rows == 1 else n,
-                                         pin(init_lm[r0:r0 + n]), pin(delta_lm[r0:r0 + n]),
+            lib().gfx_stft_reverb_ir_f32(*noise(r0, n), pin(init_lm[r0:r0 + n]), pin(delta_lm[r0:r0 + n]),
                                          pin(None if gain_env is None else gain_env[r0:r0 + n]), pin(window), pin(basis),
                                          _ptr(ir[r0:r0 + n]), _ptr(row_gain[r0:r0 + n]), n, ir_len, n_fft, hop, T,
-                                         int(ms_to_lr), _ptr(ws), nbytes, sched, _stream()),
+                                         int(ms_to_lr), *ws, sched, _stream()),
             "gfx_stft_reverb_ir_f32",
         )
     return ir, row_gain
@@ -1434,30 +1227,24 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
         raise ValueError("stft_reverb_ir_bwd: ir and row_gain come together (the normalised taps) or not at all")
     if init_lm.shape[0] != R or (ir is not None and tuple(ir.shape) != tuple(grad_ir.shape)):
         raise ValueError(f"stft_reverb_ir_bwd: gradient {tuple(grad_ir.shape)} does not match the {init_lm.shape[0]} rows")
-    noise_rows = noise_stft.shape[0] if noise_stft.ndim == 4 else 1
-    if noise_rows not in (1, R):
-        raise ValueError(f"stft_reverb_ir_bwd: {noise_rows} noise spectra for {R} rows")
-    nz = torch.view_as_real(noise_stft.contiguous())
+    noise = _reverb_noise("stft_reverb_ir_bwd", noise_stft, R)
     grad_ir, init_lm, delta_lm = grad_ir.contiguous(), init_lm.contiguous(), delta_lm.contiguous()
     gain_env = None if gain_env is None else gain_env.contiguous()
     ir = None if ir is None else ir.contiguous()
     row_gain = None if row_gain is None else row_gain.contiguous()
     g_init, g_delta = torch.empty_like(init_lm), torch.empty_like(delta_lm)
     g_env = torch.empty_like(gain_env) if (gain_env is not None and want_gain_env) else None
-    ROWS = 32767                                        # rows per launch, as the forward
-    nbytes = lib().gfx_stft_reverb_ir_bwd_ws_bytes(min(R, ROWS), ir_len)
+    nbytes = lib().gfx_stft_reverb_ir_bwd_ws_bytes(min(R, GRID_ROWS_I16_MAX), ir_len)
     if ws is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_ir.device)
     elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
         raise ValueError(f"stft_reverb_ir_bwd: the workspace must be {nbytes} contiguous uint8")
     cut = lambda t, r0, n: None if t is None else t[r0:r0 + n]  # noqa: E731
-    for r0 in range(0, R, ROWS):
-        n = min(ROWS, R - r0)
+    for r0, n in _row_chunks(R, GRID_ROWS_I16_MAX):
         pin = _Pin()
         check(
             lib().gfx_stft_reverb_ir_bwd_f32(_ptr(grad_ir[r0:r0 + n]), _ptr(cut(ir, r0, n)), _ptr(cut(row_gain, r0, n)),
-                                             _ptr(nz[r0:r0 + n] if noise_rows != 1 else nz),
-                                             noise_rows if noise_rows == 1 else n, pin(init_lm[r0:r0 + n]),
+                                             *noise(r0, n), pin(init_lm[r0:r0 + n]),
                                              pin(delta_lm[r0:r0 + n]), pin(cut(gain_env, r0, n)), pin(window), pin(basis),
                                              _ptr(g_init[r0:r0 + n]), _ptr(g_delta[r0:r0 + n]), _ptr(cut(g_env, r0, n)), n,
                                              ir_len, n_fft, hop, T, int(ms_to_lr), _ptr(ws), ws.numel(), _stream()),
@@ -1481,11 +1268,10 @@ def gather_sum(buf, src_idx, seg_ptr, out):
     if J * C > GRID_YZ_MAX:
         raise ValueError(f"gather_sum: {J} destinations x {C} channels ride on one grid dimension, at most {GRID_YZ_MAX}")
     with _timed("gather_sum_kernel", 4 * B * C * L * (src_idx.numel() + J)):
-        for b0 in range(0, B, GRID_YZ_MAX):     # the batch rides on a grid dimension: slices keep the views' strides
-            bs, os_ = buf[b0 : b0 + GRID_YZ_MAX], out[b0 : b0 + GRID_YZ_MAX]
+        for b0, nb in _row_chunks(B, GRID_YZ_MAX):     # the batch rides on a grid dimension: slices keep the views' strides
             check(
-                lib().gfx_gather_sum_f32(_ptr(bs), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(src_idx), _ptr(seg_ptr),
-                                         _ptr(os_), out.stride(0), out.stride(1), out.stride(2), bs.shape[0], J, C, L,
+                lib().gfx_gather_sum_f32(_ptr(buf[b0:]), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(src_idx),
+                                         _ptr(seg_ptr), _ptr(out[b0:]), out.stride(0), out.stride(1), out.stride(2), nb, J, C, L,
                                          _stream()),
                 "gfx_gather_sum_f32",
             )
@@ -1503,11 +1289,10 @@ def gather_sum_fanout(buf, unique_src, dest_mask, out):
     with _timed("gather_sum_kernel", 4 * B * C * L * (unique_src.numel() + J)):
         # the batch rides on a grid dimension; what the kernel refuses (alignment, J, C) it refuses for every slice alike,
         # so a refusal can only come from the first one, before anything is written
-        for b0 in range(0, B, GRID_YZ_MAX):
-            bs, os_ = buf[b0 : b0 + GRID_YZ_MAX], out[b0 : b0 + GRID_YZ_MAX]
-            code = lib().gfx_gather_sum_fanout_f32(_ptr(bs), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(unique_src),
-                                                   _ptr(dest_mask), unique_src.numel(), _ptr(os_), out.stride(0),
-                                                   out.stride(1), out.stride(2), bs.shape[0], J, C, L, _stream())
+        for b0, nb in _row_chunks(B, GRID_YZ_MAX):
+            code = lib().gfx_gather_sum_fanout_f32(_ptr(buf[b0:]), buf.stride(0), buf.stride(1), buf.stride(2), _ptr(unique_src),
+                                                   _ptr(dest_mask), unique_src.numel(), _ptr(out[b0:]), out.stride(0),
+                                                   out.stride(1), out.stride(2), nb, J, C, L, _stream())
             if code != 0:
                 if b0 == 0:
                     return False

@@ -1,0 +1,103 @@
+"""The checks every wrapper of grafx_amd.ops shares (grafx_amd/_plumbing.py and the readers in ops.py), on CPU tensors:
+none of them launches anything, and only the state check itself asks for a GPU tensor."""
+import pytest
+import torch
+
+from grafx_amd import ops
+from grafx_amd.ops import _output, _read_mix, _row_chunks, _state, rowmap
+
+SHAPE = (2, 2, 64)
+CPU = torch.device("cpu")
+
+
+def _same_map(a, b):
+    return all(getattr(a, f) == getattr(b, f) for f, _ in a._fields_)
+
+
+def test_output_allocates_and_accepts():
+    out, omap = _output(None, SHAPE, CPU, "t")
+    assert out.shape == SHAPE and out.dtype == torch.float32 and _same_map(omap, rowmap(out)[0])
+    plain = torch.zeros(SHAPE)
+    buf = torch.zeros(1, 6, 2, 64)
+    for t in (plain, buf[:, 2:4]):
+        for longer in (False, True):
+            got, omap = _output(t, SHAPE, CPU, "t", longer=longer)
+            assert got is t and _same_map(omap, rowmap(t)[0])
+    assert _output(torch.zeros(2, 2, 65), SHAPE, CPU, "t", longer=True)[0].shape[-1] == 65
+
+
+@pytest.mark.parametrize("bad, longer", [
+    (torch.zeros(1, 2, 64), False), (torch.zeros(3, 2, 64), True),                  # rows
+    (torch.zeros(2, 1, 64), False), (torch.zeros(2, 3, 64), True),                  # channels
+    (torch.zeros(2, 2, 63), False), (torch.zeros(2, 2, 63), True),                  # shorter
+    (torch.zeros(2, 2, 65), False),                                                 # longer, where equality is asked
+    (torch.zeros(1, 6, 2, 64)[:, 2:5], False), (torch.zeros(2, 2, 128)[..., ::2], False),   # 3 nodes; a last stride of 2
+])
+def test_output_refuses(bad, longer):
+    with pytest.raises(ValueError):
+        _output(bad, SHAPE, CPU, "t", longer=longer)
+
+
+def test_output_apart():
+    buf = torch.zeros(1, 6, 2, 64)
+    x = buf[:, 2:4]
+    with pytest.raises(ValueError, match="share memory"):
+        _output(x, SHAPE, CPU, "t", apart=(x,))
+    with pytest.raises(ValueError, match="share memory"):
+        _output(buf[:, 3:5], SHAPE, CPU, "t", apart=(x,))
+    assert _output(buf[:, 4:6], SHAPE, CPU, "t", apart=(x,))[0].data_ptr() == buf[:, 4:6].data_ptr()
+    assert _output(x, SHAPE, CPU, "t")[0] is x          # no list, no refusal
+
+
+def test_state_refusals_name_entry_argument_shape_and_value():
+    assert _state(None, SHAPE, "entry", "zi") is None
+    for bad in ([0.0] * 4, torch.zeros(SHAPE, dtype=torch.float64), torch.zeros(2, 2, 63), torch.zeros(2, 64, 2).transpose(1, 2),
+                torch.zeros(SHAPE)):            # the last: everything right but the device
+        with pytest.raises(ValueError, match=r"entry: zi must be .*\(2, 2, 64\).*got") as e:
+            _state(bad, SHAPE, "entry", "zi")
+        assert ("list" if isinstance(bad, list) else str(bad.dtype)) in str(e.value)
+
+
+@pytest.mark.gpu
+def test_state_on_the_gpu():
+    good = torch.zeros(SHAPE, device="cuda")
+    assert _state(good, SHAPE, "entry", "zf") is good
+    for bad in (good.double(), good[:, :, :63], torch.zeros(2, 64, 2, device="cuda").transpose(1, 2)):
+        with pytest.raises(ValueError, match=r"entry: zf must be .*\(2, 2, 64\)"):
+            _state(bad, SHAPE, "entry", "zf")
+
+
+@pytest.mark.parametrize("limit", [1, 3, ops.GRID_ROWS_I16_MAX, ops.GRID_YZ_MAX])
+def test_row_chunks(limit):
+    assert list(_row_chunks(0, limit)) == []
+    assert list(_row_chunks(limit, limit)) == [(0, limit)]
+    assert list(_row_chunks(limit + 1, limit)) == [(0, limit), (limit, 1)]
+    assert (ops.GRID_ROWS_I16_MAX, ops.GRID_YZ_MAX) == (32767, 65535)
+
+
+def _inline_mix(mix, B, n, C, L):
+    """The reading dynamics_fused and stereo_gain each spelled out before they shared _read_mix."""
+    mo, sched = mix["out"], mix["sched"]
+    if not (mo.shape == (B, mo.shape[1], C, L) and mo.stride(-1) == 1 and sched.numel() == n):
+        return None
+    ex = mix.get("extras")
+    n_ex = 0 if ex is None else ex.shape[0]
+    n_pre = mix.get("n_pre", 0)
+    return mo, sched, mix["n_acc"], ex, n_pre, n_ex - n_pre, bool(mix.get("skip_rows"))
+
+
+def test_read_mix():
+    B, n, C, L = 2, 3, 2, 64
+    sched = torch.arange(n)
+    with_extras = {"out": torch.zeros(B, 8, C, L)[:, 1:3], "sched": sched, "n_acc": 2, "extras": torch.zeros(5, 2, dtype=torch.int64),
+                   "n_pre": 2, "skip_rows": True}
+    without = {"out": torch.zeros(B, 2, C, L), "sched": sched, "n_acc": 1}
+    for mix in (with_extras, without):
+        got, want = _read_mix(mix, B, n, C, L), _inline_mix(mix, B, n, C, L)
+        assert tuple(got)[2:3] + tuple(got)[4:] == want[2:3] + want[4:]
+        assert got.out is want[0] and got.sched is want[1] and got.extras is want[3]
+    assert (_read_mix(with_extras, B, n, C, L).n_pre, _read_mix(with_extras, B, n, C, L).n_post) == (2, 3)
+    assert (_read_mix(without, B, n, C, L).extras, _read_mix(without, B, n, C, L).n_post) == (None, 0)
+    for wrong in ((B + 1, n, C, L), (B, n + 1, C, L), (B, n, 1, L), (B, n, C, L + 1)):    # each entry's shape conditions
+        assert _read_mix(without, *wrong) is None and _inline_mix(without, *wrong) is None
+    assert _read_mix({**without, "out": torch.zeros(B, 2, C, 2 * L)[..., ::2]}, B, n, C, L) is None
