@@ -143,38 +143,91 @@ def rowmap(t):
     raise ValueError(f"expected a 3-D or 4-D signal tensor, got {t.ndim}-D")
 
 
+# Nodes the exact search of _overlap may visit before it answers True.  Views cut from one contiguous buffer visit at most
+# two per level of the buffer's strides; only interleaved as_strided views come near the limit.
+_OVERLAP_NODES = 256
+
+
 def _overlap(a, b):
-    """Whether two float32 tensors share an element.  Exact for views of one storage with the same shape and (nested)
-    strides -- two node ranges of the render's (B, V, C, L) buffer interleave in memory without touching --, the bounding
-    ranges otherwise."""
-    if a.numel() == 0 or b.numel() == 0 or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+    """Whether two strided views share an element.  Never False when they do.  Exact whenever the search below ends within
+    _OVERLAP_NODES nodes -- always for views cut from one contiguous buffer by slicing, indexing and permuting, whatever
+    their extents: two node ranges of the render's (B, V, C, L) buffer interleave in memory without touching.  Integer
+    arithmetic on addresses, shapes and strides only.
+
+    An element of ``a`` at index i and one of ``b`` at index j coincide when address_a - address_b = sum_s (j_s - i_s) * s
+    over the strides s of either view, with j_s - i_s anywhere in -(na_s - 1) .. nb_s - 1.  The strides are taken largest
+    first, and a difference is tried only while what remains is within reach of the smaller strides."""
+    if a.numel() == 0 or b.numel() == 0:
         return False
-    if a.shape == b.shape and a.stride() == b.stride() and all(st > 0 for st in a.stride()):
-        dims = sorted(((st, n) for n, st in zip(a.shape, a.stride()) if n > 1), reverse=True)
+    low, reach, found = [a.data_ptr(), b.data_ptr()], [0, 0], []
+    for k, t in enumerate((a, b)):
+        for n, st in zip(t.shape, t.stride()):
+            if n > 1 and st != 0:     # (a dimension of one element or of stride 0 adds no element)
+                if st < 0:            # torch makes no such view today; one that did is still answered soundly
+                    low[k] += (n - 1) * st * t.element_size()
+                    st = -st
+                reach[k] += (n - 1) * st
+                found.append((st, k, n - 1))
+    (pa, pb), ea, eb = low, a.element_size(), b.element_size()
+    if pa + (reach[0] + 1) * ea <= pb or pb + (reach[1] + 1) * eb <= pa:
+        return False                  # the bounding ranges are apart (views of two allocations always are)
+    if ea != eb or (pa - pb) % ea:
+        return True                   # elements of different width or on different grids: the bounding ranges are the answer
+    steps = {}                        # stride -> [na - 1, nb - 1], summed over the dimensions that have it
+    for st, k, m in found:
+        steps.setdefault(st, [0, 0])[k] += m
+    dims = sorted(steps.items(), reverse=True)
+    below = [(0, 0)]                  # below[i]: lowest and highest sum the dimensions from i on can add
+    for st, (na, nb) in reversed(dims):
+        below.append((below[-1][0] - na * st, below[-1][1] + nb * st))
+    below.reverse()
+    todo, left = [((pa - pb) // ea, 0)], _OVERLAP_NODES
+    while todo:
+        delta, i = todo.pop()
+        left -= 1
+        if i == len(dims) or left < 0:           # (the last dimension leaves nothing but 0 below it)
+            return True
+        st, (na, nb) = dims[i]
+        lo, hi = below[i + 1]
+        todo += [(delta - d * st, i + 1) for d in range(max(-na, -((hi - delta) // st)), min(nb, (delta - lo) // st) + 1)]
+    return False
 
-        def reachable(delta, i):      # delta = sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on?
-            if i == len(dims):
-                return delta == 0
-            st, n = dims[i]
-            q = delta // st
-            return any(abs(c) < n and reachable(abs(delta - c * st), i + 1) for c in (q, q + 1))
 
-        return reachable(abs(a.storage_offset() - b.storage_offset()), 0)
+def _self_overlap(t):
+    """Whether two indices of a view may name one element: a stride of 0 on a dimension of more than one element
+    (``expand``), or strides that are not nested (``as_strided``) -- no stride, smallest first, beyond the reach of the ones
+    before it.  Never False when the view overlaps itself; a view cut from a contiguous buffer by slicing, indexing and
+    permuting is nested and answered False."""
+    if t.numel() == 0:
+        return False
+    reach = 0
+    for st, n in sorted((abs(st), n) for n, st in zip(t.shape, t.stride()) if n > 1):
+        if st <= reach:
+            return True
+        reach += (n - 1) * st
+    return False
 
-    def span(t):
-        lo = t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride()) if st < 0)
-        return lo, lo + 1 + sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride()))
 
-    (a0, a1), (b0, b1) = span(a), span(b)
-    return a0 < b1 and b0 < a1
+def _apart(what, name, t, apart):
+    """The aliasing rule for one tensor ``t`` a call writes (None: nothing to check): it shares no element with itself nor
+    with any tensor of ``apart`` -- what the call reads and whatever else it writes (None entries are skipped).  Every kernel
+    takes its pointers ``__restrict__``, and most read a neighbourhood of what they store: a shared element is a wrong
+    answer that depends on timing.  Called before anything is allocated or launched for the call."""
+    if t is None:
+        return
+    if _self_overlap(t):
+        raise ValueError(f"{what}: rows of {name} share memory with each other (strides {tuple(t.stride())} for shape "
+                         f"{tuple(t.shape)})")
+    if any(o is not None and _overlap(o, t) for o in apart):
+        raise ValueError(f"{what}: {name} must not share memory with a tensor the call reads or another one it writes")
 
 
 def _output(out, shape, device, what, longer=False, apart=()):
     """The destination of an entry that writes (R, C, L) = ``shape`` -> (out, its RowMap): a new float32 tensor when
     ``out`` is None, else the caller's (R, C, L) tensor or strided (B, n, C, L) view -- the same rows and channels, unit
-    last stride, and the same length (``longer``: at least that length).  ``apart``: tensors ``out`` must share no element
-    with, for kernels that read them again after writing.  A RowMap carries strides only: the library cannot see a short
-    destination, so it is refused here, before any pointer is taken."""
+    last stride, and the same length (``longer``: at least that length).  ``apart``: the tensors ``out`` must share no
+    element with (:func:`_apart`); ``out`` may not overlap itself either.  A RowMap carries strides only: the library cannot
+    see a short destination, so it is refused here, before any pointer is taken."""
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=device)
         return out, rowmap(out)[0]
@@ -182,8 +235,7 @@ def _output(out, shape, device, what, longer=False, apart=()):
     if (R, C) != tuple(shape[:2]) or (L < shape[2] if longer else L != shape[2]):
         raise ValueError(f"{what}: out {tuple(out.shape)} does not match rows={shape[0]}, channels={shape[1]}, "
                          f"length{'>=' if longer else '='}{shape[2]}")
-    if any(_overlap(t, out) for t in apart):
-        raise ValueError(f"{what}: out must not share memory with the input (the kernel makes more than one pass over it)")
+    _apart(what, "out", out, apart)
     return out, omap
 
 

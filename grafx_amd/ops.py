@@ -12,8 +12,15 @@ from collections import namedtuple
 import torch
 
 from ._lib import RowMap, check, lib
-from ._plumbing import (_expect, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks, _state,  # noqa: F401
+from ._plumbing import (_apart, _expect, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks, _state,  # noqa: F401
                         _stream, _timed, profiling, rowmap)
+
+
+# The aliasing rule (include/grafx_amd.h): no tensor a call writes shares an element with one it reads, with another it
+# writes, or with itself.  Every wrapper that writes caller memory names both sides where it takes them: ``apart=`` of
+# _output for ``out``, _apart for what is written beside it (tee, zf, u1_out, odd_alias's out).  The read side is every
+# signal, gradient, envelope, state and kept scan.  Left out: the small per-row parameter tensors and filter taps, which go
+# through pin() / .contiguous(), and the opaque byte buffers the library's own wrappers make (spectra, plans).
 
 
 # ----------------------------------------------------------------------------------------- FIR conv
@@ -121,7 +128,8 @@ def fftconv(x, Hs, N, Cf, Lout=None, off=0, out=None, tee=None, h_rows=None, par
     Lout = L if Lout is None else Lout
     Cout = max(Cin, Cf)
     h_rows = R if h_rows is None else h_rows
-    out, ymap = _output(out, (R, Cout, Lout), x.device, "fftconv", longer=True)
+    _apart("fftconv", "tee", tee, (x,))
+    out, ymap = _output(out, (R, Cout, Lout), x.device, "fftconv", longer=True, apart=(x, tee))
     if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, part_len):
         raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
     pin = _Pin()
@@ -163,8 +171,8 @@ def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=Tru
     the signal, no allocation beyond ``out`` / ``zf`` (pass both for none at all).  Blocks of a signal cut anywhere, each
     entering with the ``zf`` of the one before, concatenate to the linear convolution of the whole.
 
-    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``zf``: optional destination of the state (must not
-    share memory with ``zi``); ``schedule``: "auto" or "tile" (never the persistent kernels).  -> (out, zf); zf is None
+    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``zf``: optional destination of the state (apart from
+    ``x``, ``zi`` and ``out``); ``schedule``: "auto" or "tile" (never the persistent kernels).  -> (out, zf); zf is None
     unless ``return_state`` or a ``zf`` destination is given."""
     _require_gpu(x, out)
     if schedule not in ("auto", "tile"):
@@ -173,17 +181,15 @@ def fftconv_state(x, Hs, N, Cf, zi=None, out=None, h_rows=None, return_state=Tru
     xmap, R, Cin, L = rowmap(x)
     Cout = max(Cin, Cf)
     h_rows = R if h_rows is None else h_rows
-    out, ymap = _output(out, (R, Cout, L), x.device, "fftconv_state", longer=True)
-    if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, 0):
-        raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
     shape = (R, Cin, N - 1)      # rows, input channels, taps - 1: the input history, oldest sample first
     zi = _state(zi, shape, "fftconv_state", "zi")
     zf = _state(zf, shape, "fftconv_state", "zf")
+    _apart("fftconv_state", "zf", zf, (x, zi))        # (the state is written while the history may still be read)
+    out, ymap = _output(out, (R, Cout, L), x.device, "fftconv_state", longer=True, apart=(x, zi, zf))
+    if Hs.numel() != lib().gfx_fir_spectrum_bytes(h_rows * Cf, N, 0):
+        raise ValueError(f"filter spectra hold {Hs.numel()} bytes, expected {h_rows} x {Cf} filters of {N} taps")
     if zf is None and return_state:
         zf = torch.empty(shape, dtype=torch.float32, device=x.device)
-    if zi is not None and zf is not None and _overlap(zi, zf):
-        raise ValueError("fftconv_state: zf must not share memory with zi (the state is written while the history may "
-                         "still be read)")
     pin = _Pin()
     ws = pin.workspace(lib().gfx_fftconv_workspace_bytes(R, Cin, L, L, 0, N, 0), x.device)
     with _timed("fftconv", 4 * R * (Cin * (L + 2 * (N - 1)) + Cout * L), last="gfx_fftconv_last_kernel"):
@@ -205,7 +211,7 @@ def fir_direct(x, h, Lout=None, off=0, out=None, h_rows=None):
         raise ValueError(f"fir_direct: {hr} filter rows given, h_rows={h_rows}")
     Lout = L if Lout is None else Lout
     Cout = max(Cin, Cf)
-    out, ymap = _output(out, (R, Cout, Lout), x.device, "fir_direct", longer=True)
+    out, ymap = _output(out, (R, Cout, Lout), x.device, "fir_direct", longer=True, apart=(x,))
     with _timed("fir_mfma_kernel", 4 * R * (Cin * L + Cout * Lout)):
         check(lib().gfx_fir_direct_f32(_ptr(x), xmap, _ptr(h), h_rows, _ptr(out), ymap, R, Cin, Cf, L, Lout, off, N, _stream()),
               "gfx_fir_direct_f32")
@@ -404,8 +410,18 @@ def odd_alias(z, lo=0, length=None, rows_per_chunk=None, precise=False, out=None
     P = z.shape[-1]
     Q = P - 1
     length = Q - lo if length is None else length
+    rows = z.numel() // P
+    into, omap, Co = out is not None, None, 0
+    if into:
+        # ``out``: a (R, C, length) tensor or a strided (B, n, C, length) view whose rows, channels flattened, are z's
+        # rows: the last column pass writes them in place (the entries' ymap; float transforms only)
+        _require_gpu(out)
+        rmap, Ro, Co, Lo = rowmap(out)
+        if precise or Ro * Co != rows or Lo != length:
+            raise ValueError(f"odd_alias: out {tuple(out.shape)} does not take {rows} rows of {length} samples")
+        _apart("odd_alias", "out", out, (z, rowmax))     # before the plan, the workspace or a copy of z is made
+        omap = ctypes.byref(rmap)
     flat = z.reshape(-1, P).contiguous()
-    rows = flat.shape[0]
     rows_per_chunk = ALIAS_ROWS_PER_CHUNK if rows_per_chunk is None else rows_per_chunk
     pairs = _alias_pairs(P, rows)
     plan = _alias_plan(P, z.device, precise, pairs)
@@ -415,16 +431,7 @@ def odd_alias(z, lo=0, length=None, rows_per_chunk=None, precise=False, out=None
         rowmax = None
     if relu and not (pairs and precise and out is None):
         raise ValueError("odd_alias: relu is fused into the two-rows-per-transform double-precision form only")
-    into, omap, Co = out is not None, None, 0
-    if into:
-        # ``out``: a (R, C, length) tensor or a strided (B, n, C, length) view whose rows, channels flattened, are z's
-        # rows: the last column pass writes them in place (the entries' ymap; float transforms only)
-        _require_gpu(out)
-        rmap, Ro, Co, Lo = rowmap(out)
-        if precise or Ro * Co != rows or Lo != length:
-            raise ValueError(f"odd_alias: out {tuple(out.shape)} does not take {rows} rows of {length} samples")
-        omap = ctypes.byref(rmap)
-    else:
+    if not into:
         out = torch.empty((rows, length), dtype=torch.float32, device=z.device)
     # one record per chunk: the column / tile / column passes of the two chirp-z transforms (czt.hip), read z + write y
     name = (("czt_pair_in_kernel+czt_rows_kernel+czt_pair_mid_kernel+czt_pair_out_kernel" if pairs
@@ -665,13 +672,16 @@ def dynamics_fused(x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir
     _require_gpu(x, out)
     xmap, R, C, L = rowmap(x)
     P = R if param_rows is None else param_rows
-    out, ymap = _output(out, (R, C, L), x.device, "dynamics_fused")
-    pin = _Pin()
     if u1_out is not None:
         _require_gpu(u1_out)
         _expect(u1_out, (R, L), "dynamics_fused: u1_out")
         if not u1_out.is_contiguous() or smoother != 1:
             raise ValueError("dynamics_fused: u1_out must be contiguous and needs the one-pole smoother")
+        _apart("dynamics_fused", "u1_out", u1_out, (x,))
+    # (mix["out"] is outside the rule: its sources are row numbers held on the device, and reading them back would
+    # synchronise; the render's planner keeps the destinations out of the sources -- render/plans.py, tests/test_mix_schedule.py)
+    out, ymap = _output(out, (R, C, L), x.device, "dynamics_fused", apart=(x, u1_out))
+    pin = _Pin()
     tiled = smoother == 1 and schedule == "oneshot"
     ws = pin.workspace(tiled and (lib().gfx_dynamics_ws_bytes_ex(P, R, L) if DYN_LOOKBACK else lib().gfx_dynamics_ws_bytes(P)),
                        x.device)
@@ -733,16 +743,17 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     gmap, Rg, Cg, Lg = rowmap(gy)
     if (Rg, Cg, Lg) != (R, C, L):
         raise ValueError(f"dynamics_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
-    gx, gxmap = _output(out, (R, C, L), x.device, "dynamics_bwd")
+    kept = u1 is not None
+    if kept:
+        _require_gpu(u1)
+        _expect(u1, (R, L), "dynamics_bwd: u1")
+    gx, gxmap = _output(out, (R, C, L), x.device, "dynamics_bwd", apart=(x, gy, u1))
     gp = torch.empty((R, 3), dtype=torch.float32, device=x.device)
     da = torch.empty(R, dtype=torch.float32, device=x.device) if pole else None
     pin = _Pin()
     # the kept scan (with or without the tiles' workspace), or a scratch the scan is rebuilt into (inside the tiles with a
     # workspace, by a pass of its own over every row without)
-    kept = u1 is not None
     if kept:
-        _require_gpu(u1)
-        _expect(u1, (R, L), "dynamics_bwd: u1")
         need_ws = (DYN_SCHEDULE if schedule is None else schedule) == "oneshot"   # one-shot tiles for the short-memory rows
     else:
         u1 = torch.empty((R, L), dtype=torch.float32, device=x.device)
@@ -879,9 +890,9 @@ def dynamics_ballistics(x, log_threshold, log_ratio, log_knee, z_alpha, knee, ga
     z_alpha = z_alpha.contiguous()
     if z_alpha.shape != (P, 2):
         raise ValueError(f"z_alpha must be ({P}, 2), got {tuple(z_alpha.shape)}")
-    # the chunked schedule writes every row in its first pass and re-reads x for the rows it has to walk again
-    out, ymap = _output(out, (R, C, L), x.device, "dynamics_ballistics", apart=(x,))
     zi = _state(zi, (R,), "dynamics_ballistics", "zi")
+    # the chunked schedule writes every row in its first pass and re-reads x for the rows it has to walk again
+    out, ymap = _output(out, (R, C, L), x.device, "dynamics_ballistics", apart=(x, zi))
     zf = torch.empty(R, dtype=torch.float32, device=x.device) if return_state else None
     pin = _Pin()
     with _timed("ballistics_walk_kernel", 8 * R * C * L):
@@ -956,8 +967,8 @@ def apply_gain(x, g, exp_gain=False, out=None):
     _require_gpu(x, g, out)
     xmap, R, C, L = rowmap(x)
     _expect(g, (R, L), "apply_gain: gain")
+    out, ymap = _output(out, (R, C, L), x.device, "apply_gain", apart=(x, g))
     g = g.contiguous()
-    out, ymap = _output(out, (R, C, L), x.device, "apply_gain")
     check(lib().gfx_apply_gain_f32(_ptr(x), xmap, _ptr(g), _ptr(out), ymap, R, C, L, int(exp_gain), _stream()), "gfx_apply_gain_f32")
     return out
 
@@ -969,9 +980,9 @@ def dyn_gain_apply(x, env, log_threshold, log_ratio, log_knee, knee, gate, out=N
     _require_gpu(x, env, out)
     xmap, R, C, L = rowmap(x)
     _expect(env, (R, L), "dyn_gain_apply: envelope")
+    out, ymap = _output(out, (R, C, L), x.device, "dyn_gain_apply", apart=(x, env))
     env = env.contiguous()
     P = R if param_rows is None else param_rows
-    out, ymap = _output(out, (R, C, L), x.device, "dyn_gain_apply")
     pin = _Pin()
     with _timed("dyn_gain_apply_kernel", 4 * R * L * (2 * C + 1)):
         check(lib().gfx_dyn_gain_apply_f32(_ptr(x), xmap, _ptr(env), _ptr(out), ymap, *_curve(pin, log_threshold, log_ratio, log_knee, P),
@@ -986,7 +997,8 @@ def stereo_gain(x, log_gain, out=None, mix=None):
     _require_gpu(x, log_gain, out)
     xmap, R, C, L = rowmap(x)
     _expect(log_gain, (R, 2), "stereo_gain: log_gain")
-    out, ymap = _output(out, (R, 2, L), x.device, "stereo_gain")
+    # (mix["out"] is outside the rule, as in dynamics_fused: device-held sources, kept apart by the render's planner)
+    out, ymap = _output(out, (R, 2, L), x.device, "stereo_gain", apart=(x,))
     pin = _Pin()
     if mix is not None and MIX_FUSION and x.ndim == 4 and out.ndim == 4:
         n = x.shape[1]
@@ -1016,14 +1028,14 @@ def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None, zi=None, return_state=F
     if Rb != R or three != 3 or As.shape != Bs.shape:
         raise ValueError(f"coefficients {tuple(Bs.shape)} / {tuple(As.shape)} do not match {R} rows")
     Cout = max(Cin, Cf)
-    out, ymap = _output(out, (R, Cout, L), x.device, "biquad_cascade")
+    zi = _state(zi, (R, Cout, K, 2), "biquad_cascade", "zi")
+    out, ymap = _output(out, (R, Cout, L), x.device, "biquad_cascade", apart=(x, zi))
     Bs, As = Bs.contiguous(), As.contiguous()
     if zi is None and not return_state:
         with _timed("biquad_cascade_kernel", 4 * R * (Cin + Cout) * L):
             check(lib().gfx_biquad_cascade_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), R, Cin, Cf, K, L,
                                                int(ssm_quirk), _stream()), "gfx_biquad_cascade_f32")
         return out
-    zi = _state(zi, (R, Cout, K, 2), "biquad_cascade", "zi")
     zf = torch.empty((R, Cout, K, 2), dtype=torch.float32, device=x.device)
     with _timed("biquad_cascade_state_kernel", 4 * R * (Cin + Cout) * L + 16 * R * Cout * K):
         check(lib().gfx_biquad_cascade_state_f32(_ptr(x), xmap, _ptr(out), ymap, _ptr(Bs), _ptr(As), _ptr(zi), _ptr(zf),
@@ -1089,7 +1101,7 @@ def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None,
     means this call subtracted (None without ``remove_dc``) -- what waveshaper_bwd needs of them."""
     _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
     xmap, R, C, L = rowmap(x)
-    out, ymap = _output(out, (R, C, L), x.device, "waveshaper")
+    out, ymap = _output(out, (R, C, L), x.device, "waveshaper", apart=(x, dc))
     params, K, dc = _waveshaper_args("waveshaper", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
     with _timed("waveshaper_kernel", 8 * R * C * L):
         check(
@@ -1106,8 +1118,8 @@ def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, 
     """Backward of :func:`waveshaper` in one streaming pass (gfx_waveshaper_bwd_f32) -> (gx, grads).
 
     ``x``, ``gy``: (R,C,L) or strided (B,n,C,L) views; ``want``: which of WS_GRADS to compute (a parameter that was not
-    given is skipped).  ``gx`` is None unless "x" is wanted, else ``out`` (any view of the signal's shape that shares no
-    element with x or gy) or a new (R,C,L) tensor.  ``grads``: {name: (R, n) gradient} of the wanted parameters.
+    given is skipped).  ``gx`` is None unless "x" is wanted, else ``out`` (any view of the signal's shape, apart from x, gy
+    and dc) or a new (R,C,L) tensor.  ``grads``: {name: (R, n) gradient} of the wanted parameters.
     ``dc``: the means the forward subtracted (``waveshaper(..., return_dc=True)``); recomputed when missing."""
     _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
     xmap, R, C, L = rowmap(x)
@@ -1119,7 +1131,7 @@ def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, 
         raise ValueError(f"waveshaper_bwd: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
     gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
     if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, "waveshaper_bwd")
+        dest = _output(out, (R, C, L), x.device, "waveshaper_bwd", apart=(x, gy, dc))
         if "x" in want:
             gx, gxmap = dest
     params, K, dc = _waveshaper_args("waveshaper_bwd", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
@@ -1148,14 +1160,31 @@ def istft_basis(window):
     return basis
 
 
+STFT_MAX_N_FFT = 2048      # the frame the direct-sum kernel holds in LDS (gfx_stft_f32)
+
+
 @_on_device
 def stft(x, window, hop):
     """torch.stft(x, n_fft, hop, window, center=True, pad_mode="reflect", return_complex=True) for rows x (rows, T) on the
     direct-sum kernel (gfx_stft_f32): -> (rows, n_fft // 2 + 1, 1 + T // hop) complex64."""
-    _require_gpu(x, window)
-    x = x.contiguous()
+    _require_gpu(x)
+    if x.ndim != 2:
+        raise ValueError(f"stft: rows of samples (rows, T) expected, got {tuple(x.shape)}")
+    if not isinstance(window, torch.Tensor) or window.ndim != 1 or window.dtype != torch.float32 or window.device != x.device:
+        is_tensor = isinstance(window, torch.Tensor)
+        got = f"{tuple(window.shape)} {window.dtype} on {window.device}" if is_tensor else type(window).__name__
+        raise ValueError(f"stft: the window must be a one-dimensional float32 tensor on {x.device}, got {got}")
     rows, T = x.shape
     n_fft = window.numel()
+    # the limits of gfx_stft_f32 (csrc/reverb.hip), which answers a bare GFX_EINVAL for each
+    if n_fft < 2 or n_fft > STFT_MAX_N_FFT or n_fft % 2:
+        raise ValueError(f"stft: n_fft must be even, from 2 to {STFT_MAX_N_FFT}, got {n_fft} (the window's length)")
+    if hop < 1:
+        raise ValueError(f"stft: hop must be at least 1, got {hop}")
+    if T <= n_fft // 2:
+        raise ValueError(f"stft: rows of {T} samples are too short for n_fft = {n_fft}: the reflect padding needs more than "
+                         f"n_fft // 2 = {n_fft // 2}")
+    x = x.contiguous()
     frames = 1 + T // hop
     out = torch.empty((rows, n_fft // 2 + 1, frames, 2), dtype=torch.float32, device=x.device)
     pin = _Pin()
@@ -1257,6 +1286,9 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):
     """out[b,j] = sum of buf[b, src_idx[e]] over e in [seg_ptr[j], seg_ptr[j+1]); buf/out are (B,V,C,L) views."""
+    # Outside the aliasing rule: ``out`` is usually a node range of ``buf`` itself, and which rows are read is in src_idx,
+    # on the device -- reading it back would synchronise.  The render's planner keeps the destinations out of the sources
+    # (render/plans.py, tests/test_mix_schedule.py).
     _require_gpu(buf, out)
     if buf.stride(-1) != 1 or out.stride(-1) != 1:
         raise ValueError("last dimension must be contiguous")
@@ -1281,6 +1313,7 @@ def gather_sum(buf, src_idx, seg_ptr, out):
 @_on_device
 def gather_sum_fanout(buf, unique_src, dest_mask, out):
     """Fan-out form of :func:`gather_sum`: source rows read once, up to 32 destinations (bit mask per source)."""
+    # outside the aliasing rule, as gather_sum: the source rows are named on the device, the planner keeps them apart
     _require_gpu(buf, out)
     B, _, C, L = buf.shape
     J = out.shape[1]

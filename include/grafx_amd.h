@@ -31,6 +31,18 @@
  * buffer in place (inner = nodes of this type, stride_outer = V*C*L,
  * stride_inner = C*L) as well as plain contiguous (R, C, L) tensors
  * (inner = R, stride_inner = C*L).
+ *
+ * Aliasing: no array a call writes may share an element with an array the
+ * call reads, with another array it writes, or with itself (a row map whose
+ * rows land on the same floats).  Every kernel takes its pointers
+ * __restrict__, and most read more than the element they store -- a halo of
+ * the neighbouring tile, the samples a smoother remembers, x and gy again
+ * after gx -- so a shared element is a wrong answer that depends on timing,
+ * exact in-place use (y == x) included.  Two row ranges of one buffer that
+ * interleave without touching are fine.  ONE exception:
+ * gfx_biquad_cascade_state_f32 takes zi == zf and updates the state in place.
+ * The library sees strides, not extents, so it cannot check this: the caller
+ * does (grafx_amd/ops.py refuses such a call before anything is launched).
  */
 #ifndef GRAFX_AMD_H
 #define GRAFX_AMD_H
@@ -608,8 +620,8 @@ int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t
  * post gain:  gx = G s'(u) pre  (with dc: minus its own mean over time per row-channel, the adjoint of the centring),
  *   g_log_pre_gain (R)  = sum G (s'(u) u - [inverse_post_gain] s(u)),    g_log_post_gain (R) = sum G s(u),
  *   g_p0: (R) bias / (R,2) log_hardness / (R,K) basis weights,           g_p1: (R,2) z_threshold,
- * every sum over the row's C * L samples.  Each output may be null (not computed), not all of them; gx (addressed through
- * its own row map) must not share an element with x or gy.  A gradient may only be asked for a parameter that was given
+ * every sum over the row's C * L samples.  Each output may be null (not computed), not all of them; gx is addressed
+ * through its own row map.  A gradient may only be asked for a parameter that was given
  * (g_log_post_gain: and used, i.e. not under inverse_post_gain).  Row sums are stored per workgroup in `ws`
  * (gfx_waveshaper_bwd_ws_bytes; K = 0 for the two tanh modes) and added in double in a fixed order: no atomics, results
  * are bit-identical from run to run.  ws may be null when only gx is asked and dc is null. */

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from grafx_amd import ops
-from grafx_amd.ops import _output, _read_mix, _row_chunks, _state, rowmap
+from grafx_amd.ops import _apart, _output, _read_mix, _row_chunks, _state, rowmap
 
 SHAPE = (2, 2, 64)
 CPU = torch.device("cpu")
@@ -47,6 +47,28 @@ def test_output_apart():
         _output(buf[:, 3:5], SHAPE, CPU, "t", apart=(x,))
     assert _output(buf[:, 4:6], SHAPE, CPU, "t", apart=(x,))[0].data_ptr() == buf[:, 4:6].data_ptr()
     assert _output(x, SHAPE, CPU, "t")[0] is x          # no list, no refusal
+    assert _output(buf[:, 4:6], SHAPE, CPU, "t", apart=(x, None, buf[:, 0:2]))[0] is not None    # None: an argument not given
+
+
+def test_output_refuses_a_destination_that_overlaps_itself():
+    """Several rows of an expanded view are the same floats: torch refuses such a destination for its own ops."""
+    row = torch.zeros(1, 1, 2, 64)
+    for bad in (row.expand(1, 2, 2, 64), torch.zeros(2, 1, 64).expand(2, 2, 64), torch.zeros(256).as_strided((2, 2, 64), (64, 32, 1))):
+        with pytest.raises(ValueError, match="share memory"):
+            _output(bad, SHAPE, CPU, "t")
+    assert not bool(row.any())
+
+
+def test_apart_checks_what_is_written_beside_out():
+    buf = torch.zeros(1, 6, 2, 64)
+    x, state = buf[:, 2:4], torch.zeros(2, 2, 8)
+    _apart("t", "tee", None, (x,))
+    _apart("t", "tee", buf[:, 4:6], (x, None))
+    _apart("t", "zf", state, (x, torch.zeros(2, 2, 8)))
+    for name, t, apart in (("tee", buf[:, 3:5], (x,)), ("zf", state, (x, state)), ("zf", state.view(-1)[8:24], (state,)),
+                           ("u1_out", buf.view(-1)[256:512].view(2, 128), (x,)), ("tee", buf[:, :1].expand(1, 2, 2, 64), ())):
+        with pytest.raises(ValueError, match=f"t: .*{name}.* share memory"):
+            _apart("t", name, t, apart)
 
 
 def test_state_refusals_name_entry_argument_shape_and_value():
