@@ -105,6 +105,9 @@ SIGNATURES = {
                                                     ctypes.c_int, vp]),
     "gfx_noise_shaping_ir_f32": (ctypes.c_int, [f32p, i64, f32p, f32p, f32p, f32p, f32p, i64, i64, i64, i64,
                                                 ctypes.c_float, ctypes.c_float, vp]),
+    "gfx_noise_shaping_ir_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),
+    "gfx_noise_shaping_ir_bwd_f32": (ctypes.c_int, [f32p, f32p, f32p, f32p, i64, f32p, f32p, f32p, f32p, f32p, f32p, f32p,
+                                                    f32p, i64, i64, i64, i64, ctypes.c_float, ctypes.c_float, vp, sz, vp]),
     "gfx_row_mean_f32": (ctypes.c_int, [f32p, RowMap, f32p, i64, i64, i64, vp]),
     "gfx_waveshaper_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, f32p, f32p, f32p, f32p, i64, f32p, vp]),

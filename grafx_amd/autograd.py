@@ -688,6 +688,37 @@ class StftReverbIrFn(torch.autograd.Function):
                 None if g_env is None else g_env.view(gain_env.shape), None, None, None, None, None, None, None)
 
 
+class NoiseShapingIrFn(torch.autograd.Function):
+    """The taps of FilteredNoiseShapingReverb (reverb.py:343-366, normalize_impulse) as one autograd node: forward is the
+    inference kernel (``ops.noise_shaping_ir``) on exactly the noise view the module chose, times the row gain when
+    ``normalise`` is set -- the expression processors.core.utils.normalize_impulse evaluates, so the taps under autograd are
+    the inference taps bit for bit; backward is its adjoint ``gfx_noise_shaping_ir_bwd_f32`` -- instead of the exp / product
+    / sum chain of torch ops with its (R, C, K, ir_len) envelope tensors on autograd's tape.  Saved: the parameters, the
+    noise view (backward sees the window of the forward) and, when normalising, the un-normalised taps and the R gains.
+    The noise gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, log_decay, log_gain, log_fade_in, z_fade_in_gain, noise, ir_len, min_decay, max_decay, normalise):
+        ir = ops.noise_shaping_ir(noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, ir_len, min_decay, max_decay)
+        ctx.cfg = (min_decay, max_decay, bool(normalise))
+        if not normalise:
+            ctx.save_for_backward(log_decay, log_gain, log_fade_in, z_fade_in_gain, noise, None, None)
+            return ir
+        gain = torch.rsqrt((ir * ir).sum(dim=-1, keepdim=True).mean(dim=-2, keepdim=True) + 1e-12)   # normalize_impulse
+        ctx.save_for_backward(log_decay, log_gain, log_fade_in, z_fade_in_gain, noise, ir, gain)
+        return ir * gain
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gh):
+        log_decay, log_gain, log_fade_in, z_fade_in_gain, noise, ir, gain = ctx.saved_tensors
+        min_decay, max_decay, normalise = ctx.cfg
+        want = [name for name, need in zip(ops.NS_GRADS, ctx.needs_input_grad) if need]
+        grads = ops.noise_shaping_ir_bwd(gh, noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, min_decay, max_decay,
+                                         ir=ir if normalise else None, row_gain=gain if normalise else None, want=want)
+        return (*(grads.get(name) for name in ops.NS_GRADS), None, None, None, None, None)
+
+
 def truncated_one_pole(u, z_alpha, iir_len, exact=False):
     """core/envelope.py:34-49."""
     from .processors.core.convolution import reference_aliases

@@ -1060,6 +1060,78 @@ def noise_shaping_ir(noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, ir
     return ir
 
 
+NS_GRADS = ("log_decay", "log_gain", "log_fade_in", "z_fade_in_gain")
+NS_BWD_ROWS = 1 << 16      # rows per gfx_noise_shaping_ir_bwd_f32 call: bounds the workspace of a call without one
+
+
+def noise_shaping_ir_bwd_ws_bytes(R, C, K, ir_len):
+    """Bytes of workspace one gfx_noise_shaping_ir_bwd_f32 call over R rows needs (no GPU involved)."""
+    return lib().gfx_noise_shaping_ir_bwd_ws_bytes(R, C, K, ir_len)
+
+
+@_on_device
+def noise_shaping_ir_bwd(grad_ir, noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, min_decay, max_decay, ir=None,
+                         row_gain=None, want=NS_GRADS, ws=None):
+    """Backward of :func:`noise_shaping_ir` (gfx_noise_shaping_ir_bwd_f32) -> {name: (R,C,K) gradient} for the names of
+    ``want`` (any of NS_GRADS; a fade parameter that was not given is skipped).
+
+    ``grad_ir``: dL/dh (R,C,ir_len).  With ``ir`` (the forward's output) and ``row_gain`` (R values, 1 / sqrt(mean_c sum_t
+    ir^2 + 1e-12)) h = row_gain * ir, the normalised taps; without them h = ir.  ``noise`` must be the (C,K,>=ir_len) view
+    the forward was given.  ``ws``: a uint8 workspace of at least ``noise_shaping_ir_bwd_ws_bytes(min(R, NS_BWD_ROWS), C,
+    K, ir_len)`` bytes to reuse; it may share memory with none of the inputs."""
+    what = "noise_shaping_ir_bwd"
+    _require_gpu(grad_ir, noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, ir, row_gain)
+    R, C, K = log_decay.shape
+    if grad_ir.ndim != 3 or tuple(grad_ir.shape[:2]) != (R, C):
+        raise ValueError(f"{what}: gradient {tuple(grad_ir.shape)} does not match the parameters {tuple(log_decay.shape)}")
+    ir_len = grad_ir.shape[2]
+    if (noise.shape[:2] != (C, K) or noise.stride(-1) != 1 or noise.stride(1) != noise.stride(0) // K
+            or noise.shape[2] < ir_len):
+        raise ValueError("noise must be a (C, K, T) view of a contiguous band-split noise buffer")
+    if (ir is None) != (row_gain is None):
+        raise ValueError(f"{what}: ir and row_gain come together (the normalised taps) or not at all")
+    if (log_fade_in is None) != (z_fade_in_gain is None):
+        raise ValueError(f"{what}: log_fade_in and z_fade_in_gain come together or not at all")
+    given = {"log_decay": log_decay, "log_gain": log_gain, "log_fade_in": log_fade_in, "z_fade_in_gain": z_fade_in_gain}
+    for name, t in given.items():
+        _expect(t, (R, C, K), f"{what}: {name}")
+    _expect(ir, (R, C, ir_len), f"{what}: ir")
+    unknown = set(want) - set(NS_GRADS)
+    if unknown:
+        raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {NS_GRADS})")
+    names = [k for k in NS_GRADS if k in want and given[k] is not None]
+    if not names:
+        raise ValueError(f"{what}: no gradient asked for ({tuple(want)})")
+    if K > 64:
+        raise ValueError(f"{what}: at most 64 bands, got {K}")
+    if row_gain is not None:
+        if row_gain.numel() != R:
+            raise ValueError(f"{what}: {row_gain.numel()} gains for {R} rows")
+        row_gain = row_gain.reshape(R).contiguous()
+    nbytes = lib().gfx_noise_shaping_ir_bwd_ws_bytes(min(R, NS_BWD_ROWS), C, K, ir_len)
+    if ws is not None:
+        _apart(what, "ws", ws, (grad_ir, noise, *given.values(), ir, row_gain))
+        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
+            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
+    grad_ir = grad_ir.contiguous()
+    ir = None if ir is None else ir.contiguous()
+    given = {k: None if t is None else t.contiguous() for k, t in given.items()}
+    grads = {k: torch.empty((R, C, K), dtype=torch.float32, device=grad_ir.device) for k in names}
+    cut = lambda t, r0, n: None if t is None else t[r0:r0 + n]  # noqa: E731
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, grad_ir.device)
+    with _timed("noise_shaping_ir_bwd_kernel", 4 * R * C * ir_len * (1 if ir is None else 2)):
+        for r0, n in _row_chunks(R, NS_BWD_ROWS):
+            check(
+                lib().gfx_noise_shaping_ir_bwd_f32(_ptr(grad_ir[r0:r0 + n]), _ptr(cut(ir, r0, n)), _ptr(cut(row_gain, r0, n)),
+                                                   _ptr(noise), noise.stride(1), *(_ptr(cut(t, r0, n)) for t in given.values()),
+                                                   *(_ptr(cut(grads.get(k), r0, n)) for k in NS_GRADS), n, C, K, ir_len,
+                                                   float(min_decay), float(max_decay), *wsarg, _stream()),
+                "gfx_noise_shaping_ir_bwd_f32",
+            )
+    return grads
+
+
 # ----------------------------------------------------------------------------------------- waveshapers
 WS_TANH, WS_PIECEWISE, WS_POWER, WS_CHEBYSHEV = 0, 1, 2, 3
 

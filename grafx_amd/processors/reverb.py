@@ -271,7 +271,9 @@ class FilteredNoiseShapingReverb(StreamIO, nn.Module):
     Init: uniform noise split into `num_bands` bands by a Linkwitz-Riley crossover (host side, scipy).
     Forward: `gfx_noise_shaping_ir_f32` sums the K decaying bands into the impulse response (the reference
     materialises a (B, C, K, ir_len) envelope tensor for this), the response is energy-normalised and the
-    HIP overlap-save convolution applies it (uniformly partitioned for the default 60 000 taps)."""
+    HIP overlap-save convolution applies it (uniformly partitioned for the default 60 000 taps).
+    Under gradients the same kernel is the forward of one autograd node whose backward is `gfx_noise_shaping_ir_bwd_f32`
+    (`_taps`); `torch_compute_ir` keeps the formula as torch ops."""
 
     def __init__(self, ir_len=60000, num_bands=12, processor_channel="midside", f_min=31.5, f_max=15000, scale="log",
                  sr=30000, zerophase=True, order=2, noise_randomness="pseudo-random", use_fade_in=False,
@@ -309,17 +311,32 @@ class FilteredNoiseShapingReverb(StreamIO, nn.Module):
         return self.filtered_noise[..., start : start + self.ir_len]
 
     def compute_ir(self, log_decay, log_gain, log_fade_in=None, z_fade_in_gain=None):
+        """Un-normalised impulse responses (R, C, ir_len) (reverb.py:343-366)."""
+        return self._taps(log_decay, log_gain, log_fade_in, z_fade_in_gain, False)
+
+    def _taps(self, log_decay, log_gain, log_fade_in, z_fade_in_gain, normalise):
+        """The impulse responses on the native kernels, normalised or not.  Under gradients one node
+        (autograd.NoiseShapingIrFn: the inference kernel forward, gfx_noise_shaping_ir_bwd_f32 backward, on the noise
+        window this call cut); without, the inference kernel and normalize_impulse."""
         noise = self.get_filtered_noise()
         fade = (log_fade_in, z_fade_in_gain) if self.use_fade_in else (None, None)
         if needs_grad(log_decay, log_gain, *fade):
-            d = torch.sigmoid(log_decay) * (self.max_decay - self.min_decay) + self.min_decay
-            env = torch.exp(self.arange * d.unsqueeze(-1))
-            if self.use_fade_in:
-                f = torch.sigmoid(fade[0]) * (d - self.min_decay) + self.min_decay
-                env = env - torch.exp(self.arange * f.unsqueeze(-1)) * torch.sigmoid(fade[1]).unsqueeze(-1)
-            return (noise * (env * log_gain.unsqueeze(-1))).sum(2)
-        return ops.noise_shaping_ir(noise[0], log_decay, log_gain, fade[0], fade[1], self.ir_len, self.min_decay,
-                                    self.max_decay)
+            return diff.NoiseShapingIrFn.apply(log_decay, log_gain, fade[0], fade[1], noise[0], self.ir_len,
+                                               self.min_decay, self.max_decay, normalise)
+        ir = ops.noise_shaping_ir(noise[0], log_decay, log_gain, fade[0], fade[1], self.ir_len, self.min_decay,
+                                  self.max_decay)
+        return normalize_impulse(ir) if normalise else ir
+
+    def torch_compute_ir(self, log_decay, log_gain, log_fade_in=None, z_fade_in_gain=None):
+        """reverb.py:343-366 with torch ops, the (R, C, K, ir_len) envelope tensor materialised: the formula, and the
+        baseline of tools/noise_shaping_ir_bwd_bench.py.  No call of the module runs it."""
+        noise = self.get_filtered_noise()
+        d = torch.sigmoid(log_decay) * (self.max_decay - self.min_decay) + self.min_decay
+        env = torch.exp(self.arange * d.unsqueeze(-1))
+        if self.use_fade_in:
+            f = torch.sigmoid(log_fade_in) * (d - self.min_decay) + self.min_decay
+            env = env - torch.exp(self.arange * f.unsqueeze(-1)) * torch.sigmoid(z_fade_in_gain).unsqueeze(-1)
+        return (noise * (env * log_gain.unsqueeze(-1))).sum(2)
 
     def forward(self, input_signals, log_decay, log_gain, log_fade_in=None, z_fade_in_gain=None, state=None,
                 return_state=False):
@@ -333,7 +350,7 @@ class FilteredNoiseShapingReverb(StreamIO, nn.Module):
         block = {} if state is None and not return_state else {"state": state, "return_state": True}
         if block:
             self.stream_check()
-        ir = normalize_impulse(self.compute_ir(log_decay, log_gain, log_fade_in, z_fade_in_gain))
+        ir = self._taps(log_decay, log_gain, log_fade_in, z_fade_in_gain, True)
         x = lr_to_ms(input_signals) if self.processor_channel == "midside" else input_signals
         y = self.conv(x, ir, **block)
         y, zf = y if block else (y, None)

@@ -595,6 +595,29 @@ int gfx_biquad_cascade_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gf
 int gfx_noise_shaping_ir_f32(const float* noise, int64_t noise_stride, const float* log_decay, const float* log_gain,
                              const float* log_fade_in, const float* z_fade_in_gain, float* ir, int64_t R, int64_t C,
                              int64_t K, int64_t ir_len, float min_decay, float max_decay, void* stream);
+/* Backward of gfx_noise_shaping_ir_f32: the gradients of the parameters from grad_ir = dL/dh (R, C, ir_len), h the taps the
+ * forward call with the same noise (pointer and stride), parameters and decay range produced.
+ *   ir, row_gain both given: h = row_gain * ir (normalize_impulse applied), `ir` (R, C, ir_len) being that forward call's
+ *                            output and row_gain[r] = 1 / sqrt(mean_c sum_t ir[r,c,t]^2 + 1e-12) (R);
+ *   both null:               h = ir, the un-normalised taps.
+ * The fade pair is both null or both set, as in the forward.  Outputs (R, C, K), each nullable (not computed), not all of
+ * them; g_log_fade_in and g_z_fade_in_gain need the fade pair.  Every element of a given output is written.
+ * With e_d = exp(t d), e_f = exp(t f), fg = sigmoid(z_fade_in_gain) and v = dL/d(ir) (grad_ir, or for the normalised taps
+ * row_gain grad_ir - row_gain^3 / C <grad_ir, ir>_row ir) the kernel takes, per (r, c, k), the four sums over t of
+ * v noise {e_d, t e_d, e_f, t e_f}: one workgroup owns 2048 consecutive samples of one (r, c), keeps its grad_ir and ir
+ * samples in registers and loops over the K bands.  No atomics: the per-workgroup sums (taken against grad_ir and against ir
+ * separately, and the workgroup's share of <grad_ir, ir>) go to `ws` and a second kernel adds them in double in workgroup
+ * order and applies the chain rule (sigmoid' = s (1 - s): 0 at a saturated parameter), so results are bit-identical from
+ * run to run and a row's gradients do not depend on the other rows of the call.
+ * gfx_noise_shaping_ir_bwd_ws_bytes = R * C * ceil(ir_len / 2048) * (8 K + 1) floats (0 for a zero or negative argument).
+ * Nothing is allocated or synchronised.  K <= 64; R * C beyond one launch's grid is split on channel boundaries. */
+size_t gfx_noise_shaping_ir_bwd_ws_bytes(int64_t R, int64_t C, int64_t K, int64_t ir_len);
+int gfx_noise_shaping_ir_bwd_f32(const float* grad_ir, const float* ir, const float* row_gain, const float* noise,
+                                 int64_t noise_stride, const float* log_decay, const float* log_gain,
+                                 const float* log_fade_in, const float* z_fade_in_gain, float* g_log_decay,
+                                 float* g_log_gain, float* g_log_fade_in, float* g_z_fade_in_gain, int64_t R, int64_t C,
+                                 int64_t K, int64_t ir_len, float min_decay, float max_decay, void* ws, size_t ws_bytes,
+                                 void* stream);
 
 /* ---- memoryless waveshapers --------------------------------------------------------------
  * replaces the forward() of TanhDistortion (nonlinear.py:46-79), PiecewiseTanhDistortion (120-175),
