@@ -1248,7 +1248,7 @@ def stft(x, window, hop):
         raise ValueError(f"stft: the window must be a one-dimensional float32 tensor on {x.device}, got {got}")
     rows, T = x.shape
     n_fft = window.numel()
-    # the limits of gfx_stft_f32 (csrc/reverb.hip), which answers a bare GFX_EINVAL for each
+    # the limits of gfx_stft_f32 (csrc/stft.hip), which answers a bare GFX_EINVAL for each
     if n_fft < 2 or n_fft > STFT_MAX_N_FFT or n_fft % 2:
         raise ValueError(f"stft: n_fft must be even, from 2 to {STFT_MAX_N_FFT}, got {n_fft} (the window's length)")
     if hop < 1:

@@ -55,14 +55,23 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         return ops.built_once(self._basis, (device.type, device.index), lambda: ops.istft_basis(self.window), device,
                               "STFTMaskedNoiseReverb: the inverse-STFT bases")
 
+    def _noise(self, rows, device):
+        """The noise spectra the mask shapes: the fixed one, or with fixed_noise=False (reverb.py:63, 80-82, 165) fresh
+        noise for every row, its STFT on gfx_stft_f32 -- the kernels behind it are the same."""
+        return self.noise_stft if self.fixed_noise else self.sample_noise(rows, device)
+
     def _ir_and_gain(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, ms_lr):
         genv = gain_env_log_magnitude if self.gain_envelope else None
-        # fixed_noise=False (reverb.py:63, 80-82, 165): fresh noise for every row, its STFT on gfx_stft_f32, mask + inverse
-        # STFT + overlap-add + normalisation on the same native kernels as the fixed noise
-        noise = self.noise_stft if self.fixed_noise else self.sample_noise(init_log_magnitude.shape[0],
-                                                                          init_log_magnitude.device)
+        noise = self._noise(init_log_magnitude.shape[0], init_log_magnitude.device)
         return ops.stft_reverb_ir(noise, init_log_magnitude, delta_log_magnitude, genv, self.window,
                                   self._istft_basis(init_log_magnitude.device), self.ir_len, self.hop_length, ms_lr)
+
+    def _tap_spectra(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo):
+        """(Hs, R): the tile spectra of the R impulse responses.  normalize_impulse (core/utils.py:14-18) is folded into
+        the tap -> spectrum step."""
+        ir, gain = self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
+        R = ir.shape[0]
+        return ops.fir_spectrum(ir.view(R * 2, self.ir_len), gain=gain, gain_div=2), R
 
     def compute_ir(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None):
         """Un-normalised mid/side impulse responses (R,2,ir_len) (reverb.py:161-187)."""
@@ -88,8 +97,7 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
     def _native_taps(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, ms_lr, normalise):
         """The taps under autograd, one node: the inference kernel forward, gfx_stft_reverb_ir_bwd_f32 backward."""
         genv = gain_env_log_magnitude if self.gain_envelope else None
-        noise = self.noise_stft if self.fixed_noise else self.sample_noise(init_log_magnitude.shape[0],
-                                                                          init_log_magnitude.device)
+        noise = self._noise(init_log_magnitude.shape[0], init_log_magnitude.device)
         return diff.StftReverbIrFn.apply(init_log_magnitude, delta_log_magnitude, genv, noise, self.window,
                                          self._istft_basis(init_log_magnitude.device), self.ir_len, self.hop_length,
                                          ms_lr, normalise)
@@ -104,11 +112,8 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
     def _compute_ir_differentiable(self, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None):
         """reverb.py:161-200 with torch ops (mask, istft): the formula, and the training path of every transform size
         but the default one (see _native_backward)."""
-        logmag = init_log_magnitude[..., None] - F.softplus(delta_log_magnitude)[..., None] * self.arange
-        if self.gain_envelope:
-            logmag = logmag + gain_env_log_magnitude[:, :, None, :]
-        noise_stft = self.noise_stft if self.fixed_noise else self.sample_noise(logmag.shape[0], logmag.device)
-        spec = noise_stft * torch.exp(logmag / 8)
+        mask = self.compute_stft_mask(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
+        spec = self._noise(mask.shape[0], mask.device) * mask
         R = spec.shape[0]
         return self._istft(spec.reshape(R * 2, self.num_bins, self.num_frames)).view(R, 2, self.ir_len)
 
@@ -157,9 +162,8 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         if (not self.fixed_noise or self.processor_channel == "midside"
                 or needs_grad(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)):
             return None
-        ir, gain = self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude,
-                                     self.processor_channel == "pseudo_midside")
-        return Prepared(ops.fir_spectrum(ir.view(ir.shape[0] * 2, self.ir_len), gain=gain, gain_div=2))
+        return Prepared(self._tap_spectra(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude,
+                                          self.processor_channel == "pseudo_midside")[0])
 
     def forward(self, input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude=None, _out=None,
                 _shared_rows=None, _prepared=None, state=None, return_state=False):
@@ -171,82 +175,52 @@ class STFTMaskedNoiseReverb(BufferIO, nn.Module):
         aliasing is a property of one whole-signal transform and has no block form.  ``fixed_noise=False`` raises with
         a state: a fresh impulse response per block is not a stream.  ``(y, state)`` comes back when a state is asked
         for; the in-place ``_out`` and ``_prepared`` paths take both arguments too."""
-        if state is not None or return_state:
-            return self._forward_block(input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, _out,
-                                       _shared_rows, _prepared, state, return_state)
+        x, N = input_signals, self.ir_len
+        block = state is not None or return_state
+        if block:
+            self.stream_check()  # (one call may draw its noise afresh, a chain of blocks may not)
+        # what convolve_taps is told: one call follows the module's flashfftconv flag, a block is the linear convolution
+        conv = {"state": state, "return_state": return_state} if block else {"exact": self.flashfftconv}
         if _prepared is not None:
-            return convolve_taps(input_signals, _prepared.tensors[0], self.ir_len, 2, "causal", out=_out,
-                                 exact=self.flashfftconv, h_rows=_shared_rows)
-        pseudo = self.processor_channel == "pseudo_midside"
-        if _shared_rows is not None and not self.fixed_noise:  # a noise per row: one parameter row per signal row
-            reps = shared_reps(input_signals, _shared_rows)
-            init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude = (
-                expand_shared(t, reps) for t in (init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude))
-            _shared_rows = None
-        if needs_grad(input_signals, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude):
-            # training: the taps on one native node (autograd.StftReverbIrFn; other transform sizes: mask + istft as torch
-            # ops), the convolution below is native either way.  The impulse responses are synthesised once per parameter
-            # row (per node when the batch shares them) and the native convolution lets every batch row read them; a
-            # strided (B, n, C, L) view is read in place
-            h = self._training_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
-            if pseudo:
-                y = diff.convolve(input_signals, h, "causal", exact=self.flashfftconv, final=True)
-            elif self.processor_channel == "midside":
-                x = input_signals.reshape(-1, *input_signals.shape[-2:])
-                if h.shape[0] != x.shape[0]:
-                    h = expand_shared(h, x.shape[0] // h.shape[0])
-                y = ms_to_lr(diff.convolve(lr_to_ms(x), h, "causal", exact=self.flashfftconv, final=True))
-            else:
-                y = diff.convolve(input_signals, h, "causal", exact=self.flashfftconv, final=True)
-            if _out is None:
-                return y
-            _out.copy_(y.view(_out.shape))
-            return _out
-        ir, gain = self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
-        R = ir.shape[0]
-        # normalize_impulse (core/utils.py:14-18) is folded into the tap -> spectrum step
-        Hs = ops.fir_spectrum(ir.view(R * 2, self.ir_len), gain=gain, gain_div=2)
-        if self.processor_channel == "midside":  # reverb.py:219-223
-            return ms_to_lr(convolve_taps(lr_to_ms(input_signals), Hs, self.ir_len, 2, "causal", exact=self.flashfftconv))
-        return convolve_taps(input_signals, Hs, self.ir_len, 2, "causal", out=_out, exact=self.flashfftconv,
-                             h_rows=_shared_rows)
-
-    def _forward_block(self, x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, _out, _shared_rows,
-                       _prepared, state, return_state):
-        """forward() with a carried state: the same impulse responses, the stateful causal convolution."""
-        self.stream_check()
-        N = self.ir_len
-        if _prepared is not None:
-            return convolve_taps(x, _prepared.tensors[0], N, 2, "causal", out=_out, h_rows=_shared_rows, state=state,
-                                 return_state=return_state)
+            return convolve_taps(x, _prepared.tensors[0], N, 2, "causal", out=_out, h_rows=_shared_rows, **conv)
         pseudo = self.processor_channel == "pseudo_midside"
         midside = self.processor_channel == "midside"
-        if needs_grad(x, init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, state):
-            h = self._training_taps(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
-            xs = x.reshape(-1, *x.shape[-2:]) if midside else x
-            if midside:
-                xs = lr_to_ms(xs)
-                if h.shape[0] != xs.shape[0]:
-                    h = expand_shared(h, xs.shape[0] // h.shape[0])
-            y, zf = diff.convolve(xs, h, "causal", state=check_state(state, xs, N, "STFTMaskedNoiseReverb"),
-                                  return_state=True)
-            if midside:
-                y = ms_to_lr(y)
-            if _out is not None:
-                _out.copy_(y.view(_out.shape))
-                y = _out
-            return (y, zf) if return_state else y
-        ir, gain = self._ir_and_gain(init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude, pseudo)
-        Hs = ops.fir_spectrum(ir.view(ir.shape[0] * 2, N), gain=gain, gain_div=2)
-        if midside:  # the history is the mid/side signal the convolution reads
-            xs = lr_to_ms(x.reshape(-1, *x.shape[-2:]))
-            y, zf = convolve_taps(xs, Hs, N, 2, "causal", h_rows=_shared_rows or ir.shape[0], state=state, return_state=True)
+        params = (init_log_magnitude, delta_log_magnitude, gain_env_log_magnitude)
+        if _shared_rows is not None and not self.fixed_noise:  # a noise per row: one parameter row per signal row
+            # (one call only: with fixed_noise=False a block has raised above)
+            params = tuple(expand_shared(t, shared_reps(x, _shared_rows)) for t in params)
+            _shared_rows = None
+        training = needs_grad(x, *params, state)
+        if training:
+            # the taps on one native node (autograd.StftReverbIrFn; other transform sizes: mask + istft as torch ops), the
+            # convolution below is native either way.  The impulse responses are synthesised once per parameter row (per
+            # node when the batch shares them) and the native convolution lets every batch row read them; a strided
+            # (B, n, C, L) view is read in place
+            h = self._training_taps(*params, pseudo)
+        else:
+            Hs, R = self._tap_spectra(*params, pseudo)
+            if not midside:
+                return convolve_taps(x, Hs, N, 2, "causal", out=_out, h_rows=_shared_rows, **conv)
+        if midside:  # reverb.py:219-223; the history is the mid/side signal the convolution reads
+            # one-call inference hands its input over as it comes; training and blocks flatten the rows first
+            x = lr_to_ms(x.reshape(-1, *x.shape[-2:]) if training or block else x)
+            if training and h.shape[0] != x.shape[0]:
+                h = expand_shared(h, x.shape[0] // h.shape[0])
+        zf = None
+        if training and block:  # neither exact= nor final=: the stateful convolution is the linear one
+            y, zf = diff.convolve(x, h, "causal", state=check_state(state, x, N, "STFTMaskedNoiseReverb"), return_state=True)
+        elif training:
+            y = diff.convolve(x, h, "causal", exact=self.flashfftconv, final=True)
+        elif block:  # mid/side inference from here on
+            y, zf = convolve_taps(x, Hs, N, 2, "causal", h_rows=_shared_rows or R, state=state, return_state=True)
+        else:  # neither out= nor h_rows=: render_into routes mid/side around this path
+            y = convolve_taps(x, Hs, N, 2, "causal", exact=self.flashfftconv)
+        if midside:
             y = ms_to_lr(y)
-            if _out is not None:
-                _out.copy_(y.view(_out.shape))
-                y = _out
-            return (y, zf) if return_state else y
-        return convolve_taps(x, Hs, N, 2, "causal", out=_out, h_rows=_shared_rows, state=state, return_state=return_state)
+        if _out is not None and (training or block):  # (one-call mid/side inference returns a new tensor even with _out)
+            _out.copy_(y.view(_out.shape))
+            y = _out
+        return (y, zf) if return_state else y
 
     def stream_check(self):
         if not self.fixed_noise:

@@ -93,6 +93,24 @@ def test_size_queries_need_no_gpu():
     assert lib.gfx_fftconv_workspace_bytes(2, 2, 131072, 131072, 0, 60001, 0) == 2 * 2 * (16 + 7) * 17 * 256 * 16
     assert lib.gfx_iir_fsm_plan_bytes(4001) == (8192 + 4096 + 2 * 2052) * 8 and lib.gfx_iir_fsm_plan_bytes(5000) == 0
     assert lib.gfx_istft_basis_bytes(384) == (388 * 384 + 193 * 2 * 208 + 2 * 384) * 4   # full basis, half basis, FFT factors
+    # the reverb's impulse-response workspace.  FFT form (n_fft 384, hop 192, schedule AUTO = 0 or FFT = 2): one energy
+    # partial per workgroup of 15 blocks of 192 samples; 2880 / 2881 lie either side of a 15-block seam
+    def ceil(a, b):
+        return -(-a // b)
+
+    for sched in (0, 2):
+        for R in (1, 3):
+            for ir_len, wgs in ((193, 1), (2880, 1), (2881, 2), (60000, 21)):
+                assert ceil(ceil(ir_len, 192), 15) == wgs
+                assert lib.gfx_stft_reverb_workspace_bytes(R, ir_len, 384, 192, 1 + ir_len // 192, sched) == R * wgs * 4
+    # matrix-core form (schedule GEMM = 1, or any other transform size): the frames, then a partial per 256 samples
+    for R in (1, 3):
+        for n_fft, hop, T, sched in ((384, 192, 313, 1), (256, 128, 32, 0)):
+            want = (R * 2 * T * n_fft + R * ceil(T * n_fft, 256)) * 4
+            assert lib.gfx_stft_reverb_workspace_bytes(R, 60000 if T == 313 else 4000, n_fft, hop, T, sched) == want
+    for bad in ((0, 400, 384, 192, 3), (1, 0, 384, 192, 3), (1, 400, 0, 192, 3), (1, 400, 384, 192, 0),
+                (-1, 400, 384, 192, 3), (1, -400, 384, 192, 3), (1, 400, -384, 192, 3), (1, 400, 384, 192, -3)):
+        assert lib.gfx_stft_reverb_workspace_bytes(*bad, 0) == 0
     # the odd-length aliasing: one row per transform needs (3P - 1) / 2 points (25 tiles at P = 135 071), two rows per
     # transform 2P - 1 per pair (35 tiles); the pair form ends at 2^24 points, even lengths do not alias at all
     P = 131072 + 4000 - 1

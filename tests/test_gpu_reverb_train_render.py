@@ -174,6 +174,32 @@ def test_other_transform_sizes_keep_the_torch_chain():
         assert_close(a.cpu().double(), b, 1e-5, f"n_fft 256: gradient of {name}")
 
 
+def test_midside_inference_blocks_write_the_given_buffer():
+    """processor_channel="midside" without gradients, with state= and _out=: the block is written into _out, the state
+    that comes back is the last ir_len - 1 samples of the mid/side signal fed in (zeros before the first), and two blocks
+    concatenate to the one-call output under exact convolution, at the 1e-5 of the peak of the stream tests of
+    test_gpu_render_state.py.  400 taps are 3 frames; 1000 samples cut at 333, the first block shorter than the history."""
+    from grafx_amd.processors import STFTMaskedNoiseReverb
+    from grafx_amd.processors.core.convolution import exact_convolution_scope
+    from grafx_amd.processors.core.midside import lr_to_ms
+
+    rows, N, length, cut = 3, 400, 1000, 333
+    m = STFTMaskedNoiseReverb(ir_len=N, processor_channel="midside", flashfftconv=False).cuda()
+    x, p, _ = _inputs(m, 10, rows=rows, length=length)
+    x, p = x.cuda(), {k: v.cuda() for k, v in p.items()}
+    with torch.no_grad(), exact_convolution_scope(True):
+        want = m(x, **p)
+        out = torch.full_like(x, float("nan"))
+        y1, s1 = m(x[..., :cut], **p, _out=out[..., :cut], return_state=True)
+        y2, s2 = m(x[..., cut:], **p, _out=out[..., cut:], state=s1, return_state=True)
+    assert y1.data_ptr() == out.data_ptr() and y2.data_ptr() == out[..., cut:].data_ptr()
+    assert torch.equal(y1, out[..., :cut]) and torch.equal(y2, out[..., cut:])
+    fed = torch.cat([x.new_zeros(rows, 2, N - 1), lr_to_ms(x)], -1)
+    assert tuple(s1.shape) == tuple(s2.shape) == (rows, 2, N - 1)
+    assert torch.equal(s1, fed[..., cut : cut + N - 1]) and torch.equal(s2, fed[..., length:])
+    assert_close(out.cpu(), want.cpu(), 1e-5, "midside blocks into _out against the one call")
+
+
 # ------------------------------------------------------------------------------------------------ through render_grafx
 B, LR, N_REV, N_FSM, N_IIR = 2, 4096, 1501, 257, 255
 
