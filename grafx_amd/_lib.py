@@ -103,6 +103,9 @@ SIGNATURES = {
     "gfx_biquad_cascade_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, i64, i64, i64, i64, i64, ctypes.c_int, vp]),
     "gfx_biquad_cascade_state_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, f32p, f32p, i64, i64, i64, i64, i64,
                                                     ctypes.c_int, vp]),
+    "gfx_biquad_cascade_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),
+    "gfx_biquad_cascade_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, RowMap, f32p, f32p, f32p, f32p, f32p, f32p,
+                                                  f32p, vp, sz, i64, i64, i64, i64, i64, vp]),
     "gfx_noise_shaping_ir_f32": (ctypes.c_int, [f32p, i64, f32p, f32p, f32p, f32p, f32p, i64, i64, i64, i64,
                                                 ctypes.c_float, ctypes.c_float, vp]),
     "gfx_noise_shaping_ir_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),

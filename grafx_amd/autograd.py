@@ -801,54 +801,23 @@ class BiquadCascadeFn(torch.autograd.Function):
     """y = H_K ... H_1 x with H_i = B_i(z) / A_i(z), the exact recursion of gfx_biquad_cascade_f32 (reference
     core/iir.py:154-183: one torchaudio.lfilter call per section, differentiable upstream).
 
-    Backward, per section from the last to the first (g_K = dL/dy, u_0 = x, u_i = H_i u_{i-1} saved by the forward):
-        v_i     = (1 / A_i)^T g_i                    the all-pole part run backwards in time (same native kernel on the
-                                                     time-reversed gradient)
-        dB_i[d] =  sum_n v_i[n] u_{i-1}[n - d]       d = 0, 1, 2
-        dA_i[d] = -sum_n v_i[n] u_i[n - d]           d = 0, 1, 2   (dy/da_d = -(z^-d / A) y)
-        g_{i-1} = B_i^T v_i                          g_{i-1}[n] = sum_d b_d v_i[n + d]
-    and dL/dx = g_0.  Channel broadcasts (1 <-> C) reduce the corresponding gradient over the channel axis."""
+    Forward: the one launch inference makes (the same bits); only x, Bs and As are kept.  Backward: one
+    ops.biquad_cascade_bwd call (gfx_biquad_cascade_bwd_f32), which rebuilds every section's state from x and runs the
+    adjoint recursion -- BiquadCascadeStateFn's formulas from silence and without a state cotangent.  Channel broadcasts
+    (1 <-> C) are summed inside the kernel."""
 
     @staticmethod
     def forward(ctx, x, Bs, As):
-        K = Bs.shape[2]
-        us = [x.contiguous()]
-        for i in range(K):
-            us.append(ops.biquad_cascade(us[-1], Bs[:, :, i : i + 1].contiguous(), As[:, :, i : i + 1].contiguous()))
-        ctx.save_for_backward(Bs, As, *us)
-        return us[-1]
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        ctx.save_for_backward(x, Bs, As)
+        return ops.biquad_cascade(x, Bs, As)
 
     @staticmethod
     def backward(ctx, gy):
-        Bs, As, *us = ctx.saved_tensors
-        R, Cf, K, _ = Bs.shape
-        L = gy.shape[-1]
-        g = gy.contiguous()
-        Cout = g.shape[1]
-        gB, gA = torch.zeros_like(Bs), torch.zeros_like(As)
-        unit = torch.zeros((R, Cf, 1, 3), dtype=Bs.dtype, device=Bs.device)
-        unit[..., 0] = 1.0
-
-        def to_filter_channels(t):     # (R, Cout) -> (R, Cf)
-            return t.sum(1, keepdim=True) if (Cf == 1 and Cout > 1) else t
-
-        for i in reversed(range(K)):
-            Ai = As[:, :, i : i + 1].contiguous()
-            v = ops.biquad_cascade(g.flip(-1).contiguous(), unit, Ai).flip(-1)   # (R, Cout, L)
-            u_in, u_out = us[i], us[i + 1]
-            for d in range(3):
-                vd = v[..., d:]
-                gB[:, :, i, d] = to_filter_channels((vd * u_in[..., : L - d]).sum(-1).expand(R, Cout))
-                gA[:, :, i, d] = -to_filter_channels((vd * u_out[..., : L - d]).sum(-1))
-            b = Bs[:, :, i]                                                        # (R, Cf, 3), broadcasts over channels
-            gp = b[..., 0:1] * v
-            gp[..., :-1] += b[..., 1:2] * v[..., 1:]
-            gp[..., :-2] += b[..., 2:3] * v[..., 2:]
-            g = gp
-        x = us[0]
-        gx = g.sum(1, keepdim=True) if x.shape[1] == 1 and Cout > 1 else g
-        return (gx if ctx.needs_input_grad[0] else None, gB if ctx.needs_input_grad[1] else None,
-                gA if ctx.needs_input_grad[2] else None)
+        x, Bs, As = ctx.saved_tensors
+        want = tuple(n for n, need in zip(("x", "Bs", "As"), ctx.needs_input_grad) if need)
+        gx, gB, gA, _ = ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, want=want)
+        return gx, gB, gA
 
 
 class BiquadCascadeStateFn(torch.autograd.Function):
@@ -856,67 +825,29 @@ class BiquadCascadeStateFn(torch.autograd.Function):
     per section (w[-1], w[-2]) in and (w[L-1], w[L-2]) out of the a0-normalised direct form II
         w[n] = u[n] - a1 w[n-1] - a2 w[n-2],    y[n] = b0 w[n] + b1 w[n-1] + b2 w[n-2],    b = B / a0, a = A / a0.
 
-    Backward, per section from the last to the first, given g = dL/dy and (q1, q2) = dL/dzf of that section.  With a state
-    coming in, y is no longer (B / A) u, so BiquadCascadeFn's y-based formula for dA does not hold: everything is derived
-    from w, which the native kernel recomputes from the saved section input (unit numerator, the section's zi):
+    Backward (one ops.biquad_cascade_bwd call), per section from the last to the first, given g = dL/dy and (q1, q2) =
+    dL/dzf of that section.  With a state coming in, y is no longer (B / A) u, so everything is derived from w, which the
+    kernel rebuilds from x and the entering state of every 512-sample tile:
         r[m]   = sum_d b_d g[m + d]  (+ q1 at m = L-1, + q2 at m = L-2)        m = -2 .. L-1: what reads w[m] directly
         lam[m] = r[m] - a1 lam[m+1] - a2 lam[m+2]                               m = L-1 .. 0: the same all-pole recursion run
-                                                                                backwards in time, from silence (native kernel)
+                                                                                backwards in time, from silence
         dzi    = (r[-1] - a1 lam[0] - a2 lam[1],  r[-2] - a2 lam[0])            its two values past sample 0 (w[-2] feeds w[0] only)
         db_d   =  sum_n g[n] w[n-d]  (d = 0, 1, 2),    da_d = -sum_n lam[n] w[n-d]  (d = 1, 2)
         dB_d   = db_d / a0,   dA_d = da_d / a0 (d = 1, 2),   dA_0 = -(sum_d b_d db_d + sum_d a_d da_d) / a0
-    and lam is dL/du, the g of the section before.  Channel broadcasts (1 <-> C) reduce as in BiquadCascadeFn."""
+    and lam is dL/du, the g of the section before.  Channel broadcasts (1 <-> C) are summed inside the kernel."""
 
     @staticmethod
     def forward(ctx, x, Bs, As, zi):
-        K = Bs.shape[2]
-        us, zfs = [x.contiguous()], []
-        for i in range(K):
-            u, z = ops.biquad_cascade(us[-1], Bs[:, :, i : i + 1].contiguous(), As[:, :, i : i + 1].contiguous(),
-                                      zi=zi[:, :, i : i + 1].contiguous(), return_state=True)
-            us.append(u)
-            zfs.append(z)
-        ctx.save_for_backward(Bs, As, zi, *us[:-1])
-        return us[-1], torch.cat(zfs, 2)
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        zi = zi.contiguous()
+        ctx.save_for_backward(x, Bs, As, zi)
+        return ops.biquad_cascade(x, Bs, As, zi=zi, return_state=True)
 
     @staticmethod
     def backward(ctx, gy, gzf):
-        Bs, As, zi, *us = ctx.saved_tensors
-        R, Cf, K, _ = Bs.shape
-        Cout, L = zi.shape[1], us[0].shape[-1]
-        g = (torch.zeros((R, Cout, L), dtype=Bs.dtype, device=Bs.device) if gy is None else gy).contiguous()
-        gzf = torch.zeros_like(zi) if gzf is None else gzf
-        gB, gA, gzi = torch.zeros_like(Bs), torch.zeros_like(As), torch.zeros_like(zi)
-        unit = torch.zeros((R, Cf, 1, 3), dtype=Bs.dtype, device=Bs.device)
-        unit[..., 0] = 1.0
-
-        def to_filter_channels(t):     # (R, Cout) -> (R, Cf)
-            return t.sum(1, keepdim=True) if (Cf == 1 and Cout > 1) else t
-
-        for i in reversed(range(K)):
-            a0 = As[:, :, i, 0:1]                                   # (R, Cf, 1): broadcasts over channels and time
-            b, a = Bs[:, :, i] / a0, As[:, :, i] / a0               # (R, Cf, 3), a[..., 0] = 1
-            An = a.unsqueeze(2).contiguous()
-            zi_i = zi[:, :, i : i + 1].contiguous()
-            w = ops.biquad_cascade(us[i], unit, An, zi=zi_i, return_state=True)[0]
-            w_ext = torch.cat([zi_i[:, :, 0, 1:2], zi_i[:, :, 0, 0:1], w], -1)      # w[-2], w[-1], w[0] .. w[L-1]
-            r = torch.zeros((R, Cout, L + 2), dtype=g.dtype, device=g.device)          # r[m] at index m + 2
-            r[..., 2:] += b[..., 0:1] * g
-            r[..., 1 : L + 1] += b[..., 1:2] * g
-            r[..., :L] += b[..., 2:3] * g
-            r[..., L + 1] += gzf[:, :, i, 0]
-            r[..., L] += gzf[:, :, i, 1]
-            lam = ops.biquad_cascade(r[..., 2:].flip(-1).contiguous(), unit, An).flip(-1)
-            lam1 = lam[..., 1] if L > 1 else torch.zeros_like(lam[..., 0])
-            gzi[:, :, i, 0] = r[..., 1] - a[..., 1] * lam[..., 0] - a[..., 2] * lam1
-            gzi[:, :, i, 1] = r[..., 0] - a[..., 2] * lam[..., 0]
-            db = torch.stack([to_filter_channels((g * w_ext[..., 2 - d : L + 2 - d]).sum(-1)) for d in range(3)], -1)
-            da = torch.stack([-to_filter_channels((lam * w_ext[..., 2 - d : L + 2 - d]).sum(-1)) for d in (1, 2)], -1)
-            gB[:, :, i] = db / a0
-            gA[:, :, i, 1:] = da / a0
-            gA[:, :, i, 0] = -((b * db).sum(-1) + (a[..., 1:] * da).sum(-1)) / a0[..., 0]
-            g = lam
-        x = us[0]
-        gx = g.sum(1, keepdim=True) if x.shape[1] == 1 and Cout > 1 else g
-        need = ctx.needs_input_grad
-        return (gx if need[0] else None, gB if need[1] else None, gA if need[2] else None, gzi if need[3] else None)
+        x, Bs, As, zi = ctx.saved_tensors
+        if gy is None:
+            gy = torch.zeros((*zi.shape[:2], x.shape[-1]), dtype=x.dtype, device=x.device)
+        want = tuple(n for n, need in zip(ops.BIQUAD_GRADS, ctx.needs_input_grad) if need)
+        return ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, zi=zi, gzf=None if gzf is None else gzf.contiguous(),
+                                      want=want)

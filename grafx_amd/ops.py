@@ -1043,6 +1043,83 @@ def biquad_cascade(x, Bs, As, ssm_quirk=False, out=None, zi=None, return_state=F
     return out, zf
 
 
+BIQUAD_GRADS = ("x", "Bs", "As", "zi")
+
+
+def biquad_cascade_bwd_ws_bytes(R, C_out, K, L):
+    """Bytes of workspace one gfx_biquad_cascade_bwd_f32 call needs (no GPU involved): every section's entering state per
+    pair of row-channels and 512-sample tile."""
+    return lib().gfx_biquad_cascade_bwd_ws_bytes(R, C_out, K, L)
+
+
+@_on_device
+def biquad_cascade_bwd(x, gy, Bs, As, zi=None, gzf=None, want=BIQUAD_GRADS, out=None, ws=None):
+    """Backward of :func:`biquad_cascade` (``ssm_quirk=False``) in one call (gfx_biquad_cascade_bwd_f32) -> (gx, gB, gA, gzi),
+    None for what ``want`` (any of BIQUAD_GRADS) leaves out.  Nothing of the forward is needed but its arguments.
+
+    ``x``, ``gy``: the forward's input (R,C,L) and dL/dy (R,Cout,L), or strided (B,n,.,L) views; ``zi``: the state the
+    forward started from (None: silence); ``gzf``: dL/dzf (R,Cout,K,2) of a stateful forward (None: zero).  ``gx`` is
+    ``out`` (any view of x's shape) or a new (R,C,L) tensor, gB / gA (R,Cf,K,3), gzi (R,Cout,K,2).  ``ws``: a uint8
+    workspace of at least ``biquad_cascade_bwd_ws_bytes(R, Cout, K, L)`` bytes to reuse.  What the call writes (``out``,
+    ``ws``) may share memory with nothing it reads.  Channel broadcasts (1 <-> C) are summed inside the kernel for
+    C <= 2; with more channels the broadcast side is passed expanded and the channels of the result are added by torch
+    (a (R,C,L) temporary for gx when C_in = 1)."""
+    what = "biquad_cascade_bwd"
+    _require_gpu(x, gy, Bs, As, zi, gzf, out)
+    xmap, R, Cin, L = rowmap(x)
+    Rb, Cf, K, three = Bs.shape
+    if Rb != R or three != 3 or As.shape != Bs.shape:
+        raise ValueError(f"{what}: coefficients {tuple(Bs.shape)} / {tuple(As.shape)} do not match {R} rows")
+    Cout = max(Cin, Cf)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, Cout, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match rows={R}, channels={Cout}, length={L}")
+    unknown = set(want) - set(BIQUAD_GRADS)
+    if unknown or not want:
+        raise ValueError(f"{what}: want {tuple(want)} must name some of {BIQUAD_GRADS}")
+    zi = _state(zi, (R, Cout, K, 2), what, "zi")
+    gzf = _state(gzf, (R, Cout, K, 2), what, "gzf")
+    reads = (x, gy, Bs, As, zi, gzf)
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, Cin, L), x.device, what, apart=(*reads, ws))
+        if "x" in want:
+            gx, gxmap = dest
+    nbytes = lib().gfx_biquad_cascade_bwd_ws_bytes(R, Cout, K, L)
+    if ws is not None:
+        _apart(what, "ws", ws, reads)
+        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
+            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
+    # More than two channels with a broadcast side: the kernel sums a broadcast inside a pair of row-channels, which is a
+    # row's channels only when there are two.  The broadcast side goes in expanded instead -- the coefficients copied
+    # (parameter-sized), x through a row map with a zero channel stride -- and the channels of the result are added here.
+    wide_f = Cout > 2 and Cf == 1 and ("Bs" in want or "As" in want)
+    wide_x = Cout > 2 and Cin == 1 and gx is not None
+    kx, kxmap, kgx, kgxmap, kCin, kCf = x, xmap, gx, gxmap, Cin, Cf
+    if wide_f:
+        Bs, As, kCf = Bs.expand(R, Cout, K, 3), As.expand(R, Cout, K, 3), Cout
+    if wide_x:
+        kx = x.expand(*x.shape[:-2], Cout, L)
+        kgx = torch.empty((R, Cout, L), dtype=torch.float32, device=x.device)
+        kxmap, kgxmap, kCin = rowmap(kx)[0], rowmap(kgx)[0], Cout
+    Bs, As = Bs.contiguous(), As.contiguous()
+    gB = torch.empty_like(Bs) if "Bs" in want else None
+    gA = torch.empty_like(As) if "As" in want else None
+    gzi = torch.empty((R, Cout, K, 2), dtype=torch.float32, device=x.device) if "zi" in want else None
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    # x twice (both passes), g once, gx once
+    with _timed("biquad_cascade_bwd_kernel", 4 * R * L * (2 * Cin + Cout + (kCin if gx is not None else 0))):
+        check(lib().gfx_biquad_cascade_bwd_f32(_ptr(kx), kxmap, _ptr(gy), gmap, _ptr(kgx), kgxmap, _ptr(Bs), _ptr(As), _ptr(zi),
+                                               _ptr(gzf), _ptr(gB), _ptr(gA), _ptr(gzi), *wsarg, R, kCin, kCf, K, L, _stream()),
+              "gfx_biquad_cascade_bwd_f32")
+    if wide_f:
+        gB, gA = (None if t is None else t.sum(1, keepdim=True) for t in (gB, gA))
+    if wide_x:
+        gx.copy_(kgx.view(*gx.shape[:-2], Cout, L).sum(-2, keepdim=True))
+    return gx, gB, gA, gzi
+
+
 @_on_device
 def noise_shaping_ir(noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, ir_len, min_decay, max_decay):
     """noise (C,K,>=ir_len) view with unit last stride; parameters (R,C,K) -> ir (R,C,ir_len), un-normalised."""

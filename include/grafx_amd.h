@@ -584,6 +584,30 @@ int gfx_biquad_cascade_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowm
 int gfx_biquad_cascade_state_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* Bs,
                                  const float* As, const float* zi, float* zf, int64_t R, int64_t C_in, int64_t C_f,
                                  int64_t K, int64_t L, int ssm_quirk, void* stream);
+/* Backward of the cascade (ssm_quirk = 0) without anything of the signal's size kept from the forward: everything is
+ * rebuilt from x.  g = dL/dy (R, C_out, L) through gmap, gzf = dL/dzf (R, C_out, K, 2) or NULL (zero); zi as the forward
+ * call had it (NULL: silence).  Outputs, each NULL when not wanted (not all of them): gx = dL/dx (R, C_in, L) through
+ * gxmap, gB / gA = dL/dBs, dL/dAs (R, C_f, K, 3), gzi = dL/dzi (R, C_out, K, 2).  With C_out <= 2 channel broadcasts are
+ * summed inside the call (a pair of row-channels is then a row's two channels).  With C_out > 2 a broadcast side cannot
+ * be reduced here: gB / gA with C_f == 1, or gx with C_in == 1, return GFX_EINVAL -- pass the broadcast side expanded
+ * to C_out channels (x through a row map with stride_ch = 0) and add the channels of the result, as grafx_amd/ops.py
+ * does.  Every element of a given output is written.  With lam_i the adjoint state of section i
+ * (lam[m] = r[m] - a1 lam[m+1] - a2 lam[m+2], r[m] = sum_d b_d g_i[m+d] + the zf cotangent at m = L-1, L-2) and w_i the
+ * section's direct-form-II state:  g_{i-1} = lam_i, gx = lam_1,
+ *   db_d = sum_n g_i[n] w_i[n-d],  da_d = -sum_n lam_i[n] w_i[n-d],  gB_d = db_d / a0,  gA_{1,2} = da / a0,
+ *   gA_0 = -(b . db + a . da) / a0,  gzi = (r[-1] - a1 lam[0] - a2 lam[1], r[-2] - a2 lam[0]).
+ * Two passes, one wave per pair of row-channels: a forward walk over x that stores every section's entering state per
+ * 512-sample tile in `ws`, then a walk from the last tile to the first that rebuilds the sections' w from those and runs
+ * the adjoint recursion.  No atomics; sums are taken per tile in fp32 in a fixed order and across tiles in double, so
+ * results are bit-identical from run to run and a row's gradients do not depend on the other rows of the call.
+ * gfx_biquad_cascade_bwd_ws_bytes = ceil(R * C_out / 2) * ceil(L / 512) * K * 16 bytes (0 for a zero or negative
+ * argument); ws must be 16-byte aligned.  A workspace that is too small or bad geometry returns GFX_EINVAL before any
+ * launch.  Nothing is allocated or synchronised.  K <= 32. */
+size_t gfx_biquad_cascade_bwd_ws_bytes(int64_t R, int64_t C_out, int64_t K, int64_t L);
+int gfx_biquad_cascade_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* g, gfx_rowmap_t gmap, float* gx,
+                               gfx_rowmap_t gxmap, const float* Bs, const float* As, const float* zi, const float* gzf,
+                               float* gB, float* gA, float* gzi, void* ws, size_t ws_bytes, int64_t R, int64_t C_in,
+                               int64_t C_f, int64_t K, int64_t L, void* stream);
 
 /* ---- noise-shaping reverb impulse response ------------------------------------------------
  * replaces the envelope synthesis of FilteredNoiseShapingReverb.forward (reverb.py:343-366):
