@@ -128,6 +128,11 @@ SIGNATURES = {
     "gfx_stft_reverb_ir_bwd_ws_bytes": (sz, [i64, i64]),
     "gfx_stft_reverb_ir_bwd_f32": (ctypes.c_int, [f32p, f32p, f32p, f32p, i64, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p,
                                                   i64, i64, i64, i64, i64, ctypes.c_int, vp, sz, vp]),
+    "gfx_stft_loss_ws_bytes": (sz, [i64, i64, i64, i64]),
+    "gfx_stft_loss_sums_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, i64, i64, i64, i64, ctypes.c_float, vp, sz,
+                                              vp]),
+    "gfx_stft_loss_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, f32p, RowMap, i64, i64, i64, i64,
+                                             ctypes.c_float, ctypes.c_int, vp, sz, vp]),
 }
 
 _lib = None

@@ -851,3 +851,28 @@ class BiquadCascadeStateFn(torch.autograd.Function):
         want = tuple(n for n, need in zip(ops.BIQUAD_GRADS, ctx.needs_input_grad) if need)
         return ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, zi=zi, gzf=None if gzf is None else gzf.contiguous(),
                                       want=want)
+
+
+class StftLossSumsFn(torch.autograd.Function):
+    """sums[r, i] = (A, B, E, D) of resolution i = (windows[i], hops[i]) for every row of ``pred`` (..., L) against
+    ``target`` (ops.stft_loss_sums, one call per resolution) -> (R, n_res, 4).  The tape holds pred, target and the windows
+    -- nothing of a spectrogram's size.  Backward: one ops.stft_loss_bwd call per resolution with the cotangents of
+    (A, E, D) as coefficients, all into one gradient tensor (``accumulate`` after the first), which is the registered
+    grad_sink when ``pred`` is one.  B depends on the target alone, and the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, eps, hops, *windows):
+        if ctx.needs_input_grad[1]:
+            raise ValueError("StftLossSumsFn: the target gets no gradient (detach it)")
+        ctx.save_for_backward(pred, target, *windows)
+        ctx.eps, ctx.hops = eps, tuple(hops)
+        return torch.stack([ops.stft_loss_sums(pred, target, w, hop, eps) for w, hop in zip(windows, hops)], 1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pred, target, *windows = ctx.saved_tensors
+        gp = _sink_for(pred)
+        for i, (w, hop) in enumerate(zip(windows, ctx.hops)):
+            gp = ops.stft_loss_bwd(pred, target, w, hop, g[:, i, (0, 2, 3)].contiguous(), ctx.eps, out=gp, accumulate=i > 0)
+        return (gp, None, None, None, *(None for _ in windows))

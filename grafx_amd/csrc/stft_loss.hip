@@ -1,0 +1,556 @@
+// Multi-resolution STFT magnitude loss, one resolution per call: the four sums of a row
+//     A = sum (|T| - |P|)^2,  B = sum |T|^2,  E = sum ||T| - |P||,  D = sum |log|T| - log|P||
+// over the bins and frames of  P = stft(pred), T = stft(target)  (torch.stft: centred, reflect padding, one-sided), and
+// the gradient of a linear combination of A, E, D with respect to pred.  Nothing of a spectrogram's size is ever written:
+// the forward reads pred and target once and leaves 16 bytes per workgroup, the backward recomputes the frames and writes
+// every gradient sample once.
+//
+// Frame transform.  A 256-thread workgroup holds SLOTS = 2048 complex points in LDS: 2048 / n_fft frames side by side
+// (16 at n_fft = 128, one at 2048), so a thread owns 8 points whatever the size and takes three radix-2 stages per trip
+// through LDS in registers: 4 passes at n_fft = 2048 instead of 11.  The kernels are compiled per n_fft (five sizes), so
+// every index of a pass is a constant.  One complex transform carries the windowed pred frame in its real part and the
+// target frame in its imaginary part; P and T are split by Z[k] +- conj(Z[n - k]).  Forward: decimation in frequency,
+// natural order in, bit-reversed out.  The per-bin work runs on the bit-reversed positions (a thread owns the pair k,
+// n - k), and the backward's inverse is decimation in time, bit-reversed in, natural out: no reordering pass.  Twiddles
+// e^{-2 pi i j / n}, j < n / 2, are built once per workgroup from sincospi in double.  The samples are staged in LDS
+// first (reflection applied there), in a ring over the positions: a workgroup takes consecutive batches, so each sample
+// is read from memory once per workgroup, and in the forward the samples the next batch adds are in flight while this
+// one is transformed.
+//
+// LDS per workgroup: 16.5 KB transform buffer (padded) + n_fft * 4 + 2 KB (twiddles, and again per stage for the fine
+// stages) + n_fft * 4 (window) + 16 KB (the rings of pred and target, 2048 samples each) + 64 = 50.6 KB at n_fft = 2048,
+// 35.6 KB at 128: three or four workgroups per CU.
+//
+// A batch whose staged pred and target samples are the same floats has |T| - |P| = 0 identically; the split above would
+// return it as rounding noise, so such a batch contributes B only (forward) and no gradient (backward).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/grafx_amd.h"
+
+namespace gfx {
+namespace stftloss {
+
+constexpr int THREADS = 256;
+constexpr int SLOTS = 2048;                 // complex points of the transform buffer
+constexpr int RUN = 8;                      // batches of SLOTS / n_fft frames per forward workgroup
+constexpr int SEG = 4096;                   // gradient samples one backward workgroup owns,
+constexpr int CELLS = SEG / THREADS;        // this many per thread, in registers
+
+__device__ __forceinline__ int64_t lo(int64_t a, int64_t b) { return a < b ? a : b; }
+__device__ __forceinline__ int64_t hi(int64_t a, int64_t b) { return a > b ? a : b; }
+
+__device__ __forceinline__ int64_t row_off(const gfx_rowmap_t& m, int64_t r) {
+    return (r / m.inner) * m.stride_outer + (r % m.inner) * m.stride_inner;
+}
+
+// Where point i of the transform buffer lives: one float2 of padding after every 32, so that the eight consecutive points a
+// thread owns in the pass over the lowest bits (64 bytes apart from lane to lane) spread over all banks.
+__device__ __forceinline__ constexpr int pad(int i) { return i + (i >> 5); }
+constexpr int ZSIZE = SLOTS + SLOTS / 32;
+
+constexpr int RING = 2048;                   // staged samples per signal: a batch spans (NB - 1) * hop + N <= RING positions
+
+struct Geometry {                            // what is not fixed by n_fft
+    int hop;
+    int64_t L, frames;
+};
+
+template <int LOGN>
+struct Size {
+    static constexpr int N = 1 << LOGN, HALF = N / 2, NB = SLOTS / N;     // NB frames per batch
+};
+
+// Stages whose pairs are less than 2^FINE apart read their twiddles from per-stage tables (stage b: 2^b entries at offset
+// 2^b - 1, 2^FINE - 1 in all): in the one table of n / 2 they are 2^(logn - 1 - b) entries apart and the lanes of a wave
+// would meet on one bank, up to 32 of them.
+constexpr int FINE = 8;
+
+struct Image {                               // the carve of the dynamic LDS region
+    float2* z;
+    float2* tw;
+    float2* fine;
+    float* win;
+    float* sp;
+    float* st;
+    float* red;
+};
+
+template <int LOGN>
+__device__ __forceinline__ Image carve(char* base) {
+    Image im;
+    im.z = reinterpret_cast<float2*>(base);
+    im.tw = im.z + ZSIZE;
+    im.fine = im.tw + Size<LOGN>::HALF;
+    im.win = reinterpret_cast<float*>(im.fine + (1 << FINE));
+    im.sp = im.win + Size<LOGN>::N;
+    im.st = im.sp + RING;
+    im.red = im.st + RING;
+    return im;
+}
+
+template <int LOGN>
+__device__ __forceinline__ void build_tables(const Image& im, const float* __restrict__ window) {
+    constexpr int N = Size<LOGN>::N;
+    for (int j = threadIdx.x; j < N / 2; j += THREADS) {
+        double s, c;
+        sincospi(2.0 * (double)j / (double)N, &s, &c);
+        im.tw[j] = make_float2((float)c, (float)-s);
+    }
+    for (int i = threadIdx.x; i < (1 << FINE) - 1; i += THREADS) {
+        const int b = 31 - __clz(i + 1), j = i + 1 - (1 << b);            // e^{-2 pi i j / 2^(b + 1)}
+        double s, c;
+        sincospi((double)j / (double)(1 << b), &s, &c);
+        im.fine[i] = make_float2((float)c, (float)-s);
+    }
+    for (int j = threadIdx.x; j < N; j += THREADS) im.win[j] = window[j];
+}
+
+// The staged samples are a ring over the padded positions (position q in slot q mod RING; sample u = q - n / 2, reflected
+// at both ends): consecutive batches of a workgroup overlap, so only the positions a batch adds are read from memory --
+// fetched into registers once the batch before has left the ring, and committed to it before that batch's successor is
+// filled (the forward holds them through the transform, the backward commits them before it).
+struct Fetch {
+    float p[RING / THREADS], t[RING / THREADS];
+};
+
+template <int LOGN>
+__device__ __forceinline__ void fetch(Fetch& r, const float* __restrict__ p, const float* __restrict__ t, int64_t q, int count,
+                                      int64_t L) {
+    constexpr int HALF = Size<LOGN>::HALF;
+#pragma unroll
+    for (int i = 0; i < RING / THREADS; ++i) {
+        const int o = threadIdx.x + i * THREADS;
+        int64_t u = q + o - HALF;
+        float a = 0.0f, b = 0.0f;
+        if (o < count && u < L + HALF) {                     // (beyond the padding: frames that do not exist)
+            if (u < 0) u = -u;
+            if (u >= L) u = 2 * (L - 1) - u;
+            a = p[u];
+            b = t[u];
+        }
+        r.p[i] = a;
+        r.t[i] = b;
+    }
+}
+
+__device__ __forceinline__ void commit(const Image& im, const Fetch& r, int64_t q, int count) {
+    const int q0 = (int)(q & (RING - 1));
+#pragma unroll
+    for (int i = 0; i < RING / THREADS; ++i) {
+        const int o = threadIdx.x + i * THREADS;
+        if (o < count) {
+            im.sp[(q0 + o) & (RING - 1)] = r.p[i];
+            im.st[(q0 + o) & (RING - 1)] = r.t[i];
+        }
+    }
+}
+
+// Fill the transform buffer with the windowed frames of the batch that starts at frame mb; frames past the last one are
+// zero.  Returns whether any pred sample this thread read differs from its target sample.  No barrier.
+template <int LOGN>
+__device__ __forceinline__ int fill(const Image& im, int64_t mb, const Geometry& g) {
+    constexpr int N = Size<LOGN>::N;
+    const int q0 = (int)((mb * g.hop) & (RING - 1));
+    const int valid = (int)lo(Size<LOGN>::NB, g.frames - mb);
+    int differ = 0;
+#pragma unroll
+    for (int q = 0; q < SLOTS / THREADS; ++q) {
+        const int idx = threadIdx.x + q * THREADS;
+        const int f = idx >> LOGN, j = idx & (N - 1);
+        float2 v = make_float2(0.0f, 0.0f);
+        if (f < valid) {
+            const int slot = (q0 + f * g.hop + j) & (RING - 1);
+            const float a = im.sp[slot], b = im.st[slot], w = im.win[j];
+            differ |= !(a == b);
+            v = make_float2(w * a, w * b);
+        }
+        im.z[pad(idx)] = v;
+    }
+    return differ;
+}
+
+// One pass over the buffer: thread t owns the 8 points whose index differs in bits [LO, LO + 3) and runs the radix-2
+// butterflies of index bits LO + FIRST .. LO + LAST in registers (decimation in frequency takes the bits downwards and
+// multiplies after the difference; the inverse, decimation in time, takes them upwards with conjugate twiddles before
+// the sum).  The frames of the buffer lie above bit LOGN and are never paired.  No barrier.
+template <bool INVERSE, int LOGN, int LO, int FIRST, int LAST>
+__device__ __forceinline__ void pass8(float2* z, const float2* tw, const float2* fine) {
+    const int tlow = threadIdx.x & ((1 << LO) - 1);
+    const int base = ((threadIdx.x >> LO) << (LO + 3)) | tlow;
+    float2 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = z[pad(base | (e << LO))];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int bit = INVERSE ? s : 2 - s;
+        if (bit < FIRST || bit > LAST) continue;
+        const int b = LO + bit;                              // the index bit of this stage: pairs 2^b apart
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (e & (1 << bit)) continue;
+            const int jl = e & ((1 << bit) - 1);             // (with LO = 0 the twiddle index is this constant)
+            float2 w;
+            if (b == 0) w = make_float2(1.0f, 0.0f);
+            else if (b == 1 && LO == 0) w = jl ? make_float2(0.0f, -1.0f) : make_float2(1.0f, 0.0f);
+            else if (b < FINE && b < LOGN - 1) w = fine[(1 << b) - 1 + ((jl << LO) | tlow)];
+            else w = tw[((jl << LO) | tlow) << (LOGN - 1 - b)];
+            const float2 a = v[e], c = v[e | (1 << bit)];
+            if (INVERSE) {
+                const float cx = c.x * w.x + c.y * w.y, cy = c.y * w.x - c.x * w.y;      // c * conj(w)
+                v[e] = make_float2(a.x + cx, a.y + cy);
+                v[e | (1 << bit)] = make_float2(a.x - cx, a.y - cy);
+            } else {
+                const float dx = a.x - c.x, dy = a.y - c.y;
+                v[e] = make_float2(a.x + c.x, a.y + c.y);
+                v[e | (1 << bit)] = make_float2(dx * w.x - dy * w.y, dx * w.y + dy * w.x);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[pad(base | (e << LO))] = v[e];
+}
+
+// natural order in, bit-reversed order out, every frame of the buffer at once; ends with a barrier
+template <int LOGN, int TOP = LOGN - 1>
+__device__ __forceinline__ void fft_dif(float2* z, const float2* tw, const float2* fine) {
+    if constexpr (TOP >= 0) {
+        constexpr int LO = TOP >= 2 ? TOP - 2 : 0;
+        pass8<false, LOGN, LO, 0, TOP - LO>(z, tw, fine);
+        __syncthreads();
+        fft_dif<LOGN, LO - 1>(z, tw, fine);
+    }
+}
+
+// the unnormalised inverse (e^{+...}): bit-reversed order in, natural order out; ends with a barrier
+template <int LOGN, int DONE = 0>
+__device__ __forceinline__ void ifft_dit(float2* z, const float2* tw, const float2* fine) {
+    if constexpr (DONE < LOGN) {
+        constexpr int LO = DONE <= LOGN - 3 ? DONE : LOGN - 3;
+        pass8<true, LOGN, LO, DONE - LO, 2>(z, tw, fine);
+        __syncthreads();
+        ifft_dit<LOGN, LO + 3>(z, tw, fine);
+    }
+}
+
+// The bins thread-slot b of the buffer owns: k = bitrev(2 c) < n / 2 of frame f at position pk = 2 c, and its mirror n - k
+// at pm.  c = 0 is k = 0 and owns k = n / 2 (position 1) too; both mirror themselves.
+struct Bins {
+    int f, k, pk, pm;
+};
+
+template <int LOGN>
+__device__ __forceinline__ Bins bins_of(int b) {
+    constexpr int N = Size<LOGN>::N;
+    Bins s;
+    s.f = b >> (LOGN - 1);
+    const int c = b & (N / 2 - 1);
+    const int base = s.f << LOGN;
+    s.k = (int)(__brev((unsigned)(2 * c)) >> (32 - LOGN));
+    s.pk = base + 2 * c;
+    s.pm = base + (int)(__brev((unsigned)((N - s.k) & (N - 1))) >> (32 - LOGN));
+    return s;
+}
+
+__device__ __forceinline__ void split(const float2 zk, const float2 zm, float2& P, float2& T) {
+    P = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    T = make_float2(0.5f * (zk.y + zm.y), 0.5f * (zm.x - zk.x));
+}
+
+struct Sums {
+    float A, B, E, D;
+};
+
+// (the hardware's square root, reciprocal and logarithm, one unit in the last place each: the sums are held to 1e-5)
+__device__ __forceinline__ void add_bin(Sums& s, float2 P, float2 T, float eps, bool same) {
+    const float t2 = fmaxf(T.x * T.x + T.y * T.y, eps);
+    s.B += t2;
+    if (same) return;
+    const float p2 = fmaxf(P.x * P.x + P.y * P.y, eps);
+    const float d = __builtin_amdgcn_sqrtf(t2) - __builtin_amdgcn_sqrtf(p2);
+    s.A += d * d;
+    s.E += fabsf(d);
+    s.D += 0.5f * fabsf(__logf(t2 * __builtin_amdgcn_rcpf(p2)));      // |log|T| - log|P||
+}
+
+// G = live * (2 cA (|P| - |T|) + cE sign(|P| - |T|) + cD sign(log|P| - log|T|) / |P|) * P / |P|
+__device__ __forceinline__ float2 bin_grad(float2 P, float2 T, float eps, float cA, float cE, float cD) {
+    const float p2 = P.x * P.x + P.y * P.y;
+    if (!(p2 > eps)) return make_float2(0.0f, 0.0f);
+    const float ip = __builtin_amdgcn_rsqf(p2);              // 1 / |P|
+    const float d = p2 * ip - __builtin_amdgcn_sqrtf(fmaxf(T.x * T.x + T.y * T.y, eps));
+    const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+    const float s = (2.0f * cA * d + sg * (cE + cD * ip)) * ip;
+    return make_float2(s * P.x, s * P.y);
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(THREADS) void stft_loss_sums_kernel(const float* __restrict__ pred, gfx_rowmap_t pmap,
+                                                                 const float* __restrict__ target, gfx_rowmap_t tmap,
+                                                                 const float* __restrict__ window,
+                                                                 float4* __restrict__ partials, Geometry g, int chunks,
+                                                                 float eps) {
+    constexpr int NB = Size<LOGN>::NB;
+    extern __shared__ __attribute__((aligned(16))) char stft_loss_lds[];
+    const Image im = carve<LOGN>(stft_loss_lds);
+    const int64_t row = blockIdx.x / (unsigned)chunks;
+    const int chunk = (int)(blockIdx.x % (unsigned)chunks);
+    const float* p = pred + row_off(pmap, row);
+    const float* t = target + row_off(tmap, row);
+    build_tables<LOGN>(im, window);
+    Sums s = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int64_t m0 = (int64_t)chunk * RUN * NB;
+    const int spanv = (NB - 1) * g.hop + Size<LOGN>::N, adv = NB * g.hop;      // positions of a batch, and from one to the next
+    Fetch next;
+    fetch<LOGN>(next, p, t, m0 * g.hop, spanv, g.L);
+    commit(im, next, m0 * g.hop, spanv);
+    for (int r = 0; r < RUN; ++r) {
+        const int64_t mb = m0 + (int64_t)r * NB;
+        if (mb >= g.frames) break;                           // (the same for every thread)
+        __syncthreads();                                     // the ring holds the batch, the buffer is free
+        int differ = fill<LOGN>(im, mb, g);
+        const bool more = r + 1 < RUN && mb + NB < g.frames;
+        if (more) fetch<LOGN>(next, p, t, mb * g.hop + spanv, adv, g.L);
+        const bool same = !__syncthreads_or(differ);
+        fft_dif<LOGN>(im.z, im.tw, im.fine);
+        const int valid = (int)lo(NB, g.frames - mb);
+#pragma unroll
+        for (int q = 0; q < SLOTS / 2 / THREADS; ++q) {
+            const Bins o = bins_of<LOGN>(threadIdx.x + q * THREADS);
+            if (o.f >= valid) continue;
+            float2 P, T;
+            split(im.z[pad(o.pk)], im.z[pad(o.pm)], P, T);
+            add_bin(s, P, T, eps, same);
+            if (o.k == 0) {
+                const float2 zh = im.z[pad(o.pk + 1)];       // bin n / 2
+                add_bin(s, make_float2(zh.x, 0.0f), make_float2(zh.y, 0.0f), eps, same);
+            }
+        }
+        if (more) commit(im, next, mb * g.hop + spanv, adv);
+    }
+    // one quadruple per workgroup: lanes, then waves, in a fixed order
+    for (int o = 32; o >= 1; o >>= 1) {
+        s.A += __shfl_down(s.A, o, 64);
+        s.B += __shfl_down(s.B, o, 64);
+        s.E += __shfl_down(s.E, o, 64);
+        s.D += __shfl_down(s.D, o, 64);
+    }
+    __syncthreads();
+    float4* red = reinterpret_cast<float4*>(im.red);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = make_float4(s.A, s.B, s.E, s.D);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float4 a = red[0];
+        for (int w = 1; w < THREADS / 64; ++w) {
+            a.x += red[w].x;
+            a.y += red[w].y;
+            a.z += red[w].z;
+            a.w += red[w].w;
+        }
+        partials[blockIdx.x] = a;
+    }
+}
+
+// a row's partials in their order, in double
+__global__ __launch_bounds__(THREADS) void stft_loss_finish_kernel(const float4* __restrict__ partials,
+                                                                   float4* __restrict__ sums, int64_t R, int chunks) {
+    const int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (row >= R) return;
+    double A = 0.0, B = 0.0, E = 0.0, D = 0.0;
+    const float4* q = partials + row * chunks;
+    for (int c = 0; c < chunks; ++c) {
+        const float4 v = q[c];
+        A += v.x;
+        B += v.y;
+        E += v.z;
+        D += v.w;
+    }
+    sums[row] = make_float4((float)A, (float)B, (float)E, (float)D);
+}
+
+// Gather form: the workgroup owns samples [s0, s0 + SEG) of one row, transforms every frame that reaches them -- directly
+// or through the reflection at either end -- and each thread adds, for its own CELLS samples, the windowed inverse of
+// every such frame at the (up to three) padded positions that fold onto the sample.
+template <int LOGN>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 8))) void stft_loss_bwd_kernel(
+    const float* __restrict__ pred, gfx_rowmap_t pmap, const float* __restrict__ target, gfx_rowmap_t tmap,
+    const float* __restrict__ window, const float* __restrict__ coef, float* __restrict__ gpred, gfx_rowmap_t gmap, Geometry g,
+    int segs, float eps, int accumulate) {
+    constexpr int N = Size<LOGN>::N, HALF = Size<LOGN>::HALF, NB = Size<LOGN>::NB;
+    extern __shared__ __attribute__((aligned(16))) char stft_loss_lds[];
+    const Image im = carve<LOGN>(stft_loss_lds);
+    const int64_t row = blockIdx.x / (unsigned)segs;
+    const int64_t s0 = (int64_t)(blockIdx.x % (unsigned)segs) * SEG;
+    const int64_t s1 = lo(s0 + SEG, g.L);          // one past the last owned sample
+    const float* p = pred + row_off(pmap, row);
+    const float* t = target + row_off(tmap, row);
+    float* out = gpred + row_off(gmap, row);
+    const float cA = coef[row * 3], cE = coef[row * 3 + 1], cD = coef[row * 3 + 2];
+    const int64_t last = g.L - 1, half = HALF, n = N, hop = g.hop;
+
+    // the hull of the frames that reach the segment (a frame inside it that reaches nothing adds nothing below)
+    auto first_frame = [&](int64_t pq) { const int64_t a = pq - n + 1; return a <= 0 ? (int64_t)0 : (a + hop - 1) / hop; };
+    int64_t mlo = first_frame(s0 + half), mhi = (s1 - 1 + half) / hop;
+    if (s0 <= half && s1 - 1 >= 1) {                         // samples 1 .. half also stand at -1 .. -half
+        mlo = 0;
+        mhi = hi(mhi, (half - hi(1, s0)) / hop);
+    }
+    const int64_t ra = hi(s0, last - half), rb = lo(s1 - 1, last - 1);
+    if (ra <= rb) {                                          // samples L-1-half .. L-2 also stand at L .. L-1+half
+        mlo = lo(mlo, first_frame(2 * last - rb + half));
+        mhi = hi(mhi, (2 * last - ra + half) / hop);
+    }
+    mhi = lo(mhi, g.frames - 1);
+
+    build_tables<LOGN>(im, window);
+    float acc[CELLS];
+#pragma unroll
+    for (int q = 0; q < CELLS; ++q) acc[q] = 0.0f;
+
+    const int spanv = (NB - 1) * g.hop + N, adv = NB * g.hop;  // positions of a batch, and from one to the next
+    Fetch next;
+    fetch<LOGN>(next, p, t, mlo * hop, spanv, g.L);
+    commit(im, next, mlo * hop, spanv);
+    for (int64_t mb = mlo; mb <= mhi; mb += NB) {
+        __syncthreads();                                     // the ring holds the batch, the buffer is free
+        int differ = fill<LOGN>(im, mb, g);
+        const bool more = mb + NB <= mhi;
+        if (more) fetch<LOGN>(next, p, t, mb * hop + spanv, adv, g.L);
+        const bool same = !__syncthreads_or(differ);
+        // (committed before the transform, unlike the forward: this kernel has no registers to hold the samples through it)
+        if (more) commit(im, next, mb * hop + spanv, adv);
+        if (same) continue;                                  // pred is target here: no gradient (the same for every thread)
+        fft_dif<LOGN>(im.z, im.tw, im.fine);
+#pragma unroll
+        for (int q = 0; q < SLOTS / 2 / THREADS; ++q) {
+            const Bins o = bins_of<LOGN>(threadIdx.x + q * THREADS);
+            float2 P, T;
+            split(im.z[pad(o.pk)], im.z[pad(o.pm)], P, T);
+            if (o.k == 0) {
+                const float2 zh = im.z[pad(o.pk + 1)];
+                im.z[pad(o.pk)] = bin_grad(P, T, eps, cA, cE, cD);
+                im.z[pad(o.pk + 1)] = bin_grad(make_float2(zh.x, 0.0f), make_float2(zh.y, 0.0f), eps, cA, cE, cD);
+            } else {
+                im.z[pad(o.pk)] = bin_grad(P, T, eps, cA, cE, cD);
+                im.z[pad(o.pm)] = make_float2(0.0f, 0.0f);   // bins above n / 2 are not part of the one-sided transform
+            }
+        }
+        __syncthreads();
+        ifft_dit<LOGN>(im.z, im.tw, im.fine);
+        const int nbv = (int)lo(NB, g.frames - mb);          // frames of the batch
+        const int64_t q0 = mb * hop - half;                  // sample index (before reflection) of the batch's first point
+#pragma unroll
+        for (int q = 0; q < CELLS; ++q) {
+            const int64_t i = s0 + threadIdx.x + q * THREADS;
+            if (i >= s1) continue;
+            float a = acc[q];
+#pragma unroll 1
+            for (int e = 0; e < 3; ++e) {                    // the sample itself, its mirror before 0, its mirror beyond L - 1
+                const int64_t u = e == 0 ? i : (e == 1 ? -i : 2 * last - i);
+                const bool on = e == 0 || (e == 1 ? i >= 1 && i <= half : i <= last - 1 && i >= last - half);
+                const int64_t d = u - q0;                    // position inside the batch's span
+                if (!on || d < 0 || d >= spanv) continue;
+#pragma unroll 1
+                for (int f = 0; f < nbv; ++f) {
+                    const int j = (int)d - f * g.hop;
+                    if ((unsigned)j < (unsigned)N) a += im.win[j] * im.z[pad((f << LOGN) + j)].x;
+                }
+            }
+            acc[q] = a;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CELLS; ++q) {
+        const int64_t i = s0 + threadIdx.x + q * THREADS;
+        if (i < s1) out[i] = accumulate ? out[i] + acc[q] : acc[q];
+    }
+}
+
+static bool geometry(Geometry& g, int& logn, int64_t L, int64_t n_fft, int64_t hop) {
+    if (n_fft < 128 || n_fft > 2048 || (n_fft & (n_fft - 1)) || hop < 1 || hop > n_fft || L <= n_fft / 2 ||
+        L > 0x7fffffffLL - 4096)
+        return false;
+    logn = __builtin_ctz((unsigned)n_fft);
+    g.hop = (int)hop;
+    g.L = L;
+    g.frames = 1 + L / hop;
+    return true;
+}
+
+static int64_t chunks_of(const Geometry& g, int64_t n_fft) {
+    const int64_t per = (int64_t)RUN * (SLOTS / n_fft);
+    return (g.frames + per - 1) / per;
+}
+
+static size_t lds_bytes(int64_t n_fft) {
+    return (size_t)ZSIZE * sizeof(float2) + (size_t)(n_fft / 2 + (1 << FINE)) * sizeof(float2) + (size_t)n_fft * sizeof(float) +
+           2 * (size_t)RING * sizeof(float) + 64;
+}
+
+// the kernel compiled for n_fft = 2^logn
+#define GFX_STFT_LOSS_BY_SIZE(logn, launch) \
+    switch (logn) {                         \
+        case 7: launch(7); break;           \
+        case 8: launch(8); break;           \
+        case 9: launch(9); break;           \
+        case 10: launch(10); break;         \
+        default: launch(11); break;         \
+    }
+
+}  // namespace stftloss
+}  // namespace gfx
+
+extern "C" {
+
+size_t gfx_stft_loss_ws_bytes(int64_t R, int64_t L, int64_t n_fft, int64_t hop) {
+    gfx::stftloss::Geometry g;
+    int logn;
+    if (R <= 0 || !gfx::stftloss::geometry(g, logn, L, n_fft, hop)) return 0;
+    return (size_t)R * (size_t)gfx::stftloss::chunks_of(g, n_fft) * 16;
+}
+
+int gfx_stft_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap, const float* window,
+                           float* sums, int64_t R, int64_t L, int64_t n_fft, int64_t hop, float eps, void* ws,
+                           size_t ws_bytes, void* stream) {
+    using namespace gfx::stftloss;
+    Geometry g;
+    int logn;
+    if (!pred || !target || !window || !sums || !ws || R <= 0 || !(eps > 0.0f) || pmap.inner <= 0 || tmap.inner <= 0 ||
+        !geometry(g, logn, L, n_fft, hop))
+        return GFX_EINVAL;
+    const int64_t chunks = chunks_of(g, n_fft);
+    if (R > 0x7fffffffLL / chunks || ((uintptr_t)ws & 15)) return GFX_EINVAL;
+    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;
+    hipStream_t s = (hipStream_t)stream;
+#define GFX_LAUNCH(LOGN)                                                                                                  \
+    hipLaunchKernelGGL(stft_loss_sums_kernel<LOGN>, dim3((unsigned)(R * chunks)), dim3(THREADS), lds_bytes(n_fft), s, pred, \
+                       pmap, target, tmap, window, (float4*)ws, g, (int)chunks, eps)
+    GFX_STFT_LOSS_BY_SIZE(logn, GFX_LAUNCH)
+#undef GFX_LAUNCH
+    hipLaunchKernelGGL(stft_loss_finish_kernel, dim3((unsigned)((R + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
+                       (const float4*)ws, (float4*)sums, R, (int)chunks);
+    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+}
+
+int gfx_stft_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap, const float* window,
+                          const float* coef, float* gpred, gfx_rowmap_t gmap, int64_t R, int64_t L, int64_t n_fft,
+                          int64_t hop, float eps, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    using namespace gfx::stftloss;
+    Geometry g;
+    int logn;
+    if (!pred || !target || !window || !coef || !gpred || !ws || R <= 0 || !(eps > 0.0f) || pmap.inner <= 0 ||
+        tmap.inner <= 0 || gmap.inner <= 0 || !geometry(g, logn, L, n_fft, hop))
+        return GFX_EINVAL;
+    const int64_t segs = (L + SEG - 1) / SEG, chunks = chunks_of(g, n_fft);
+    if (R > 0x7fffffffLL / segs || R > 0x7fffffffLL / chunks) return GFX_EINVAL;
+    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;      // one buffer serves both calls of a step
+#define GFX_LAUNCH(LOGN)                                                                                               \
+    hipLaunchKernelGGL(stft_loss_bwd_kernel<LOGN>, dim3((unsigned)(R * segs)), dim3(THREADS), lds_bytes(n_fft),          \
+                       (hipStream_t)stream, pred, pmap, target, tmap, window, coef, gpred, gmap, g, (int)segs, eps, accumulate)
+    GFX_STFT_LOSS_BY_SIZE(logn, GFX_LAUNCH)
+#undef GFX_LAUNCH
+    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+}
+
+}  // extern "C"

@@ -1431,6 +1431,109 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
     return g_init, g_delta, g_env
 
 
+# ----------------------------------------------------------------------------------------- STFT loss
+def stft_loss_ws_bytes(R, L, n_fft, hop):
+    """Bytes of workspace one gfx_stft_loss_sums_f32 / gfx_stft_loss_bwd_f32 call needs (no GPU involved): 16 per row and
+    run of 16384 / n_fft frames; 0 for a resolution outside the native range (n_fft a power of two in [128, 2048],
+    1 <= hop <= n_fft, L > n_fft / 2)."""
+    return lib().gfx_stft_loss_ws_bytes(R, L, n_fft, hop)
+
+
+def _loss_rows(t, what, name, view_only=False):
+    """A (..., L) signal of the STFT loss as a (B, C, L) view and the RowMap of its B * C single rows (row r at
+    (r / C) * stride(0) + (r % C) * stride(1)): a (B, C, L) slice of a larger buffer is addressed in place.  Leading
+    dimensions that do not fold into two strides are copied -- or refused, for a tensor the call writes (``view_only``)."""
+    if t.ndim < 2:
+        raise ValueError(f"{what}: {name} must be (..., L) with at least one leading dimension, got {tuple(t.shape)}")
+    if t.stride(-1) != 1:
+        if view_only:
+            raise ValueError(f"{what}: the last dimension of {name} must be contiguous")
+        t = t.contiguous()
+    if t.ndim == 2:
+        t3 = t.unsqueeze(1)
+    elif t.ndim == 3:
+        t3 = t
+    elif view_only:
+        try:
+            t3 = t.view(-1, *t.shape[-2:])
+        except RuntimeError:
+            raise ValueError(f"{what}: the leading dimensions of {name} {tuple(t.shape)} (strides {tuple(t.stride())}) do not "
+                             f"fold into one") from None
+    else:
+        t3 = t.reshape(-1, *t.shape[-2:])
+    return t3, RowMap(max(t3.shape[1], 1), t3.stride(0), t3.stride(1), 0)
+
+
+def _loss_args(what, pred, target, window, hop, ws):
+    _require_gpu(pred, target, window)
+    if pred.shape != target.shape:
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+    p3, pmap = _loss_rows(pred, what, "pred")
+    t3, tmap = _loss_rows(target, what, "target")
+    B, C, L = p3.shape
+    n_fft = window.numel()
+    nbytes = lib().gfx_stft_loss_ws_bytes(B * C, L, n_fft, hop)
+    if not nbytes:
+        raise ValueError(f"{what}: n_fft={n_fft} (the window's length), hop={hop}, L={L} with {B * C} rows is outside the "
+                         f"native range: n_fft a power of two in [128, 2048], 1 <= hop <= n_fft, L > n_fft / 2")
+    if ws is not None and (not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes):
+        raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
+    return p3, pmap, t3, tmap, B * C, L, n_fft, nbytes
+
+
+@_on_device
+def stft_loss_sums(pred, target, window, hop, eps=1e-8, ws=None):
+    """The four sums of one resolution of an STFT magnitude loss per row (gfx_stft_loss_sums_f32) -> (R, 4) float32:
+    A = sum (|T|-|P|)^2, B = sum |T|^2, E = sum ||T|-|P||, D = sum |log|T| - log|P|| over the bins and frames of
+    P = torch.stft(pred, n_fft, hop, window=window, center=True, pad_mode="reflect") and T likewise, magnitudes floored at
+    sqrt(eps).  ``pred`` / ``target``: (..., L) of one shape, R = the product of the leading dimensions; a (B, C, L) slice
+    of a larger buffer is read in place.  ``window``: n_fft floats, n_fft a power of two in [128, 2048].  ``ws``: a uint8
+    workspace of at least ``stft_loss_ws_bytes(R, L, n_fft, hop)`` bytes to reuse.  Nothing of a spectrogram's size is
+    allocated; equal bits from call to call."""
+    what = "stft_loss_sums"
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
+    _apart(what, "ws", ws, (p3, t3, window))
+    sums = torch.empty((R, 4), dtype=torch.float32, device=pred.device)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
+    with _timed("stft_loss_sums_kernel", 4 * R * L * 2):
+        check(lib().gfx_stft_loss_sums_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(sums), R, L, n_fft, hop, eps,
+                                           *wsarg, _stream()), "gfx_stft_loss_sums_f32")
+    return sums
+
+
+@_on_device
+def stft_loss_bwd(pred, target, window, hop, coef, eps=1e-8, out=None, accumulate=False, ws=None):
+    """Gradient with respect to ``pred`` of sum_r (cA A + cE E + cD D)[r], the sums of :func:`stft_loss_sums`, with
+    ``coef`` (R, 3) = (cA, cE, cD) per row (gfx_stft_loss_bwd_f32) -> a tensor of pred's shape.  The frames are
+    recomputed from ``pred`` and ``target``; every gradient sample is stored once.  ``out``: the destination (pred's shape;
+    any view whose leading dimensions fold into two strides), required with ``accumulate``, which adds to what it holds
+    -- the resolutions of one loss sum into one tensor.  It may share memory with nothing the call reads.  ``ws``: as for
+    :func:`stft_loss_sums`."""
+    what = "stft_loss_bwd"
+    _require_gpu(coef, out)
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
+    _expect(coef, (R, 3), what + ": coef")
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate adds to a given out")
+    reads = (p3, t3, window, coef)
+    _apart(what, "ws", ws, reads)
+    if out is not None:
+        if out.shape != pred.shape:
+            raise ValueError(f"{what}: out {tuple(out.shape)} does not match pred {tuple(pred.shape)}")
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+        _output(o3, tuple(p3.shape), pred.device, what, apart=(*reads, ws))
+    else:
+        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
+    with _timed("stft_loss_bwd_kernel", 4 * R * L * (4 if accumulate else 3)):
+        check(lib().gfx_stft_loss_bwd_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), pin(coef), _ptr(o3), gmap, R, L, n_fft,
+                                          hop, eps, int(bool(accumulate)), *wsarg, _stream()), "gfx_stft_loss_bwd_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- routing
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):

@@ -679,6 +679,40 @@ int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, g
                            float* gx, gfx_rowmap_t omap, float* g_log_pre_gain, float* g_log_post_gain, float* g_p0,
                            float* g_p1, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- multi-resolution STFT magnitude loss, one resolution per call ------------------------
+ * replaces the call site of a training step's loss: torch.stft of the prediction and of the target, their magnitudes
+ * and logs, and autograd through all of them.  For rows p = pred[r], t = target[r] of L samples,
+ *   P = torch.stft(p, n_fft, hop, window=window, center=True, pad_mode="reflect", return_complex=True)   (T likewise)
+ *   |P| = sqrt(max(P.re^2 + P.im^2, eps)),  |T| likewise
+ *   sums[r] = (A, B, E, D) = (sum (|T|-|P|)^2, sum |T|^2, sum ||T|-|P||, sum |log|T| - log|P||)
+ * over the n_fft / 2 + 1 bins of the 1 + L / hop frames; `window` holds n_fft floats.  The rows of pred, target and gpred
+ * are single signals: row r lives at base + (r / inner) * stride_outer + (r % inner) * stride_inner of its row map
+ * (stride_ch is not used), so the B * C rows of a (B, C, L) slice of a larger buffer are read in place.
+ * gfx_stft_loss_sums_f32: one pass over pred and target; every workgroup transforms a run of consecutive frames in LDS
+ * (one complex transform per frame: pred in the real part, target in the imaginary part) and leaves one partial
+ * quadruple in `ws`; a second kernel adds a row's partials in their order, in double.  No atomics: equal bits from run
+ * to run, and a row's sums do not depend on the other rows of the call.
+ * gfx_stft_loss_bwd_f32: gpred[r] (=, or += with accumulate != 0) the gradient of cA A + cE E + cD D with respect to
+ * pred[r], coef[r] = (cA, cE, cD).  Per bin, with live = P.re^2 + P.im^2 > eps,
+ *   G = live * (2 cA (|P|-|T|) + cE sign(|P|-|T|) + cD sign(log|P|-log|T|) / |P|) * P / |P|
+ * and a frame's gradient is window[j] * Re sum_{k <= n_fft/2} G_k e^{+2 pi i jk / n_fft} (every kept bin once),
+ * overlap-added, the reflect padding folded back onto the samples it mirrors.  Gather form: a workgroup owns 4096
+ * samples of a row, recomputes every frame that reaches them and stores each sample once -- no atomics, no zero-fill
+ * before the call; the target gets no gradient.  Frames whose pred and target samples are the same floats count
+ * |T|-|P| = 0 exactly in both entries.
+ * n_fft: a power of two in [128, 2048]; 1 <= hop <= n_fft; n_fft / 2 < L <= 2^31 - 4097; eps > 0; anything else, a
+ * null pointer (ws included), R <= 0 or an empty row map is GFX_EINVAL; a workspace below
+ *   gfx_stft_loss_ws_bytes = R * ceil((1 + L / hop) * n_fft / 16384) * 16 bytes   (0 for a bad argument)
+ * is GFX_ENOSPC (ws 16-byte aligned).  The backward takes the same workspace so that one buffer serves both calls of a
+ * step; it launches nothing that touches it today.  Every check comes before the first launch. */
+size_t gfx_stft_loss_ws_bytes(int64_t R, int64_t L, int64_t n_fft, int64_t hop);
+int gfx_stft_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap, const float* window,
+                           float* sums, int64_t R, int64_t L, int64_t n_fft, int64_t hop, float eps, void* ws,
+                           size_t ws_bytes, void* stream);
+int gfx_stft_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap, const float* window,
+                          const float* coef, float* gpred, gfx_rowmap_t gmap, int64_t R, int64_t L, int64_t n_fft,
+                          int64_t hop, float eps, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
