@@ -133,6 +133,10 @@ SIGNATURES = {
                                               vp]),
     "gfx_stft_loss_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, f32p, RowMap, i64, i64, i64, i64,
                                              ctypes.c_float, ctypes.c_int, vp, sz, vp]),
+    "gfx_stft_band_loss_sums_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, vp, vp, i64, f32p, i64, i64, i64, i64,
+                                                   ctypes.c_float, vp, sz, vp]),
+    "gfx_stft_band_loss_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, vp, vp, vp, vp, i64, f32p, f32p, RowMap,
+                                                  i64, i64, i64, i64, ctypes.c_float, ctypes.c_int, vp, sz, vp]),
 }
 
 _lib = None

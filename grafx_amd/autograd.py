@@ -876,3 +876,44 @@ class StftLossSumsFn(torch.autograd.Function):
         for i, (w, hop) in enumerate(zip(windows, ctx.hops)):
             gp = ops.stft_loss_bwd(pred, target, w, hop, g[:, i, (0, 2, 3)].contiguous(), ctx.eps, out=gp, accumulate=i > 0)
         return (gp, None, None, None, *(None for _ in windows))
+
+
+class StftBandLossSumsFn(torch.autograd.Function):
+    """:class:`StftLossSumsFn` for a loss some of whose resolutions are on a filterbank scale: ``banked[i]`` says whether
+    resolution i has one, and after the windows come, for every such resolution in order, its filterbank and the four band
+    arrays of losses.filterbank_bands.  A banked resolution calls ops.stft_band_loss_sums / ops.stft_band_loss_bwd, the
+    others the plain entries; one call per resolution each way, all gradients into one tensor (``accumulate`` after the
+    first), the registered grad_sink when ``pred`` is one.  The tape holds pred, target, the windows, the filterbanks and
+    their bands -- nothing of a spectrogram's size.  The filterbanks get no gradient."""
+
+    @staticmethod
+    def _calls(hops, banked, tensors):
+        """(window, hop, None or (fb, bands)) per resolution out of the flat tensor list."""
+        windows, rest = tensors[:len(hops)], list(tensors[len(hops):])
+        return [(w, hop, (rest.pop(0), tuple(rest.pop(0) for _ in range(4))) if has else None)
+                for w, hop, has in zip(windows, hops, banked)]
+
+    @staticmethod
+    def forward(ctx, pred, target, eps, hops, banked, *tensors):
+        if ctx.needs_input_grad[1]:
+            raise ValueError("StftBandLossSumsFn: the target gets no gradient (detach it)")
+        if any(ctx.needs_input_grad[5:]):
+            raise ValueError("StftBandLossSumsFn: windows and filterbanks get no gradient (detach them)")
+        ctx.save_for_backward(pred, target, *tensors)
+        ctx.eps, ctx.hops, ctx.banked = eps, tuple(hops), tuple(banked)
+        return torch.stack([ops.stft_loss_sums(pred, target, w, hop, eps) if bank is None
+                            else ops.stft_band_loss_sums(pred, target, w, hop, *bank, eps)
+                            for w, hop, bank in StftBandLossSumsFn._calls(ctx.hops, ctx.banked, tensors)], 1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pred, target, *tensors = ctx.saved_tensors
+        gp = _sink_for(pred)
+        for i, (w, hop, bank) in enumerate(StftBandLossSumsFn._calls(ctx.hops, ctx.banked, tensors)):
+            coef = g[:, i, (0, 2, 3)].contiguous()
+            if bank is None:
+                gp = ops.stft_loss_bwd(pred, target, w, hop, coef, ctx.eps, out=gp, accumulate=i > 0)
+            else:
+                gp = ops.stft_band_loss_bwd(pred, target, w, hop, *bank, coef, ctx.eps, out=gp, accumulate=i > 0)
+        return (gp, None, None, None, None, *(None for _ in tensors))

@@ -1534,6 +1534,77 @@ def stft_loss_bwd(pred, target, window, hop, coef, eps=1e-8, out=None, accumulat
     return out
 
 
+def _band_args(what, fb, bands, n_fft):
+    """The filterbank of a banded STFT loss call, checked: ``fb`` (n_bins, n_fft / 2 + 1) float32 and ``bands`` =
+    (row_lo, row_hi, col_lo, col_hi), int32 on the GPU (losses.filterbank_bands) -> (fb, the four arrays, n_bins), all
+    contiguous.  What the arrays hold is not read here (that would synchronise): it is the caller's, as the header says."""
+    _require_gpu(fb)
+    bins = n_fft // 2 + 1
+    if fb.ndim != 2 or fb.shape[1] != bins or not 1 <= fb.shape[0] <= bins:
+        raise ValueError(f"{what}: the filterbank must be (n_bins, n_fft / 2 + 1 = {bins}) with 1 <= n_bins <= {bins}, got "
+                         f"{tuple(fb.shape)}")
+    if fb.requires_grad:
+        raise ValueError(f"{what}: the filterbank gets no gradient (detach it)")
+    if len(bands) != 4:
+        raise ValueError(f"{what}: bands are (row_lo, row_hi, col_lo, col_hi), got {len(bands)} entries")
+    for name, b, n in zip(("row_lo", "row_hi", "col_lo", "col_hi"), bands, (fb.shape[0], fb.shape[0], bins, bins)):
+        if not isinstance(b, torch.Tensor) or not b.is_cuda or b.dtype != torch.int32 or tuple(b.shape) != (n,):
+            raise ValueError(f"{what}: {name} must be {n} int32 on the GPU")
+    return fb.contiguous(), tuple(b.contiguous() for b in bands), fb.shape[0]
+
+
+@_on_device
+def stft_band_loss_sums(pred, target, window, hop, fb, bands, eps=1e-8, ws=None):
+    """:func:`stft_loss_sums` on a filterbank scale (gfx_stft_band_loss_sums_f32) -> (R, 4) float32: with
+    Pm = fb @ |P| and Tm = fb @ |T| per frame (magnitudes floored at sqrt(eps) per bin),  A = sum (Tm-Pm)^2, B = sum Tm^2,
+    E = sum |Tm-Pm|, D = sum |log Tm - log Pm| over the n_bins bands of all frames.  ``fb``: (n_bins, n_fft / 2 + 1)
+    non-negative weights, staircase banded; ``bands``: what ``losses.filterbank_bands(fb)`` returned, on the GPU.  The
+    rest as for :func:`stft_loss_sums`, the workspace included."""
+    what = "stft_band_loss_sums"
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
+    fb, bands, n_bins = _band_args(what, fb, bands, n_fft)
+    _apart(what, "ws", ws, (p3, t3, window, fb, *bands))
+    sums = torch.empty((R, 4), dtype=torch.float32, device=pred.device)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
+    with _timed("stft_band_loss_sums_kernel", 4 * R * L * 2):
+        check(lib().gfx_stft_band_loss_sums_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(fb), _ptr(bands[0]),
+                                                _ptr(bands[1]), n_bins, _ptr(sums), R, L, n_fft, hop, eps, *wsarg, _stream()),
+              "gfx_stft_band_loss_sums_f32")
+    return sums
+
+
+@_on_device
+def stft_band_loss_bwd(pred, target, window, hop, fb, bands, coef, eps=1e-8, out=None, accumulate=False, ws=None):
+    """:func:`stft_loss_bwd` for the sums of :func:`stft_band_loss_sums` (gfx_stft_band_loss_bwd_f32): the gradient with
+    respect to ``pred`` of sum_r (cA A + cE E + cD D)[r] -> a tensor of pred's shape.  ``fb`` and ``bands`` as in the
+    forward (the filterbank gets no gradient), everything else as for :func:`stft_loss_bwd`."""
+    what = "stft_band_loss_bwd"
+    _require_gpu(coef, out)
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
+    fb, bands, n_bins = _band_args(what, fb, bands, n_fft)
+    _expect(coef, (R, 3), what + ": coef")
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate adds to a given out")
+    reads = (p3, t3, window, coef, fb, *bands)
+    _apart(what, "ws", ws, reads)
+    if out is not None:
+        if out.shape != pred.shape:
+            raise ValueError(f"{what}: out {tuple(out.shape)} does not match pred {tuple(pred.shape)}")
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+        _output(o3, tuple(p3.shape), pred.device, what, apart=(*reads, ws))
+    else:
+        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
+    with _timed("stft_band_loss_bwd_kernel", 4 * R * L * (4 if accumulate else 3)):
+        check(lib().gfx_stft_band_loss_bwd_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(fb), *(_ptr(b) for b in bands),
+                                               n_bins, pin(coef), _ptr(o3), gmap, R, L, n_fft, hop, eps, int(bool(accumulate)),
+                                               *wsarg, _stream()), "gfx_stft_band_loss_bwd_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- routing
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):

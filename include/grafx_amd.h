@@ -713,6 +713,37 @@ int gfx_stft_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float* tar
                           const float* coef, float* gpred, gfx_rowmap_t gmap, int64_t R, int64_t L, int64_t n_fft,
                           int64_t hop, float eps, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same loss on a filterbank scale (mel, bark, third octaves, per-bin weights, a band limit) ----
+ * fb is an (n_bins, n_fft / 2 + 1) matrix W of non-negative weights, dense and row-major.  With |P|_k, |T|_k per bin
+ * and frame as above (the clamp stays on the bins),
+ *   Pm[m] = sum_k W[m, k] |P|_k,   Tm[m] likewise,
+ *   sums[r] = (A, B, E, D) = (sum (Tm-Pm)^2, sum Tm^2, sum |Tm-Pm|, sum |log Tm - log Pm|)
+ * over the n_bins bands of the 1 + L / hop frames (the logarithm moves to the bands), and gfx_stft_band_loss_bwd_f32
+ * gives the gradient of cA A + cE E + cD D with respect to pred[r]: per band and per bin
+ *   g_m = 2 cA (Pm-Tm) + cE sign(Pm-Tm) + cD sign(log Pm - log Tm) / Pm
+ *   G_k = live_k * (sum_m W[m, k] g_m) * P_k / |P|_k,     live_k = P.re^2 + P.im^2 > eps,
+ * followed by the windowed one-sided inverse, the overlap-add and the reflection fold of gfx_stft_loss_bwd_f32.
+ * Staircase contract: the non-zeros of row m are one run [row_lo[m], row_hi[m]) of bins, not empty and of positive
+ * weight sum (so that log Pm exists), and row_lo, row_hi are non-decreasing in m.  The rows that touch bin k are then a
+ * run too, [col_lo[k], col_hi[k]) (n_fft / 2 + 1 entries each; empty for a bin no row covers, whose G_k is 0).  Only
+ * the band entries of fb are read.  The band arrays (int32, on the device) and the non-negativity of fb are the
+ * caller's to guarantee: the entries cannot read device memory before a launch.  The kernels cut every run to
+ * [0, n_fft / 2 + 1) and [0, n_bins), so wrong arrays give wrong numbers, not reads outside fb.
+ * Rows, row maps, window, workspace (gfx_stft_loss_ws_bytes, the same buffer), accumulate, the treatment of frames whose
+ * pred and target samples are the same floats, and the guarantees (no atomics, equal bits from run to run, a fixed group
+ * of lanes reduces a band whatever its width, every gradient sample stored once) are those of the plain entries.
+ * Refused with GFX_EINVAL: everything the plain entries refuse, a null fb or band array, n_bins outside
+ * 1 .. n_fft / 2 + 1; a workspace too small is GFX_ENOSPC.  Every check comes before the first launch. */
+int gfx_stft_band_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap,
+                                const float* window, const float* fb, const int32_t* row_lo, const int32_t* row_hi,
+                                int64_t n_bins, float* sums, int64_t R, int64_t L, int64_t n_fft, int64_t hop, float eps,
+                                void* ws, size_t ws_bytes, void* stream);
+int gfx_stft_band_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float* target, gfx_rowmap_t tmap,
+                               const float* window, const float* fb, const int32_t* row_lo, const int32_t* row_hi,
+                               const int32_t* col_lo, const int32_t* col_hi, int64_t n_bins, const float* coef, float* gpred,
+                               gfx_rowmap_t gmap, int64_t R, int64_t L, int64_t n_fft, int64_t hop, float eps, int accumulate,
+                               void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

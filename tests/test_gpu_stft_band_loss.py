@@ -1,0 +1,326 @@
+"""The native STFT loss on a filterbank scale on the GPU against its float64 definition (tests/stft_band_loss_float64.py): the
+sums and the gradient of the two band entries over the table of filterbanks, their tie to the plain entries through the
+identity filterbank, the module end to end, the guarantees on bits, memory and layouts, and the refusals."""
+import warnings
+
+import pytest
+import torch
+from conftest import assert_close
+
+import stft_band_loss_float64 as b64
+import stft_loss_float64 as f64
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+NAMES = "ABED"      # the order of the four sums
+
+
+def ident(shape):
+    return "{}/{}/{}".format(*shape[:3])
+
+
+def window(n_fft):
+    return f64.hann(n_fft, dtype=torch.float32).cuda()
+
+
+def bank(name, n_fft):
+    """(fb, bands) of a table filterbank on the GPU."""
+    from grafx_amd.losses import filterbank_bands
+
+    W = b64.filterbank(name, n_fft).cuda()
+    return W, filterbank_bands(W)
+
+
+def on_gpu(name, n_fft, hop, L, kind):
+    return tuple(x.cuda() for x in b64.inputs(name, n_fft, hop, L, kind))
+
+
+# ------------------------------------------------------------------------------------------------ 1: the sums
+SUMS_CASES = ([("mel", s) for s in f64.SHAPES] + [(name, s) for name in ("aweight", "one", "boxes") for s in b64.ANY_SHAPES]
+              + [("htk", b64.HTK_SHAPE)])
+
+
+@pytest.mark.parametrize("kind", f64.KINDS)
+@pytest.mark.parametrize("name,shape", SUMS_CASES, ids=[f"{n}-{ident(s)}" for n, s in SUMS_CASES])
+def test_sums_match_float64(name, shape, kind):
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = shape
+    pred, target = on_gpu(name, n_fft, hop, L, kind)
+    got = ops.stft_band_loss_sums(pred, target, window(n_fft), hop, *bank(name, n_fft), eps)
+    want, _ = b64.reference(name, n_fft, hop, L, eps, kind)
+    assert got.shape == (f64.ROWS, 4) and got.dtype == torch.float32
+    for r in range(f64.ROWS):
+        for c, what in enumerate(NAMES):
+            print(f"{name} {ident(shape)} {kind} row {r} {what}: {float(got[r, c]):.9g} vs {float(want[r, c]):.9g}")
+            assert_close(got[r, c].reshape(1), want[r, c].reshape(1), TOL, f"{what} of row {r}")
+
+
+# ------------------------------------------------------------------------------------------------ 2: the plain entries
+@pytest.mark.parametrize("shape", b64.ANY_SHAPES, ids=ident)
+def test_identity_filterbank_reproduces_the_plain_entries(shape):
+    """Ties the band kernels to the plain ones.  Not to the bit: the order of summation differs."""
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = shape
+    pred, target = on_gpu("identity", n_fft, hop, L, "half")
+    w, coef = window(n_fft), f64.coefficients("random", n_fft + hop + L).cuda()
+    fb, bands = bank("identity", n_fft)
+    got, want = ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps), ops.stft_loss_sums(pred, target, w, hop, eps)
+    print((got - want).abs().max(0).values.tolist(), want.abs().max(0).values.tolist())
+    assert ((got - want).abs() <= 1e-6 * want.abs()).all()
+    assert_close(ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps),
+                 ops.stft_loss_bwd(pred, target, w, hop, coef, eps).double(), TOL, "gradient through the identity")
+
+
+# ------------------------------------------------------------------------------------------------ 3: the gradient
+@pytest.mark.parametrize("name,shape,kind", b64.GRADIENT_CASES, ids=[f"{n}-{ident(s)}-{k}" for n, s, k in b64.GRADIENT_CASES])
+def test_gradient_matches_float64_autograd(name, shape, kind):
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = shape
+    pred, target = on_gpu(name, n_fft, hop, L, kind)
+    fb, bands = bank(name, n_fft)
+    for coefs in ("A", "E", "D", "random"):
+        coef = f64.coefficients(coefs, n_fft + hop + L).cuda()
+        got = ops.stft_band_loss_bwd(pred, target, window(n_fft), hop, fb, bands, coef, eps)
+        _, want = b64.reference(name, n_fft, hop, L, eps, kind, coefs)
+        assert got.shape == pred.shape
+        assert_close(got, want, TOL, f"gradient for coefficients {coefs}")
+
+
+# ------------------------------------------------------------------------------------------------ 4: the module
+RESOLUTIONS = ((128, 32, 128), (512, 50, 512))
+WEIGHTS = dict(w_sc=1.0, w_log_mag=0.7, w_lin_mag=0.3)
+MODULE_EPS = 0.25
+
+
+def stereo_inputs():
+    """(2, 2, 1000) cut from four rows of 128/32/1000's draw, pred = 0.5 target + 0.02 noise."""
+    target, noise = f64.draw(128, 32, 1000, rows=4)
+    return (0.5 * target + 0.02 * noise).view(2, 2, -1), target.view(2, 2, -1).clone()
+
+
+def graph_names(fn):
+    seen, todo, names = set(), [fn], []
+    while todo:
+        f = todo.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        names.append(type(f).__name__)
+        todo += [g for g, _ in f.next_functions]
+    return names
+
+
+@pytest.mark.parametrize("case", ["mel", "mixed"])
+def test_module_matches_float64_and_trains_on_the_native_node(case):
+    from grafx_amd import ops
+    from grafx_amd.losses import MultiResolutionSTFTLoss
+
+    pred, target = stereo_inputs()
+    sizes, hops = [r[0] for r in RESOLUTIONS], [r[1] for r in RESOLUTIONS]
+    if case == "mel":
+        banks = [torch.from_numpy(b64.mel_numpy(b64.SAMPLE_RATE, n, 8)).float() for n in sizes]
+        module = MultiResolutionSTFTLoss(sizes, hops, eps=MODULE_EPS, sum_and_difference=True, scale="mel", n_bins=8,
+                                         sample_rate=b64.SAMPLE_RATE, **WEIGHTS).cuda()
+    else:
+        banks = [b64.filterbank("boxes", sizes[0]), None]
+        module = MultiResolutionSTFTLoss(sizes, hops, eps=MODULE_EPS, sum_and_difference=True, filterbanks=banks, **WEIGHTS).cuda()
+    want, want_grad = b64.loss_and_grad(pred, target, RESOLUTIONS, banks, 1.0, 0.7, 0.3, MODULE_EPS, sum_and_difference=True)
+    assert not list(module.parameters()) and not module.state_dict()
+    p = pred.cuda().requires_grad_(True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", ops.FftLibraryWarning)
+        loss = module(p, target.cuda())
+    names = graph_names(loss.grad_fn)
+    assert "StftBandLossSumsFnBackward" in names
+    assert not [n for n in names if "stft" in n.lower().replace("stftbandlosssumsfn", "") or "fft" in n.lower()], names
+    loss.backward()
+    assert_close(loss.detach().reshape(1), want.reshape(1), TOL, "loss")
+    assert_close(p.grad, want_grad, TOL, "pred.grad")
+
+
+def test_identical_signals_give_zero_loss_and_an_exactly_zero_gradient():
+    from grafx_amd import ops
+    from grafx_amd.losses import MultiResolutionSTFTLoss
+
+    target = f64.draw(128, 32, 1000)[0].cuda()
+    pred = target.clone().requires_grad_(True)
+    module = MultiResolutionSTFTLoss((128, 512), (32, 50), w_lin_mag=1.0, scale="mel", n_bins=8, sample_rate=b64.SAMPLE_RATE).cuda()
+    loss = module(pred, target)
+    loss.backward()
+    assert loss.item() == 0.0
+    assert torch.isfinite(pred.grad).all() and torch.count_nonzero(pred.grad) == 0
+    sums = ops.stft_band_loss_sums(target, target, window(512), 50, *bank("mel", 512))
+    assert torch.count_nonzero(sums[:, (0, 2, 3)]) == 0 and (sums[:, 1] > 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ 5: bits
+def test_results_are_the_same_bits_whatever_the_workspace_held_and_on_a_side_stream():
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = f64.SHAPES[4]
+    pred, target = on_gpu("mel", n_fft, hop, L, "half")
+    w, coef = window(n_fft), f64.coefficients("random", 7).cuda()
+    fb, bands = bank("mel", n_fft)
+    sums = ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps)
+    grad = ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps)
+    assert torch.equal(sums, ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps))
+    assert torch.equal(grad, ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps))
+    ws = torch.full((ops.stft_loss_ws_bytes(f64.ROWS, L, n_fft, hop),), 0xFF, dtype=torch.uint8, device="cuda")
+    assert torch.equal(sums, ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps, ws=ws))
+    ws.fill_(0xFF)
+    assert torch.equal(grad, ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, ws=ws))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        sums_side = ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps)
+        grad_side = ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps)
+    side.synchronize()
+    assert torch.equal(sums, sums_side) and torch.equal(grad, grad_side)
+
+
+# ------------------------------------------------------------------------------------------------ 6: accumulate
+def test_accumulate_adds_to_the_buffer_and_a_plain_call_overwrites_all_of_it():
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = f64.SHAPES[1]
+    pred, target = on_gpu("mel", n_fft, hop, L, "half")
+    w, coef = window(n_fft), f64.coefficients("random", 3).cuda()
+    fb, bands = bank("mel", n_fft)
+    plain = ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps)
+    held = torch.randn(f64.ROWS, L, generator=torch.Generator().manual_seed(5)).cuda() * plain.abs().max()
+    buf = held.clone()
+    assert ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, out=buf, accumulate=True) is buf
+    assert float((buf - (held + plain)).abs().max()) <= 1e-6 * float((held + plain).abs().max())
+    buf.fill_(float("nan"))
+    ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, out=buf)
+    assert torch.equal(buf, plain)
+    with pytest.raises(ValueError, match="accumulate"):
+        ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, accumulate=True)
+
+
+# ------------------------------------------------------------------------------------------------ 7: layouts
+def test_a_strided_view_is_read_in_place_and_a_grad_sink_is_written_once():
+    from grafx_amd import autograd, ops
+    from grafx_amd.losses import MultiResolutionSTFTLoss
+
+    n_fft, hop, L, eps = f64.SHAPES[1]
+    target, noise = f64.draw(n_fft, hop, L, rows=4)
+    flat_pred, flat_target = (0.5 * target + 0.02 * noise).cuda(), target.cuda()
+    big = torch.full((2, 5, 2, L + 24), float("nan"), device="cuda")         # a render buffer: (B, V, C, L) with room to spare
+    view = big[:, 3, :, 8:8 + L]
+    view.copy_(flat_pred.view(2, 2, L))
+    assert not view.is_contiguous()
+    before = big.clone()
+    w, coef = window(n_fft), f64.coefficients("random", 11, rows=4).cuda()
+    fb, bands = bank("mel", n_fft)
+    want_sums = ops.stft_band_loss_sums(flat_pred, flat_target, w, hop, fb, bands, eps)
+    want_grad = ops.stft_band_loss_bwd(flat_pred, flat_target, w, hop, fb, bands, coef, eps)
+    ptr = view.data_ptr()
+    assert torch.equal(ops.stft_band_loss_sums(view, flat_target.view(2, 2, L), w, hop, fb, bands, eps), want_sums)
+    grad = ops.stft_band_loss_bwd(view, flat_target.view(2, 2, L), w, hop, fb, bands, coef, eps)
+    assert grad.shape == (2, 2, L) and torch.equal(grad.view(4, L), want_grad)
+    assert view.data_ptr() == ptr and torch.equal(torch.nan_to_num(big, nan=7.0), torch.nan_to_num(before, nan=7.0))
+    # a strided destination, and one that shares memory with what is read -- the filterbank included
+    dest_big = torch.zeros_like(big)
+    dest = dest_big[:, 1, :, 4:4 + L]
+    ops.stft_band_loss_bwd(view, flat_target.view(2, 2, L), w, hop, fb, bands, coef, eps, out=dest)
+    assert torch.equal(dest.reshape(4, L), want_grad)
+    dest.zero_()
+    assert torch.count_nonzero(dest_big) == 0               # nothing was written beside the destination
+    with pytest.raises(ValueError, match="share memory"):
+        ops.stft_band_loss_bwd(view, flat_target.view(2, 2, L), w, hop, fb, bands, coef, eps, out=big[:, 3, :, 12:12 + L])
+    room = torch.zeros(4 * L + fb.numel(), device="cuda")
+    inside = room[4 * L - 8:4 * L - 8 + fb.numel()].view_as(fb).copy_(fb)
+    with pytest.raises(ValueError, match="share memory"):
+        ops.stft_band_loss_bwd(flat_pred, flat_target, w, hop, inside, bands, coef, eps, out=room[:4 * L].view(4, L))
+    # through autograd: the node writes the gradient of a registered input straight into its sink, once
+    module = MultiResolutionSTFTLoss((n_fft,), (hop,), eps=eps, filterbanks=(fb.cpu(),)).cuda()
+    leaf = flat_pred.view(2, 2, L).clone().requires_grad_(True)
+    module(leaf, flat_target.view(2, 2, L)).backward()
+    src = view.detach().requires_grad_(True)
+    sink_big = torch.zeros_like(big)
+    sink_view = sink_big[:, 2, :, :L]
+    with autograd.grad_sink(src, sink_view) as sink:
+        module(src, flat_target.view(2, 2, L)).backward()
+        assert sink.writes == 1
+    assert torch.equal(sink_view, leaf.grad) and torch.equal(src.grad, leaf.grad)
+
+
+# ------------------------------------------------------------------------------------------------ 8: many rows
+def test_rows_beyond_the_grid_limit_equal_the_three_row_call():
+    from grafx_amd import ops
+
+    n_fft, hop, L, eps = f64.SHAPES[0]
+    pred3, target3 = on_gpu("mel", n_fft, hop, L, "half")
+    R, at = 65537, (0, 65535, 65536)
+    g = torch.Generator(device="cuda").manual_seed(8)
+    pred, target = torch.randn(R, L, device="cuda", generator=g), torch.randn(R, L, device="cuda", generator=g)
+    pred[list(at)], target[list(at)] = pred3, target3
+    w = window(n_fft)
+    fb, bands = bank("mel", n_fft)
+    coef = torch.rand(R, 3, device="cuda", generator=g) + 0.25
+    coef3 = coef[list(at)].contiguous()
+    sums = ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps)
+    grad = ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps)
+    assert torch.equal(sums[list(at)], ops.stft_band_loss_sums(pred3, target3, w, hop, fb, bands, eps))
+    assert torch.equal(grad[list(at)], ops.stft_band_loss_bwd(pred3, target3, w, hop, fb, bands, coef3, eps))
+    assert torch.isfinite(sums).all() and torch.isfinite(grad).all()
+
+
+# ------------------------------------------------------------------------------------------------ 9: refusals
+def test_a_filterbank_off_the_staircase_takes_the_torch_path_and_bad_ones_are_refused():
+    from grafx_amd import ops
+    from grafx_amd.losses import MultiResolutionSTFTLoss
+
+    n_fft, hop, L, eps = f64.SHAPES[1]
+    pred, target = on_gpu("boxes", n_fft, hop, L, "half")
+    W = b64.filterbank("boxes", n_fft).flip(0).contiguous()              # rows from the top down: the same bands, no staircase
+    module = MultiResolutionSTFTLoss((n_fft,), (hop,), eps=eps, filterbanks=(W,), **WEIGHTS).cuda()
+    p = pred.clone().requires_grad_(True)
+    with pytest.warns(ops.FftLibraryWarning):
+        loss = module(p, target)
+    loss.backward()
+    assert "StftBandLossSumsFnBackward" not in graph_names(loss.grad_fn)
+    want, want_grad = b64.loss_and_grad(pred.cpu(), target.cpu(), ((n_fft, hop, n_fft),), (W,), 1.0, 0.7, 0.3, eps)
+    assert_close(loss.detach().reshape(1), want.reshape(1), TOL, "loss through torch_forward")
+    assert_close(p.grad, want_grad, TOL, "gradient through torch_forward")
+    with pytest.raises(ValueError, match="not both"):
+        MultiResolutionSTFTLoss((n_fft,), (hop,), filterbanks=(W,), scale="mel", n_bins=8, sample_rate=b64.SAMPLE_RATE)
+    with pytest.raises(ValueError, match="n_fft / 2 \\+ 1"):
+        MultiResolutionSTFTLoss((2 * n_fft,), (hop,), filterbanks=(W,))
+    # the ops: a filterbank of another transform's width, bands on the CPU, a filterbank that asks for a gradient
+    fb, bands = bank("boxes", n_fft)
+    with pytest.raises(ValueError, match="n_fft / 2 \\+ 1"):
+        ops.stft_band_loss_sums(pred, target, window(n_fft), hop, bank("boxes", 256)[0], bands, eps)
+    with pytest.raises(ValueError, match="int32 on the GPU"):
+        ops.stft_band_loss_sums(pred, target, window(n_fft), hop, fb, tuple(b.cpu() for b in bands), eps)
+    with pytest.raises(ValueError, match="no gradient"):
+        ops.stft_band_loss_sums(pred, target, window(n_fft), hop, fb.clone().requires_grad_(True), bands, eps)
+
+
+# ------------------------------------------------------------------------------------------------ 10: memory
+def test_forward_and_backward_allocate_the_gradient_and_little_else():
+    from grafx_amd import ops
+    from grafx_amd.losses import MultiResolutionSTFTLoss
+
+    n_fft, hop, L, eps = f64.SHAPES[4]
+    R = 8
+    target, noise = f64.draw(n_fft, hop, L, rows=R)
+    pred = (0.5 * target + 0.02 * noise).cuda().requires_grad_(True)
+    target = target.cuda()
+    module = MultiResolutionSTFTLoss((n_fft,), (hop,), eps=eps, scale="mel", n_bins=40, sample_rate=b64.SAMPLE_RATE).cuda()
+    module(pred, target).backward()                       # first call: whatever the library sets up once
+    pred.grad = None
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    module(pred, target).backward()
+    torch.cuda.synchronize()
+    growth = torch.cuda.max_memory_allocated() - base
+    bound = 1.5 * R * L * 4 + ops.stft_loss_ws_bytes(R, L, n_fft, hop) + module.filterbank_0.numel() * 4
+    spectrogram = R * (n_fft // 2 + 1) * (1 + L // hop) * 4
+    print(f"peak growth {growth} bytes, bound {bound:.0f} (one gradient tensor is {R * L * 4}, one spectrogram {spectrogram})")
+    assert pred.grad is not None and growth <= bound

@@ -13,7 +13,11 @@ torch.stft runs).  The torch path is tried from the largest batch of ``--batches
 fits in memory; the native path is measured there (the shared batch: the rounds alternate the two paths, so that they share
 whatever else the machine is doing) and at the first batch of the list alone.
 
+``--scale mel --n-bins N`` measures the loss on a mel scale instead (N Slaney bands per resolution at ``--sample-rate``):
+the native path is then csrc/stft_band_loss.hip, the torch path the same formula through torch.stft and a matmul.
+
     python tools/stft_loss_timing.py [--batches 256 128 64 32 16 8] [--length 131072] [--steps 5] [--repeats 5] [--native-only]
+                                     [--scale mel --n-bins 64 [--sample-rate 44100]]
 """
 import argparse
 import json
@@ -52,13 +56,18 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--native-only", action="store_true", help="stop after the first batch on the native path (for a profile)")
+    ap.add_argument("--scale", choices=["mel"], default=None, help="compare filterbank bands instead of bins")
+    ap.add_argument("--n-bins", type=int, default=64,
+                    help="bands per resolution with --scale (at 44.1 kHz the 512-point resolution has bins for 80 at most)")
+    ap.add_argument("--sample-rate", type=int, default=44100)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("stft_loss_timing: no GPU -- a time taken anywhere else says nothing")
 
     from grafx_amd.losses import MultiResolutionSTFTLoss
 
-    module = MultiResolutionSTFTLoss(sum_and_difference=True).cuda()
+    scale = {} if args.scale is None else {"scale": args.scale, "n_bins": args.n_bins, "sample_rate": args.sample_rate}
+    module = MultiResolutionSTFTLoss(sum_and_difference=True, **scale).cuda()
 
     def signals(batch):
         g = torch.Generator(device="cuda").manual_seed(batch)
@@ -79,6 +88,7 @@ def main():
         row = {"batch": batch, "rows": 4 * batch, "length": args.length, "path": path, "steps": args.steps, "repeats": len(times),
                "ms": round(sorted(times)[len(times) // 2], 3), "min_max_ms": [round(min(times), 3), round(max(times), 3)],
                "peak_MiB": round(peak, 1)}
+        row.update(scale)
         row.update(extra or {})
         print(json.dumps(row), flush=True)
 
