@@ -137,6 +137,10 @@ SIGNATURES = {
                                                    ctypes.c_float, vp, sz, vp]),
     "gfx_stft_band_loss_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, vp, vp, vp, vp, i64, f32p, f32p, RowMap,
                                                   i64, i64, i64, i64, ctypes.c_float, ctypes.c_int, vp, sz, vp]),
+    "gfx_kweight_energy_ws_bytes": (sz, [i64, i64, i64]),
+    "gfx_kweight_energy_f32": (ctypes.c_int, [f32p, RowMap, vp, vp, i64, i64, i64, i64, vp, sz, vp]),
+    "gfx_kweight_energy_bwd_f32": (ctypes.c_int, [f32p, RowMap, vp, vp, f32p, RowMap, i64, i64, i64, i64, ctypes.c_int, vp, sz,
+                                                  vp]),
 }
 
 _lib = None

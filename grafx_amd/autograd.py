@@ -917,3 +917,22 @@ class StftBandLossSumsFn(torch.autograd.Function):
             else:
                 gp = ops.stft_band_loss_bwd(pred, target, w, hop, *bank, coef, ctx.eps, out=gp, accumulate=i > 0)
         return (gp, None, None, None, None, *(None for _ in tensors))
+
+
+class KWeightEnergyFn(torch.autograd.Function):
+    """energy[r, c, k] = the sum of squares over sub-block k (``hop`` samples) of row-channel (r, c) of ``x`` behind the
+    two-biquad cascade ``coef`` (ops.kweight_energy; (2, 5) float64 on the host, shared by every row) -> (R, C, L // hop)
+    float64.  The tape holds ``x`` alone -- no filtered signal.  Backward: one ops.kweight_energy_bwd call, which rebuilds
+    the filtered signal from ``x`` and writes the gradient once, into the registered grad_sink when ``x`` is one."""
+
+    @staticmethod
+    def forward(ctx, x, coef, hop):
+        ctx.save_for_backward(x)
+        ctx.coef, ctx.hop = coef, hop
+        return ops.kweight_energy(x, coef, hop)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return ops.kweight_energy_bwd(x, ctx.coef, g.contiguous(), ctx.hop, out=_sink_for(x)), None, None

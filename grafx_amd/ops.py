@@ -1605,6 +1605,81 @@ def stft_band_loss_bwd(pred, target, window, hop, fb, bands, coef, eps=1e-8, out
     return out
 
 
+# ----------------------------------------------------------------------------------------- loudness
+def kweight_energy_ws_bytes(R, C, L):
+    """Bytes of workspace one gfx_kweight_energy_f32 / gfx_kweight_energy_bwd_f32 call needs (no GPU involved): 64 per
+    row-channel and 1024-sample tile; 0 for a zero or negative argument."""
+    return lib().gfx_kweight_energy_ws_bytes(R, C, L)
+
+
+def _kweight_args(what, x, coef, hop, ws, reads):
+    """What the two K-weighting entries share, checked: the signal's row map, the ten coefficients as a host array, the
+    number of sub-blocks and the workspace's size."""
+    xmap, R, C, L = rowmap(x)
+    if isinstance(coef, torch.Tensor) and coef.is_cuda:
+        raise ValueError(f"{what}: coef is read on the host at the call: a (2, 5) float64 CPU tensor or sequence")
+    coef = torch.as_tensor(coef, dtype=torch.float64)
+    _expect(coef, (2, 5), what + ": coef")
+    if not torch.isfinite(coef).all():
+        raise ValueError(f"{what}: coef holds a value that is not finite")
+    if isinstance(hop, bool) or not isinstance(hop, int) or not 1 <= hop <= L:
+        raise ValueError(f"{what}: hop={hop!r} must be an integer in 1..L={L}")
+    nbytes = lib().gfx_kweight_energy_ws_bytes(R, C, L)
+    if ws is not None:
+        _apart(what, "ws", ws, reads)
+        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 16:
+            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU, 16-byte aligned")
+    return xmap, R, C, L, (ctypes.c_double * 10)(*coef.reshape(-1).tolist()), L // hop, nbytes
+
+
+@_on_device
+def kweight_energy(x, coef, hop, ws=None):
+    """Sub-block energies of x (R,C,L), or a strided (B,n,C,L) view, behind the two-biquad cascade ``coef``
+    (gfx_kweight_energy_f32) -> (R, C, n_sub) float64, n_sub = L // hop: the sums of squares of the filtered signal over
+    consecutive runs of ``hop`` samples; the samples from n_sub * hop on belong to none.  ``coef``: (2, 5) float64 on the
+    CPU (or a sequence), (b0, b1, b2, a1, a2) per section, a0-normalised, the same for every row -- the K-weighting of
+    loudness.k_weighting.  The recursion and the sums run in double.  ``ws``: a uint8 workspace of at least
+    ``kweight_energy_ws_bytes(R, C, L)`` bytes to reuse.  Equal bits from call to call."""
+    what = "kweight_energy"
+    _require_gpu(x)
+    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop, ws, (x,))
+    energy = torch.empty((R, C, n_sub), dtype=torch.float64, device=x.device)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    with _timed("kweight_energy_kernel", 4 * R * C * L * 2):     # x twice: the tiles' end states, then the energies
+        check(lib().gfx_kweight_energy_f32(_ptr(x), xmap, c10, _ptr(energy), R, C, L, hop, *wsarg, _stream()),
+              "gfx_kweight_energy_f32")
+    return energy
+
+
+@_on_device
+def kweight_energy_bwd(x, coef, genergy, hop, out=None, accumulate=False, ws=None):
+    """Gradient with respect to ``x`` of sum(genergy * kweight_energy(x, coef, hop)) (gfx_kweight_energy_bwd_f32) -> a
+    float32 tensor of x's shape.  ``genergy``: (R, C, n_sub) float64 on the GPU.  The filtered signal is rebuilt from
+    ``x``; every gradient sample is stored once, the samples from n_sub * hop on get 0.  ``out``: the destination (x's
+    rows, channels and length; any strided (B,n,C,L) view), required with ``accumulate``, which adds to what it holds.
+    What the call writes (``out``, ``ws``) may share memory with nothing it reads.  ``ws``: as for :func:`kweight_energy`."""
+    what = "kweight_energy_bwd"
+    _require_gpu(x, out)
+    if not isinstance(genergy, torch.Tensor) or not genergy.is_cuda or genergy.dtype != torch.float64:
+        raise TypeError(f"{what}: genergy must be a float64 tensor on the GPU")
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate adds to a given out")
+    reads = (x, genergy)
+    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop, ws, reads)
+    _expect(genergy, (R, C, n_sub), what + ": genergy")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _, gmap = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    # x three times (end states, the adjoint's end states, the adjoint), gx once
+    with _timed("kweight_energy_bwd_kernel", 4 * R * C * L * (5 if accumulate else 4)):
+        check(lib().gfx_kweight_energy_bwd_f32(_ptr(x), xmap, c10, pin(genergy), _ptr(out), gmap, R, C, L, hop,
+                                               int(bool(accumulate)), *wsarg, _stream()), "gfx_kweight_energy_bwd_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- routing
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):

@@ -744,6 +744,36 @@ int gfx_stft_band_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float
                                gfx_rowmap_t gmap, int64_t R, int64_t L, int64_t n_fft, int64_t hop, float eps, int accumulate,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* ---- block energies behind a two-section biquad cascade with shared coefficients (ITU-R BS.1770 K-weighting) ----
+ * Every row-channel of x (R rows of C channels through a row map with a channel stride, as gfx_biquad_cascade_f32: a
+ * (B, C, L) slice of a (B, n, C, L) render buffer is read in place) goes through
+ *   w_i[n] = u_{i-1}[n] - a1 w_i[n-1] - a2 w_i[n-2],   u_i[n] = b0 w_i[n] + b1 w_i[n-1] + b2 w_i[n-2],   i = 1, 2,
+ * u_0 = x, y = u_2, from silence, and leaves
+ *   energy[r, c, k] = sum of y[n]^2 over k * hop <= n < (k + 1) * hop,   k < n_sub = L / hop (floor)
+ * as (R, C, n_sub) contiguous doubles; samples from n_sub * hop on belong to no sub-block.  `coef` is ten doubles in HOST
+ * memory, (b0, b1, b2, a1, a2) per section, a0-normalised, shared by the whole call and read at the call: the powers of
+ * the cascade's 4 x 4 state matrix that join runs of samples are built from it on the host.  Recursion, states, squares
+ * and sums are in double; x is read as float32.
+ * gfx_kweight_energy_bwd_f32: gx (=, or += with accumulate != 0) the gradient of sum genergy * energy with respect to x,
+ * genergy (R, C, n_sub) contiguous doubles: with v[n] = 2 genergy[n / hop] y[n] (0 from n_sub * hop on) it is the adjoint
+ * cascade applied to v, the same recursion run over the reversed signal.  y is rebuilt from x; nothing of the signal's
+ * size is kept between the two calls.  Every gradient sample is stored once, float32, through gmap (as xmap).
+ * Tile: 1024 samples of a row-channel per wave; rows may be of any length, a single long row is spread over the device.
+ * No atomics: equal bits from run to run, and a row-channel's results do not depend on the other rows of the call.
+ * Any hop in 1 .. L.  GFX_EINVAL: a null pointer (ws included), R, C or L <= 0, hop outside 1 .. L, an empty row map, a
+ * coefficient that is not finite (or so large that a power of the state matrix is not), energy / genergy not 8-byte or ws
+ * not 16-byte aligned, more than 2^31 - 1 row-channels or 2^33 - 4 tiles; a workspace below
+ *   gfx_kweight_energy_ws_bytes = R * C * ceil(L / 1024) * 64 bytes   (0 for a zero or negative argument)
+ * is GFX_ENOSPC.  One buffer serves both entries: per tile the entering state of the forward recursion (32 bytes) and
+ * the parts of the sub-blocks that cross its edges, or the adjoint's entering state.  Every check comes before the
+ * first launch. */
+size_t gfx_kweight_energy_ws_bytes(int64_t R, int64_t C, int64_t L);
+int gfx_kweight_energy_f32(const float* x, gfx_rowmap_t xmap, const double* coef, double* energy, int64_t R, int64_t C,
+                           int64_t L, int64_t hop, void* ws, size_t ws_bytes, void* stream);
+int gfx_kweight_energy_bwd_f32(const float* x, gfx_rowmap_t xmap, const double* coef, const double* genergy, float* gx,
+                               gfx_rowmap_t gmap, int64_t R, int64_t C, int64_t L, int64_t hop, int accumulate, void* ws,
+                               size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
