@@ -12,8 +12,9 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # processors, losses and the loudness meter import the native library lazily so that graph-only use works without it
-    if name in ("processors", "ops", "losses", "loudness"):
+    # processors, losses, the loudness meter and the resampler import the native library lazily so that graph-only use works
+    # without it
+    if name in ("processors", "ops", "losses", "loudness", "resample"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")

@@ -141,6 +141,9 @@ SIGNATURES = {
     "gfx_kweight_energy_f32": (ctypes.c_int, [f32p, RowMap, vp, vp, i64, i64, i64, i64, vp, sz, vp]),
     "gfx_kweight_energy_bwd_f32": (ctypes.c_int, [f32p, RowMap, vp, vp, f32p, RowMap, i64, i64, i64, i64, ctypes.c_int, vp, sz,
                                                   vp]),
+    "gfx_upfirdn_f32": (ctypes.c_int, [f32p, RowMap, f32p, i64, i64, i64, i64, f32p, RowMap, i64, i64, i64, i64, ctypes.c_int, vp]),
+    "gfx_upfirdn_absmax_ws_bytes": (sz, [i64, i64, i64]),
+    "gfx_upfirdn_absmax_f32": (ctypes.c_int, [f32p, RowMap, f32p, i64, i64, i64, i64, f32p, vp, i64, i64, i64, i64, vp, sz, vp]),
 }
 
 _lib = None

@@ -89,13 +89,18 @@ class grad_sink:
         return self.entry[1]
 
 
-def _sink_for(x):
+def _sink_at(ptr, shape):
+    """The sink registered for the view at address ``ptr`` of shape ``shape``: for a node that keeps no input on its tape."""
     with _SINKS_LOCK:
-        e = _SINKS.get(x.data_ptr())
-        if e is not None and tuple(x.shape) == tuple(e[0].shape):
+        e = _SINKS.get(ptr)
+        if e is not None and tuple(shape) == tuple(e[0].shape):
             e[1] += 1
             return e[0]
     return None
+
+
+def _sink_for(x):
+    return _sink_at(x.data_ptr(), x.shape)
 
 
 # Gradient sources (the mirror image of the sinks; same registration by the stage-wise backward): data_ptr of a stage's
@@ -936,3 +941,71 @@ class KWeightEnergyFn(torch.autograd.Function):
     def backward(ctx, g):
         x, = ctx.saved_tensors
         return ops.kweight_energy_bwd(x, ctx.coef, g.contiguous(), ctx.hop, out=_sink_for(x)), None, None
+
+
+class UpfirdnFn(torch.autograd.Function):
+    """y[r, c, m] = sum_k x[r, c, k] h[m down + offset - k up], m < n_out (ops.upfirdn; ``h``: 1-D float32 taps on the GPU,
+    shared by every row).  The tape holds the taps and ``x``'s shape -- no signal, no phase-expanded tensor.  Backward: one
+    ops.upfirdn call on the cotangent with the taps reversed, ``up`` and ``down`` exchanged, offset' = N - 1 - offset and
+    n_out = L, written into the registered grad_sink when ``x`` is one.  The taps get no gradient; there is no double
+    backward."""
+
+    @staticmethod
+    def forward(ctx, x, h, up, down, offset, n_out):
+        if ctx.needs_input_grad[1]:
+            raise ValueError("UpfirdnFn: the taps get no gradient (detach them)")
+        ctx.save_for_backward(h)
+        ctx.geometry = (up, down, offset, tuple(x.shape), x.data_ptr())
+        y = ops.upfirdn(x, h, up, down, offset, n_out)
+        return y if x.ndim == 3 else y.view(*x.shape[:-1], y.shape[-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        h, = ctx.saved_tensors
+        up, down, offset, shape, ptr = ctx.geometry
+        if g.stride(-1) != 1 or 0 in g.stride():       # (an expanded cotangent, as sum() hands back)
+            g = g.contiguous()
+        sink = _sink_at(ptr, shape)
+        gx = ops.upfirdn(g, h.flip(0), down, up, h.numel() - 1 - offset, n_out=shape[-1],
+                         out=torch.empty(shape, dtype=torch.float32, device=g.device) if sink is None else sink)
+        return gx, None, None, None, None, None
+
+
+class UpfirdnAbsmaxFn(torch.autograd.Function):
+    """peak[r, c] = max over m < n_out of |y[r, c, m]|, y = ops.upfirdn(x, h, up, down, offset) (one ops.upfirdn_absmax
+    call: y never reaches memory) -> (peak, index), index the lowest m that attains the peak (not differentiable).
+    Differentiable in ``x`` through the arg-max: y[m*] depends on the at most ceil(N / up) samples under its tap window,
+    x[q - j] with weight h[ph + j up] (q, ph the quotient and remainder of m* down + offset by up), so the forward gathers
+    those samples and taps for the sign of y[m*] and the tape holds the weights sign(y[m*]) h[...] and their positions --
+    (R, C, ceil(N / up)) each, no signal.  Backward: one scatter of g times the weights into zeros (the registered
+    grad_sink when ``x`` is one).  An all-zero row has weight 0 everywhere.  Small torch ops, nothing synchronises."""
+
+    @staticmethod
+    def forward(ctx, x, h, up, down, offset, n_out):
+        if ctx.needs_input_grad[1]:
+            raise ValueError("UpfirdnAbsmaxFn: the taps get no gradient (detach them)")
+        peak, index = ops.upfirdn_absmax(x, h, up, down, offset, n_out)
+        N, L = h.numel(), x.shape[-1]
+        p = index * down + offset
+        q, ph = p // up, p % up
+        j = torch.arange(-(-N // up), device=x.device)
+        tap, k = ph[..., None] + j * up, q[..., None] - j                       # (R, C, K)
+        live = (tap < N) & (k >= 0) & (k < L)
+        k = k.clamp(0, L - 1).view(*x.shape[:-1], -1)
+        w = torch.where(live, h[tap.clamp(max=N - 1)], torch.zeros((), device=x.device)).view(k.shape)
+        w = w * torch.sign((w * x.gather(-1, k)).sum(-1, keepdim=True))
+        ctx.save_for_backward(w, k)
+        ctx.geometry = (tuple(x.shape), x.data_ptr())
+        ctx.mark_non_differentiable(index)
+        return peak.view(x.shape[:-1]), index.view(x.shape[:-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        w, k = ctx.saved_tensors
+        shape, ptr = ctx.geometry
+        sink = _sink_at(ptr, shape)
+        gx = torch.zeros(shape, dtype=torch.float32, device=g.device) if sink is None else sink.zero_()
+        gx.scatter_add_(-1, k, g[..., None] * w)                                # (the positions of one row are distinct)
+        return gx, None, None, None, None, None

@@ -1,6 +1,7 @@
 """Programme loudness after ITU-R BS.1770: K-weighting, mean squares over overlapping blocks, the two gates, LUFS.
 :class:`IntegratedLoudness` meters a batch of signals on the GPU and is differentiable in them; :func:`loudness_normalize`
-brings them to a target.  The K-weighting filter and the sums of squares run in double on the native kernels of
+brings them to a target; :class:`TruePeak` and :func:`true_peak_normalize` are the other half of the recommendation, the
+oversampled peak in dBTP.  The K-weighting filter and the sums of squares run in double on the native kernels of
 csrc/loudness.hip (autograd.KWeightEnergyFn: the tape holds the signal alone); the gating is a handful of float64 torch ops
 on the small (rows, channels, sub-blocks) tensor."""
 import math
@@ -9,7 +10,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .autograd import KWeightEnergyFn
+from .autograd import KWeightEnergyFn, UpfirdnAbsmaxFn
 
 # the analogue prototypes whose bilinear transform at 48 kHz is the standard's coefficient table
 SHELF_F0, SHELF_GAIN_DB, SHELF_Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
@@ -153,4 +154,72 @@ def loudness_normalize(x, target_lufs, meter, detach_gain=False):
     finite = torch.isfinite(level)
     level = torch.where(finite, level, torch.full_like(level, float(target_lufs)))
     gain = torch.pow(10.0, (float(target_lufs) - level) / 20.0)
+    return x * gain[..., None, None]
+
+
+def _dbtp(p):
+    """20 log10 p where p > 0, -inf elsewhere, with a zero gradient there (no NaN either way)."""
+    positive = p > 0
+    safe = torch.where(positive, p, torch.ones_like(p))
+    return torch.where(positive, 20.0 * torch.log10(safe), torch.full_like(p, -math.inf))
+
+
+class TruePeak(nn.Module):
+    """True-peak level (BS.1770 Annex 2) of ``x`` (..., C, L) in dBTP -> (...), in ``x.dtype``, differentiable in ``x``:
+    20 log10 of the largest |y| over the item's channels, y being ``x`` oversampled by ``oversample`` (``oversample * L``
+    samples per channel); -inf for a silent item, with a zero gradient there and no NaN.  ``channel_peaks`` gives the linear
+    peak per channel, (..., C).
+
+    The default taps are ``resample.sinc_kernel(1, oversample)``: 49 taps at 4x, about 12 per phase, which is the structure
+    of BS.1770 Annex 2.  The standard's own 48-coefficient table is not reproduced here, so it is not the default;
+    ``taps=`` takes any 1-D prototype at the oversampled rate (the table, for whoever has it), and ``offset`` is then
+    (N - 1) // 2.  The signal must be float32 on the GPU: the meter is one native call (ops.upfirdn_absmax) and the
+    oversampled signal never reaches memory.  The gradient of a channel's peak lands on the at most ceil(N / oversample)
+    input samples under the tap window of the output that attains it (autograd.UpfirdnAbsmaxFn)."""
+
+    def __init__(self, oversample=4, taps=None):
+        super().__init__()
+        if isinstance(oversample, bool) or not isinstance(oversample, int) or not 1 <= oversample <= ops.UPFIRDN_MAX_RATIO:
+            raise ValueError(f"TruePeak: oversample={oversample!r} must be an integer in 1..{ops.UPFIRDN_MAX_RATIO}")
+        if taps is None:
+            from .resample import sinc_kernel
+
+            h, _, _, self.offset = sinc_kernel(1, oversample)
+        else:
+            h = torch.as_tensor(taps).detach().cpu()
+            if h.ndim != 1 or not 1 <= h.numel() <= ops.UPFIRDN_MAX_TAPS:
+                raise ValueError(f"TruePeak: taps must hold 1..{ops.UPFIRDN_MAX_TAPS} values in one dimension, got "
+                                 f"{tuple(h.shape)}")
+            self.offset = (h.numel() - 1) // 2
+        self.oversample = oversample
+        self.register_buffer("taps", h.float(), persistent=False)
+
+    def channel_peaks(self, x):
+        """(..., C, L) -> (..., C) float32: the largest magnitude of every channel's oversampled signal."""
+        if x.ndim < 2:
+            raise ValueError(f"TruePeak: x must be (..., C, L), got {tuple(x.shape)}")
+        ops._require_gpu(x)
+        if x.ndim == 2:
+            rows = x.unsqueeze(0)
+        elif x.ndim > 4 or x.stride(-1) != 1:
+            rows = x.reshape(-1, *x.shape[-2:])
+        else:
+            rows = x                                       # (R,C,L) or a strided (B,n,C,L) view, read in place
+        peak, _ = UpfirdnAbsmaxFn.apply(rows, self.taps, self.oversample, 1, self.offset, self.oversample * x.shape[-1])
+        return peak.view(x.shape[:-1])
+
+    def forward(self, x):
+        return _dbtp(self.channel_peaks(x).amax(-1)).to(x.dtype)
+
+
+def true_peak_normalize(x, target_dbtp, meter, detach_gain=False):
+    """``x`` (..., C, L) scaled per item to a true peak of ``target_dbtp`` as ``meter`` (a :class:`TruePeak`) measures it:
+    x * 10^((target - level) / 20).  A silent item (-inf) is returned unchanged.  ``detach_gain``: the gain is a constant of
+    the gradient; otherwise the gradient flows through the meter as well."""
+    level = meter(x)
+    if detach_gain:
+        level = level.detach()
+    finite = torch.isfinite(level)
+    level = torch.where(finite, level, torch.full_like(level, float(target_dbtp)))
+    gain = torch.pow(10.0, (float(target_dbtp) - level) / 20.0)
     return x * gain[..., None, None]

@@ -1680,6 +1680,86 @@ def kweight_energy_bwd(x, coef, genergy, hop, out=None, accumulate=False, ws=Non
     return out
 
 
+# ----------------------------------------------------------------------------------------- polyphase FIR
+UPFIRDN_TILE = 1024          # GFX_UPFIRDN_TILE of include/grafx_amd.h: consecutive outputs of a row-channel per workgroup
+UPFIRDN_MAX_RATIO = 1024     # up and down
+UPFIRDN_MAX_TAPS = 16384
+
+
+def upfirdn_absmax_ws_bytes(R, C, M):
+    """Bytes of workspace one gfx_upfirdn_absmax_f32 call needs (no GPU involved): 16 per row-channel and tile of
+    UPFIRDN_TILE outputs; 0 for a zero or negative argument."""
+    return lib().gfx_upfirdn_absmax_ws_bytes(R, C, M)
+
+
+def _upfirdn_args(what, x, h, up, down, offset, n_out):
+    """What the two polyphase entries share, checked before anything is allocated: the signal's row map, the taps, the
+    ratio, the offset and the number of outputs -> (xmap, R, C, L, N, M)."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32:
+        raise TypeError(f"{what}: h must be a float32 tensor on the GPU")
+    if h.ndim != 1 or not 1 <= h.numel() <= UPFIRDN_MAX_TAPS:
+        raise ValueError(f"{what}: h must hold 1..{UPFIRDN_MAX_TAPS} taps in one dimension, got {tuple(h.shape)}")
+    N = h.numel()
+    for name, v in (("up", up), ("down", down)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= UPFIRDN_MAX_RATIO:
+            raise ValueError(f"{what}: {name}={v!r} must be an integer in 1..{UPFIRDN_MAX_RATIO}")
+    if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset < N:
+        raise ValueError(f"{what}: offset={offset!r} must be an integer in 0..N-1={N - 1}")
+    xmap, R, C, L = rowmap(x)
+    if min(R, C, L) < 1:
+        raise ValueError(f"{what}: x {tuple(x.shape)} holds no sample")
+    M = -(-(L * up + N - 1 - offset) // down) if n_out is None else n_out
+    if isinstance(M, bool) or not isinstance(M, int) or M < 1:
+        raise ValueError(f"{what}: n_out={n_out!r} must be a positive integer")
+    return xmap, R, C, L, N, M
+
+
+@_on_device
+def upfirdn(x, h, up, down, offset=0, n_out=None, out=None, accumulate=False):
+    """y[r,c,m] = sum_k x[r,c,k] h[m down + offset - k up], m < n_out (gfx_upfirdn_f32): x (R,C,L), or a strided (B,n,C,L)
+    view read in place, zero outside [0, L); ``h``: N <= 16384 float32 taps on the GPU, shared by every row, zero outside
+    [0, N); ``up``, ``down`` in 1..1024; ``offset`` in 0..N-1.  -> (R, C, n_out) float32, or ``out``: a (R, C, n_out) tensor
+    or strided (B, n, C, n_out) view, written in place (``accumulate``: added to; requires ``out``).  ``n_out`` defaults to
+    ceil((L up + N - 1 - offset) / down), every output with a non-empty tap window; outputs beyond them are 0.0.  The adjoint
+    with respect to x is ``upfirdn(g, h.flip(0), down, up, N - 1 - offset, n_out=L)``.  ``out`` may share memory with
+    neither ``x`` nor ``h``.  Equal bits from call to call; a row's result does not depend on the other rows."""
+    what = "upfirdn"
+    _require_gpu(x, out)
+    xmap, R, C, L, N, M = _upfirdn_args(what, x, h, up, down, offset, n_out)
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate adds to a given out")
+    out, ymap = _output(out, (R, C, M), x.device, what, apart=(x, h))
+    pin = _Pin()
+    with _timed("upfirdn_kernel", 4 * R * C * (L + M)):
+        check(lib().gfx_upfirdn_f32(_ptr(x), xmap, pin(h), N, up, down, offset, _ptr(out), ymap, R, C, L, M,
+                                    int(bool(accumulate)), _stream()), "gfx_upfirdn_f32")
+    return out
+
+
+@_on_device
+def upfirdn_absmax(x, h, up, down, offset=0, n_out=None, ws=None):
+    """(peak, index) of :func:`upfirdn`'s output without writing it (gfx_upfirdn_absmax_f32): peak (R, C) float32, the
+    largest |y[r,c,m]| over m < n_out, and index (R, C) int64, the lowest m that attains it (0.0 and 0 for an all-zero
+    row).  ``ws``: a uint8 workspace of at least ``upfirdn_absmax_ws_bytes(R, C, n_out)`` bytes to reuse, 16-byte aligned,
+    apart from ``x`` and ``h``.  Equal bits from call to call."""
+    what = "upfirdn_absmax"
+    _require_gpu(x)
+    xmap, R, C, L, N, M = _upfirdn_args(what, x, h, up, down, offset, n_out)
+    nbytes = lib().gfx_upfirdn_absmax_ws_bytes(R, C, M)
+    if ws is not None:
+        _apart(what, "ws", ws, (x, h))
+        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 16:
+            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU, 16-byte aligned")
+    peak = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    index = torch.empty((R, C), dtype=torch.int64, device=x.device)
+    pin = _Pin()
+    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    with _timed("upfirdn_absmax_kernel", 4 * R * C * L):
+        check(lib().gfx_upfirdn_absmax_f32(_ptr(x), xmap, pin(h), N, up, down, offset, _ptr(peak), _ptr(index), R, C, L, M,
+                                           *wsarg, _stream()), "gfx_upfirdn_absmax_f32")
+    return peak, index
+
+
 # ----------------------------------------------------------------------------------------- routing
 @_on_device
 def gather_sum(buf, src_idx, seg_ptr, out):

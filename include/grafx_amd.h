@@ -774,6 +774,33 @@ int gfx_kweight_energy_bwd_f32(const float* x, gfx_rowmap_t xmap, const double* 
                                gfx_rowmap_t gmap, int64_t R, int64_t C, int64_t L, int64_t hop, int accumulate, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* ---- rational polyphase FIR ("upfirdn"): sample-rate conversion, its adjoint, and the oversampled peak ----
+ * Every row-channel of x (R rows of C channels of L samples through a row map with a channel stride, as
+ * gfx_kweight_energy_f32: a (B, C, L) slice of a (B, n, C, L) render buffer is read and written in place) gives
+ *   y[r, c, m] = sum_k x[r, c, k] h[m * down + offset - k * up],   0 <= m < M,
+ * x zero outside [0, L), h zero outside [0, N): N float32 taps on the device, shared by every row.  About N / up products
+ * per output.  y is stored once per sample through ymap (=, or += with accumulate != 0).  M is the caller's: any M >= 1;
+ * outputs whose tap window misses [0, L) entirely are 0.0.  The adjoint with respect to x is the same entry with up and
+ * down exchanged, the taps reversed, offset' = N - 1 - offset and M' = L.
+ * Tile: GFX_UPFIRDN_TILE consecutive outputs of one row-channel per workgroup; the taps and the span of x under the tile
+ * (under a part of it where down / up is large) are staged in LDS.  The tile's base index m * down + offset is formed in 64
+ * bits.  Each output accumulates in float32 over ascending k: equal bits from run to run, and a row-channel's result does
+ * not depend on the other rows of the call (taps {1.0f} with up = down = 1 return x's bits).  No workspace, no atomics.
+ * gfx_upfirdn_absmax_f32 runs the same tiles without writing y and leaves, per row-channel, peak[r, c] = max_m |y[m]|
+ * (R * C floats) and index[r, c] (R * C int64_t), the LOWEST m that attains it (0.0 and 0 for an all-zero row): per-tile
+ * (value, index) pairs go to the workspace, a second kernel reduces a row's pairs.  No atomics.
+ *   gfx_upfirdn_absmax_ws_bytes = R * C * ceil(M / GFX_UPFIRDN_TILE) * 16 bytes   (0 for a zero or negative argument)
+ * GFX_EINVAL: a null pointer (ws included), R, C, L or M <= 0, an empty row map, up or down outside 1 .. 1024, N outside
+ * 1 .. 16384, offset outside 0 .. N - 1, more than 2^31 - 1 row-channels or tiles in the call, ws not 16-byte or index not
+ * 8-byte aligned; a workspace that is too small is GFX_ENOSPC.  Every check comes before the first launch. */
+#define GFX_UPFIRDN_TILE 1024
+int gfx_upfirdn_f32(const float* x, gfx_rowmap_t xmap, const float* h, int64_t N, int64_t up, int64_t down, int64_t offset,
+                    float* y, gfx_rowmap_t ymap, int64_t R, int64_t C, int64_t L, int64_t M, int accumulate, void* stream);
+size_t gfx_upfirdn_absmax_ws_bytes(int64_t R, int64_t C, int64_t M);
+int gfx_upfirdn_absmax_f32(const float* x, gfx_rowmap_t xmap, const float* h, int64_t N, int64_t up, int64_t down,
+                           int64_t offset, float* peak, int64_t* index, int64_t R, int64_t C, int64_t L, int64_t M, void* ws,
+                           size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
