@@ -658,6 +658,49 @@ class WaveshaperFn(torch.autograd.Function):
                 like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None)
 
 
+class OversampledWaveshaperFn(torch.autograd.Function):
+    """WaveshaperFn at ``factor`` times the rate (ops.oversampled_waveshaper: interpolate, shape, decimate in one fused
+    pass each way).  Saved: x, the parameters, the R * C means of remove_dc and the two filters -- no signal at the high
+    rate, which exists in LDS only.  ``filters``: (h_up, offset_up, h_dn, offset_dn), the taps float32 on the GPU; they get
+    no gradient.  There is no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc, factor, filters):
+        h_up, offset_up, h_dn, offset_dn = filters
+        if h_up.requires_grad or h_dn.requires_grad:
+            raise ValueError("OversampledWaveshaperFn: the taps get no gradient (detach them)")
+        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+            x = x.contiguous()
+        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
+            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+            dc = ops.row_mean(x) if remove_dc else None
+        else:
+            y, dc = ops.oversampled_waveshaper(x, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain, log_post_gain,
+                                               p0=p0, p1=p1, use_tanh=use_tanh, inverse_post_gain=inverse_post_gain,
+                                               remove_dc=remove_dc, return_dc=True)
+        ctx.save_for_backward(x, log_pre_gain, log_post_gain, p0, p1, dc, h_up, h_dn)
+        ctx.cfg = (mode, use_tanh, inverse_post_gain, remove_dc, factor, offset_up, offset_dn)
+        return y.view(x.shape) if four else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, log_pre_gain, log_post_gain, p0, p1, dc, h_up, h_dn = ctx.saved_tensors
+        mode, use_tanh, inverse_post_gain, remove_dc, factor, offset_up, offset_dn = ctx.cfg
+        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+            gy = gy.contiguous()
+        want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
+        gx, grads = ops.oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain,
+                                                   log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
+                                                   inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, dc=dc,
+                                                   out=_sink_for(x) if "x" in want else None, want=want)
+        like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
+        return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain),
+                like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None, None, None)
+
+
 class StftReverbIrFn(torch.autograd.Function):
     """The taps of STFTMaskedNoiseReverb (reverb.py:161-200, ms_to_lr, normalize_impulse) for n_fft = 384, hop = 192 as one
     autograd node: forward is the inference kernel (``ops.stft_reverb_ir``, "fft" schedule; times ``row_gain`` when

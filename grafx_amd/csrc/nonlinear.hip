@@ -8,21 +8,10 @@
 // where f = tanh or identity, dc = the row-channel mean when remove_dc is set (row_mean_kernel),
 // pre = exp(log_pre_gain), post = exp(log_post_gain) or 1/pre.  The upstream torch code materialises
 // K full-size tensors for the two polynomial shapers; here the K terms live in registers.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+// The per-sample math (WsRow, shape, ws_row_setup, bwd_samples) lives in waveshaper.hpp, shared with oversampled.hip.
+#include "waveshaper.hpp"
 
 namespace gfx {
-
-constexpr int WS_MAX_K = 32;
-
-__device__ __forceinline__ int64_t nrow_off(const gfx_rowmap_t& m, int64_t r, int c) {
-    const unsigned inner = (unsigned)m.inner, rr = (unsigned)r;
-    const unsigned q = rr / inner, rem = rr - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
 
 struct WsArgs {
     gfx_rowmap_t xmap, ymap;
@@ -30,78 +19,6 @@ struct WsArgs {
     int C, mode, K;
     int use_tanh, inverse_post;
 };
-
-struct WsRow {
-    float pre, post, dc;
-    float b, tb;                    // tanh: bias, tanh(bias)
-    float kp, kn, gp, gn, ap, an, bp, bn;  // piecewise
-    const float* w;                 // polynomial weights (already tanh'ed), in LDS: a run-time-indexed register
-};                                  // array would live in scratch memory
-
-template <int MODE>
-__device__ __forceinline__ float shape(float x, const WsRow& q, int K, bool use_tanh) {
-    const float u = (x - q.dc) * q.pre;
-    float y;
-    if (MODE == GFX_WS_TANH) {
-        y = tanhf(u + q.b) - q.tb;
-    } else if (MODE == GFX_WS_PIECEWISE) {
-        if (u > q.kp)
-            y = q.ap * tanhf(q.gp * (u - q.kp)) + q.bp;
-        else if (u < -q.kn)
-            y = q.an * tanhf(q.gn * (u + q.kn)) + q.bn;
-        else
-            y = tanhf(u);
-    } else if (MODE == GFX_WS_POWER) {
-        float p = 1.0f;
-        y = q.w[0] * (use_tanh ? tanhf(1.0f) : 1.0f);
-        for (int k = 1; k < K; ++k) {
-            p *= u;
-            y += q.w[k] * (use_tanh ? tanhf(p) : p);
-        }
-    } else {  // Chebyshev
-        float t0 = 1.0f, t1 = u;
-        y = q.w[0] * (use_tanh ? tanhf(1.0f) : 1.0f);
-        if (K > 1) y += q.w[1] * (use_tanh ? tanhf(u) : u);
-        for (int k = 2; k < K; ++k) {
-            const float t2 = 2.0f * u * t1 - t0;
-            y += q.w[k] * (use_tanh ? tanhf(t2) : t2);
-            t0 = t1;
-            t1 = t2;
-        }
-    }
-    return y * q.post;
-}
-
-// the row's constants, as both the forward and the backward kernel use them (polynomial weights: tanh'ed, into LDS)
-template <int MODE>
-__device__ __forceinline__ void ws_row_setup(WsRow& q, float* sw, int64_t r, int K, int inverse_post,
-                                             const float* __restrict__ log_pre, const float* __restrict__ log_post,
-                                             const float* __restrict__ p0, const float* __restrict__ p1) {
-    q.w = sw;
-    q.pre = log_pre ? expf(log_pre[r]) : 1.0f;
-    q.post = inverse_post ? 1.0f / q.pre : (log_post ? expf(log_post[r]) : 1.0f);
-    q.b = q.tb = 0.0f;
-    if (MODE == GFX_WS_TANH && p0) {
-        q.b = p0[r];
-        q.tb = tanhf(q.b);
-    }
-    if (MODE == GFX_WS_PIECEWISE) {
-        // nonlinear.py:163-166: threshold splits as (kn, kp), hardness as (gp, gn)
-        q.gp = expf(p0[2 * r]);
-        q.gn = expf(p0[2 * r + 1]);
-        q.kn = 1.0f / (1.0f + expf(-p1[2 * r]));
-        q.kp = 1.0f / (1.0f + expf(-p1[2 * r + 1]));
-        q.bp = tanhf(q.kp);
-        q.bn = -tanhf(q.kn);
-        q.ap = (1.0f - q.bp) / q.gp;
-        q.an = (1.0f + q.bn) / q.gn;
-    }
-    if (MODE == GFX_WS_POWER || MODE == GFX_WS_CHEBYSHEV) {
-        __syncthreads();  // previous row's readers are done
-        if ((int)threadIdx.x < K) sw[threadIdx.x] = tanhf(p0[r * K + threadIdx.x]);
-        __syncthreads();
-    }
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void waveshaper_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -230,128 +147,9 @@ struct WsBwdArgs {
     int use_tanh, inverse_post, want_par;
 };
 
-// slots of a row's sums: 0 = d/d log_pre, 1 = d/d log_post, 2.. = the mode's own
-template <int MODE>
-struct WsAcc {
-    static constexpr int N = MODE == GFX_WS_TANH ? 3 : MODE == GFX_WS_PIECEWISE ? 6 : 2 + WS_MAX_K;
-};
-
-static inline int ws_nsums(int64_t K) { return K > 0 ? 2 + (int)K : 6; }
 static inline int64_t ws_blocks(int64_t L) {
     const int64_t bx = (L / 4 + 255) / 256;
     return bx > 64 ? 64 : (bx < 1 ? 1 : bx);
-}
-
-// NV samples of one row-channel: their input gradient into go[], their terms onto the thread's sums acc[] (every index a
-// compile-time constant after unrolling: a run-time-indexed accumulator array would live in scratch memory)
-template <int MODE, int NV>
-__device__ __forceinline__ void bwd_samples(const float (&xs)[NV], const float (&gs)[NV], float (&go)[NV], const WsRow& q,
-                                            int K, bool use_tanh, float inv, bool par, float (&acc)[WsAcc<MODE>::N]) {
-    if (MODE == GFX_WS_TANH) {
-        const float db = 1.0f - q.tb * q.tb;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float u = (xs[j] - q.dc) * q.pre, G = gs[j] * q.post;
-            const float th = tanhf(u + q.b), d = 1.0f - th * th, s = th - q.tb;
-            go[j] = G * d * q.pre;
-            if (par) {
-                acc[0] += G * (d * u - inv * s);
-                acc[1] += G * s;
-                acc[2] += G * (d - db);
-            }
-        }
-    } else if (MODE == GFX_WS_PIECEWISE) {
-        // hi: y = ap tanh(gp (u - kp)) + bp,  ap = (1 - tanh kp) / gp   -> d/d log gp = ap (a d - t),  a = gp (u - kp)
-        //     d/d kp = sech^2(kp) (1 - t / gp) - (1 - bp) d;   lo mirrors it with kn, gn;   (acc[2..5] are scaled by
-        //     ap, an, kn (1 - kn), kp (1 - kp) when the partials are written)
-        const float skp = 1.0f - q.bp * q.bp, skn = 1.0f - q.bn * q.bn, rgp = 1.0f / q.gp, rgn = 1.0f / q.gn;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float u = (xs[j] - q.dc) * q.pre, G = gs[j] * q.post;
-            float s, sp;
-            if (u > q.kp) {
-                const float a = q.gp * (u - q.kp), t = tanhf(a), d = 1.0f - t * t;
-                s = q.ap * t + q.bp;
-                sp = (1.0f - q.bp) * d;
-                if (par) {
-                    acc[2] += G * (a * d - t);
-                    acc[5] += G * (skp * (1.0f - t * rgp) - sp);
-                }
-            } else if (u < -q.kn) {
-                const float a = q.gn * (u + q.kn), t = tanhf(a), d = 1.0f - t * t;
-                s = q.an * t + q.bn;
-                sp = (1.0f + q.bn) * d;
-                if (par) {
-                    acc[3] += G * (a * d - t);
-                    acc[4] += G * (sp - skn * (1.0f + t * rgn));
-                }
-            } else {
-                s = tanhf(u);
-                sp = 1.0f - s * s;
-            }
-            go[j] = G * sp * q.pre;
-            if (par) {
-                acc[0] += G * (sp * u - inv * s);
-                acc[1] += G * s;
-            }
-        }
-    } else {
-        // k outermost, unrolled to the bound: the recurrences' state and the sums stay in registers.  Chebyshev: T_k and
-        // U_(k-1) by the same three-term recurrence (T_k' = k U_(k-1)), started one step early so that k = 1 needs no case.
-        float u[NV], G[NV], sp[NV], t0[NV], t1[NV], v0[NV], v1[NV];
-        float a0 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            u[j] = (xs[j] - q.dc) * q.pre;
-            G[j] = gs[j] * q.post;
-            sp[j] = 0.0f;
-            t0[j] = u[j]; t1[j] = 1.0f;      // T_(-1) = T_1 = u, T_0 = 1   (power: t1 = u^(k-1))
-            v0[j] = -1.0f; v1[j] = 0.0f;     // U_(-2) = -1, U_(-1) = 0
-            a0 += G[j];
-        }
-        if (par) acc[2] += a0;               // (times f(1) when the partials are written)
-#pragma unroll
-        for (int k = 1; k < WS_MAX_K; ++k) {
-            if (k < K) {
-                const float wk = q.w[k];
-                float a = 0.0f;
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    float B, Bp;
-                    if (MODE == GFX_WS_POWER) {
-                        Bp = (float)k * t1[j];
-                        B = t1[j] * u[j];
-                        t1[j] = B;
-                    } else {
-                        B = 2.0f * u[j] * t1[j] - t0[j];
-                        const float U = 2.0f * u[j] * v1[j] - v0[j];
-                        t0[j] = t1[j]; t1[j] = B;
-                        v0[j] = v1[j]; v1[j] = U;
-                        Bp = (float)k * U;
-                    }
-                    float f = B, df = 1.0f;
-                    if (use_tanh) {
-                        f = tanhf(B);
-                        df = 1.0f - f * f;
-                    }
-                    sp[j] += wk * df * Bp;
-                    a += G[j] * f;
-                }
-                if (par) acc[2 + k] += a;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            go[j] = G[j] * sp[j] * q.pre;
-            if (par) acc[0] += G[j] * sp[j] * u[j];
-        }
-    }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 template <int MODE>
@@ -512,53 +310,6 @@ __global__ __launch_bounds__(256) void ws_sub_mean_kernel(float* __restrict__ gx
             for (int64_t n = n0; n < L; n += nthr) outr[n] -= m;
         }
     }
-}
-
-// [lo, hi) in floats that a mapped (R, C, L) signal covers (strides >= 0)
-static inline void map_span(const float* p, const gfx_rowmap_t& m, int64_t R, int64_t C, int64_t L, const float*& lo,
-                            const float*& hi) {
-    const int64_t nin = R < m.inner ? R : m.inner;
-    lo = p;
-    hi = p + ((R - 1) / m.inner) * m.stride_outer + (nin - 1) * m.stride_inner + (C - 1) * m.stride_ch + L;
-}
-
-// Is `delta` a sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on (strides sorted, largest first)?
-static bool ws_reachable(int64_t delta, const int64_t (*dims)[2], int nd, int i) {
-    if (i == nd) return delta == 0;
-    const int64_t st = dims[i][0], n = dims[i][1], qd = delta / st;
-    for (int64_t c = qd; c <= qd + 1; ++c) {
-        if (c >= n) continue;
-        const int64_t rest = delta - c * st;
-        if (ws_reachable(rest < 0 ? -rest : rest, dims, nd, i + 1)) return true;
-    }
-    return false;
-}
-
-// Do two mapped signals share an element?  Exact for two views with the same positive strides (two node ranges of one
-// render buffer interleave in memory without touching), the covered ranges otherwise.
-static bool ws_overlap(const float* a, const gfx_rowmap_t& am, const float* b, const gfx_rowmap_t& bm, int64_t R, int64_t C,
-                       int64_t L) {
-    const float *alo, *ahi, *blo, *bhi;
-    map_span(a, am, R, C, L, alo, ahi);
-    map_span(b, bm, R, C, L, blo, bhi);
-    if (!(alo < bhi && blo < ahi)) return false;
-    const int64_t nin = R < am.inner ? R : am.inner, nout = (R + am.inner - 1) / am.inner;
-    const bool same = am.inner == bm.inner && am.stride_outer == bm.stride_outer && am.stride_inner == bm.stride_inner &&
-                      am.stride_ch == bm.stride_ch && (nout == 1 || am.stride_outer > 0) &&
-                      (nin == 1 || am.stride_inner > 0) && (C == 1 || am.stride_ch > 0) && R % am.inner == 0;
-    if (!same) return true;
-    int64_t dims[4][2] = {{am.stride_outer, nout}, {am.stride_inner, nin}, {am.stride_ch, C}, {1, L}};
-    int nd = 0;
-    for (int i = 0; i < 4; ++i)
-        if (dims[i][1] > 1) { dims[nd][0] = dims[i][0]; dims[nd][1] = dims[i][1]; ++nd; }
-    for (int i = 1; i < nd; ++i)                       // insertion sort, largest stride first
-        for (int j = i; j > 0 && dims[j][0] > dims[j - 1][0]; --j) {
-            const int64_t s0 = dims[j][0], s1 = dims[j][1];
-            dims[j][0] = dims[j - 1][0]; dims[j][1] = dims[j - 1][1];
-            dims[j - 1][0] = s0; dims[j - 1][1] = s1;
-        }
-    const int64_t delta = a > b ? a - b : b - a;
-    return ws_reachable(delta, dims, nd, 0);
 }
 
 }  // namespace gfx

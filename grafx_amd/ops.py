@@ -1298,6 +1298,97 @@ def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, 
     return gx, grads
 
 
+# ----------------------------------------------------------------------------------------- oversampled waveshapers
+OVERSAMPLE_MAX_FACTOR = 16
+OVERSAMPLE_MAX_TAPS = 1024
+
+
+def oversampled_waveshaper_tile(factor):
+    """Base-rate samples of a row-channel that one workgroup of the oversampled kernels produces (os_tile in
+    csrc/oversampled.hip): about 4096 / factor, a multiple of 64."""
+    if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= OVERSAMPLE_MAX_FACTOR:
+        raise ValueError(f"oversampled_waveshaper_tile: factor={factor!r} must be an integer in 1..{OVERSAMPLE_MAX_FACTOR}")
+    return 4096 // factor // 64 * 64
+
+
+def _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn):
+    """The factor, the two filters and their offsets, checked before anything is allocated."""
+    oversampled_waveshaper_tile(factor)
+    for name, h, offset in (("h_up", h_up, offset_up), ("h_dn", h_dn, offset_dn)):
+        if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be a float32 tensor on the GPU")
+        if h.ndim != 1 or not 1 <= h.numel() <= OVERSAMPLE_MAX_TAPS:
+            raise ValueError(f"{what}: {name} must hold 1..{OVERSAMPLE_MAX_TAPS} taps in one dimension, got {tuple(h.shape)}")
+        if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset < h.numel():
+            raise ValueError(f"{what}: the offset {offset!r} of {name} must be an integer in 0..N-1={h.numel() - 1}")
+
+
+@_on_device
+def oversampled_waveshaper(x, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain=None, log_post_gain=None, p0=None,
+                           p1=None, use_tanh=False, inverse_post_gain=False, remove_dc=False, out=None, dc=None,
+                           return_dc=False):
+    """:func:`waveshaper` at ``factor`` times the rate in one fused pass (gfx_oversampled_waveshaper_f32): x minus its mean is
+    interpolated by ``h_up`` (u[p] = sum_k xc[k] h_up[p + offset_up - k factor]), shaped, zero outside [0, factor L), and
+    decimated by ``h_dn`` (y[m] = sum_p v[p] h_dn[m factor + offset_dn - p]); the high-rate signals never reach memory.
+    ``h_up``, ``h_dn``: 1..1024 float32 taps on the GPU each, shared by every row; ``factor`` in 1..16.  Everything else as
+    :func:`waveshaper`, except that ``out`` may never share memory with ``x``: tiles read each other's halos.  Equal bits
+    from call to call; a row's result does not depend on the other rows."""
+    what = "oversampled_waveshaper"
+    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
+    _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn)
+    xmap, R, C, L = rowmap(x)
+    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, dc, h_up, h_dn))
+    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
+    pin = _Pin()
+    with _timed("oversampled_waveshaper_kernel", 8 * R * C * L):
+        check(
+            lib().gfx_oversampled_waveshaper_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, factor, pin(h_up), h_up.numel(),
+                                                 offset_up, pin(h_dn), h_dn.numel(), offset_dn, mode, int(use_tanh),
+                                                 int(inverse_post_gain), *(_ptr(v) for v in params.values()), K, _ptr(dc),
+                                                 _stream()),
+            "gfx_oversampled_waveshaper_f32",
+        )
+    return (out, dc) if return_dc else out
+
+
+@_on_device
+def oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain=None, log_post_gain=None,
+                               p0=None, p1=None, use_tanh=False, inverse_post_gain=False, remove_dc=False, dc=None, out=None,
+                               want=WS_GRADS):
+    """Backward of :func:`oversampled_waveshaper` in one fused pass (gfx_oversampled_waveshaper_bwd_f32) -> (gx, grads), with
+    the arguments and results of :func:`waveshaper_bwd`; the taps get no gradient."""
+    what = "oversampled_waveshaper_bwd"
+    _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
+    _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn)
+    xmap, R, C, L = rowmap(x)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    unknown = set(want) - set(WS_GRADS)
+    if unknown:
+        raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
+    gx, gxmap = None, xmap
+    if "x" in want or out is not None:
+        dest = _output(out, (R, C, L), x.device, what, apart=(x, gy, dc, h_up, h_dn))
+        if "x" in want:
+            gx, gxmap = dest
+    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
+    grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
+    pin = _Pin()
+    ws = pin.workspace((bool(grads) or (gx is not None and dc is not None))
+                       and lib().gfx_oversampled_waveshaper_bwd_ws_bytes(R, C, L, K, factor), x.device)
+    with _timed("oversampled_waveshaper_bwd_kernel", (8 if gx is None else 12) * R * C * L):
+        check(
+            lib().gfx_oversampled_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, factor, pin(h_up), h_up.numel(),
+                                                     offset_up, pin(h_dn), h_dn.numel(), offset_dn, mode, int(use_tanh),
+                                                     int(inverse_post_gain), *(_ptr(v) for v in params.values()), K,
+                                                     _ptr(dc), _ptr(gx), gxmap, *(_ptr(grads.get(k)) for k in params), *ws,
+                                                     _stream()),
+            "gfx_oversampled_waveshaper_bwd_f32",
+        )
+    return gx, grads
+
+
 # ----------------------------------------------------------------------------------------- reverb IR
 @_on_device
 def istft_basis(window):

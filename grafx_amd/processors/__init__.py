@@ -30,6 +30,7 @@ from .filter import (
     PeakingFilter,
     StateVariableFilter,
 )
-from .nonlinear import ChebyshevDistortion, PiecewiseTanhDistortion, PowerDistortion, TanhDistortion
+from .nonlinear import (ChebyshevDistortion, PiecewiseTanhDistortion, PowerDistortion, TanhDistortion,
+                        oversampling_filters)
 from .reverb import FilteredNoiseShapingReverb, STFTMaskedNoiseReverb
 from .stereo import MidSideToStereo, MonoToStereo, SideGainImager, StereoGain, StereoToMidSide

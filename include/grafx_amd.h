@@ -679,6 +679,38 @@ int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, g
                            float* gx, gfx_rowmap_t omap, float* g_log_pre_gain, float* g_log_post_gain, float* g_p0,
                            float* g_p1, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- oversampled (anti-aliased) waveshapers: interpolate by `factor`, shape, decimate, in one tile kernel ----
+ * For every row-channel, with F = factor, xc = x - dc inside [0, L) and zero outside, taps zero outside [0, N):
+ *   u[p] = sum_k xc[k] h_up[p + offset_up - k F]          0 <= p < F L
+ *   v[p] = post s(pre u[p])                               0 <= p < F L, and zero outside (not s(0))
+ *   y[m] = sum_p v[p] h_dn[m F + offset_dn - p]           0 <= m < L
+ * s, pre, post, the modes and their parameters exactly those of gfx_waveshaper_f32; h_up and h_dn are device arrays
+ * shared by every row.  The high-rate signals exist only in LDS: 8 bytes of traffic per sample.  y is addressed through its
+ * own row map and may not share memory with x (tiles read each other's halos of x).
+ * gfx_oversampled_waveshaper_bwd_f32 is the adjoint, with the outputs, the workspace rule and the refusals of
+ * gfx_waveshaper_bwd_f32: gx is the input gradient (minus its mean per row-channel with dc), the parameter gradients are
+ * the row sums of that entry taken over the F L high-rate samples, stored per tile and added in double in a fixed order
+ * (no atomics, equal bits from run to run).  The taps get no gradient.
+ *   gfx_oversampled_waveshaper_bwd_ws_bytes = 4 (R NS C nt + R C nt + R C),  nt = ceil(L / tile(factor)),
+ *   NS = 2 + K (polynomial) or 6 (K = 0);  0 for a bad argument.
+ * GFX_EINVAL before any launch: factor outside 1 .. 16, N_up or N_dn outside 1 .. 1024, an offset outside 0 .. N - 1, a null
+ * filter, everything the waveshaper entries refuse, more than 2^31 - 1 workgroups (row-channels times tiles), a row map with
+ * a negative stride, an output that overlaps an input.  A workspace that is too small is GFX_ENOSPC. */
+int gfx_oversampled_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, int64_t R, int64_t C,
+                                   int64_t L, int64_t factor, const float* h_up, int64_t N_up, int64_t offset_up,
+                                   const float* h_dn, int64_t N_dn, int64_t offset_dn, int mode, int use_tanh,
+                                   int inverse_post_gain, const float* log_pre_gain, const float* log_post_gain,
+                                   const float* p0, const float* p1, int64_t K, const float* dc, void* stream);
+size_t gfx_oversampled_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K, int64_t factor);
+int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R,
+                                       int64_t C, int64_t L, int64_t factor, const float* h_up, int64_t N_up,
+                                       int64_t offset_up, const float* h_dn, int64_t N_dn, int64_t offset_dn, int mode,
+                                       int use_tanh, int inverse_post_gain, const float* log_pre_gain,
+                                       const float* log_post_gain, const float* p0, const float* p1, int64_t K,
+                                       const float* dc, float* gx, gfx_rowmap_t omap, float* g_log_pre_gain,
+                                       float* g_log_post_gain, float* g_p0, float* g_p1, void* ws, size_t ws_bytes,
+                                       void* stream);
+
 /* ---- multi-resolution STFT magnitude loss, one resolution per call ------------------------
  * replaces the call site of a training step's loss: torch.stft of the prediction and of the target, their magnitudes
  * and logs, and autograd through all of them.  For rows p = pred[r], t = target[r] of L samples,
