@@ -1,7 +1,9 @@
 """What every wrapper of :mod:`grafx_amd.ops` goes through before its launch: the device and stream plumbing, the
 per-launch timing hook, and the checks of the tensors whose pointers are passed.  The kernels trust their sizes, and a
 RowMap carries strides only, so a destination, a carried state or a workspace is checked or made here, once, and
-nowhere else."""
+nowhere else: :func:`_output`, :func:`_state` and :func:`_workspace`, all on the aliasing rule of :func:`_apart`.  The
+small checks more than one wrapper needs are here too: :func:`_expect` (a shape), :func:`_int_in` (an integer in a range),
+:func:`_taps` (shared filter taps) and :func:`_want` (the gradients asked of a backward entry)."""
 import contextvars
 import functools
 
@@ -249,6 +251,44 @@ def _state(z, shape, what, name):
         got = f"{tuple(z.shape)} {z.dtype} on {z.device}" if isinstance(z, torch.Tensor) else type(z).__name__
         raise ValueError(f"{what}: {name} must be a contiguous float32 GPU tensor of shape {tuple(shape)}, got {got}")
     return z
+
+
+def _workspace(what, ws, nbytes, device, pin, apart, align=1):
+    """The (pointer, byte count) pair of a launch's workspace.  Without ``ws``: what ``pin.workspace(nbytes, device)``
+    makes.  A caller's ``ws`` is held to the aliasing rule against ``apart`` (:func:`_apart`: what the call reads and
+    whatever else it writes), then to its form: contiguous uint8 on ``device``, at least ``nbytes`` of them, at an address
+    that is a multiple of ``align`` -- the library answers a bare error code for a short or misaligned workspace, and
+    takes a pointer to host memory as it comes.  Called where the workspace is made, the last thing before the launch: a
+    refused ``ws`` has cost the call's own allocations, and none of its kernels has run."""
+    if ws is None:
+        return pin.workspace(nbytes, device)
+    _apart(what, "ws", ws, apart)
+    if ws.device != device or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % align:
+        aligned = f", {align}-byte aligned" if align > 1 else ""
+        raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on {device}{aligned}")
+    return ws.data_ptr(), ws.numel()
+
+
+def _int_in(what, name, v, lo, hi):
+    """An integer argument that reaches the library as it is: an int (no bool, no float that happens to be whole) in
+    ``lo`` .. ``hi``."""
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{what}: {name}={v!r} must be an integer in {lo}..{hi}")
+
+
+def _taps(what, name, h, max_taps):
+    """Filter taps every row shares: a one-dimensional float32 tensor on the GPU of 1 .. ``max_taps`` values."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32:
+        raise TypeError(f"{what}: {name} must be a float32 tensor on the GPU")
+    if h.ndim != 1 or not 1 <= h.numel() <= max_taps:
+        raise ValueError(f"{what}: {name} must hold 1..{max_taps} taps in one dimension, got {tuple(h.shape)}")
+
+
+def _want(what, want, known):
+    """The gradients a backward entry is asked for are some of the ones it knows."""
+    unknown = set(want) - set(known)
+    if unknown:
+        raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {known})")
 
 
 def _row_chunks(rows, limit):

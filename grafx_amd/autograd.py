@@ -620,6 +620,47 @@ class DynamicsFn(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+def _waveshaper_forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc, factor=None,
+                        filters=None):
+    """Forward of WaveshaperFn and, with ``factor`` and ``filters`` = (h_up, offset_up, h_dn, offset_dn), of
+    OversampledWaveshaperFn."""
+    four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+    if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+        x = x.contiguous()
+    rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+    flags = dict(use_tanh=use_tanh, inverse_post_gain=inverse_post_gain, remove_dc=remove_dc)
+    if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
+        y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+        dc = ops.row_mean(x) if remove_dc else None
+    elif filters is None:
+        y, dc = ops.waveshaper(x, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, return_dc=True, **flags)
+    else:
+        y, dc = ops.oversampled_waveshaper(x, mode, factor, *filters, log_pre_gain, log_post_gain, p0=p0, p1=p1,
+                                           return_dc=True, **flags)
+    ctx.save_for_backward(x, log_pre_gain, log_post_gain, p0, p1, dc, *(() if filters is None else filters[0::2]))
+    ctx.cfg = (mode, flags, None if filters is None else (factor, *filters[1::2]))
+    return y.view(x.shape) if four else y
+
+
+def _waveshaper_backward(ctx, gy):
+    """Backward of the same two nodes -> the gradients of x and the four parameters."""
+    x, log_pre_gain, log_post_gain, p0, p1, dc, *taps = ctx.saved_tensors
+    mode, flags, oversampling = ctx.cfg
+    if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+        gy = gy.contiguous()
+    want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
+    shaper = dict(flags, p0=p0, p1=p1, dc=dc, out=_sink_for(x) if "x" in want else None, want=want)
+    if oversampling is None:
+        gx, grads = ops.waveshaper_bwd(x, gy, mode, log_pre_gain, log_post_gain, **shaper)
+    else:
+        (h_up, h_dn), (factor, offset_up, offset_dn) = taps, oversampling
+        gx, grads = ops.oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain,
+                                                   log_post_gain, **shaper)
+    like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
+    return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain), like("log_post_gain", log_post_gain),
+            like("p0", p0), like("p1", p1))
+
+
 class WaveshaperFn(torch.autograd.Function):
     """The memoryless distortions (nonlinear.py:46-79, 120-175, 210-233, 270-307) as one autograd node: forward is the
     streaming inference kernel, backward ONE streaming pass over x and dL/dy (gfx_waveshaper_bwd_f32) that leaves the input
@@ -628,34 +669,12 @@ class WaveshaperFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc):
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
-        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
-            dc = ops.row_mean(x) if remove_dc else None
-        else:
-            y, dc = ops.waveshaper(x, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
-                                   inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, return_dc=True)
-        ctx.save_for_backward(x, log_pre_gain, log_post_gain, p0, p1, dc)
-        ctx.cfg = (mode, use_tanh, inverse_post_gain, remove_dc)
-        return y.view(x.shape) if four else y
+        return _waveshaper_forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, log_pre_gain, log_post_gain, p0, p1, dc = ctx.saved_tensors
-        mode, use_tanh, inverse_post_gain, remove_dc = ctx.cfg
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
-        want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
-        gx, grads = ops.waveshaper_bwd(x, gy, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
-                                       inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, dc=dc,
-                                       out=_sink_for(x) if "x" in want else None, want=want)
-        like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
-        return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain),
-                like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None)
+        return (*_waveshaper_backward(ctx, gy), None, None, None, None)
 
 
 class OversampledWaveshaperFn(torch.autograd.Function):
@@ -666,39 +685,15 @@ class OversampledWaveshaperFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc, factor, filters):
-        h_up, offset_up, h_dn, offset_dn = filters
-        if h_up.requires_grad or h_dn.requires_grad:
+        if filters[0].requires_grad or filters[2].requires_grad:
             raise ValueError("OversampledWaveshaperFn: the taps get no gradient (detach them)")
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
-        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
-            dc = ops.row_mean(x) if remove_dc else None
-        else:
-            y, dc = ops.oversampled_waveshaper(x, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain, log_post_gain,
-                                               p0=p0, p1=p1, use_tanh=use_tanh, inverse_post_gain=inverse_post_gain,
-                                               remove_dc=remove_dc, return_dc=True)
-        ctx.save_for_backward(x, log_pre_gain, log_post_gain, p0, p1, dc, h_up, h_dn)
-        ctx.cfg = (mode, use_tanh, inverse_post_gain, remove_dc, factor, offset_up, offset_dn)
-        return y.view(x.shape) if four else y
+        return _waveshaper_forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_tanh, inverse_post_gain, remove_dc,
+                                   factor, filters)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, log_pre_gain, log_post_gain, p0, p1, dc, h_up, h_dn = ctx.saved_tensors
-        mode, use_tanh, inverse_post_gain, remove_dc, factor, offset_up, offset_dn = ctx.cfg
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
-        want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
-        gx, grads = ops.oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain,
-                                                   log_post_gain, p0=p0, p1=p1, use_tanh=use_tanh,
-                                                   inverse_post_gain=inverse_post_gain, remove_dc=remove_dc, dc=dc,
-                                                   out=_sink_for(x) if "x" in want else None, want=want)
-        like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
-        return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain),
-                like("log_post_gain", log_post_gain), like("p0", p0), like("p1", p1), None, None, None, None, None, None)
+        return (*_waveshaper_backward(ctx, gy), None, None, None, None, None, None)
 
 
 class StftReverbIrFn(torch.autograd.Function):
@@ -901,6 +896,35 @@ class BiquadCascadeStateFn(torch.autograd.Function):
                                       want=want)
 
 
+def _loss_calls(hops, banked, tensors):
+    """(window, hop, None or (fb, bands)) per resolution out of the flat tensor list of the two STFT loss nodes."""
+    windows, rest = tensors[:len(hops)], list(tensors[len(hops):])
+    return [(w, hop, (rest.pop(0), tuple(rest.pop(0) for _ in range(4))) if has else None)
+            for w, hop, has in zip(windows, hops, banked)]
+
+
+def _loss_sums_forward(ctx, pred, target, eps, hops, banked, tensors):
+    """Forward of StftBandLossSumsFn, and of StftLossSumsFn with no resolution banked."""
+    ctx.save_for_backward(pred, target, *tensors)
+    ctx.eps, ctx.hops, ctx.banked = eps, tuple(hops), tuple(banked)
+    return torch.stack([ops.stft_loss_sums(pred, target, w, hop, eps) if bank is None
+                        else ops.stft_band_loss_sums(pred, target, w, hop, *bank, eps)
+                        for w, hop, bank in _loss_calls(ctx.hops, ctx.banked, tensors)], 1)
+
+
+def _loss_sums_backward(ctx, g):
+    """Backward of the same two nodes -> the gradient of pred."""
+    pred, target, *tensors = ctx.saved_tensors
+    gp = _sink_for(pred)
+    for i, (w, hop, bank) in enumerate(_loss_calls(ctx.hops, ctx.banked, tensors)):
+        coef = g[:, i, (0, 2, 3)].contiguous()
+        if bank is None:
+            gp = ops.stft_loss_bwd(pred, target, w, hop, coef, ctx.eps, out=gp, accumulate=i > 0)
+        else:
+            gp = ops.stft_band_loss_bwd(pred, target, w, hop, *bank, coef, ctx.eps, out=gp, accumulate=i > 0)
+    return gp
+
+
 class StftLossSumsFn(torch.autograd.Function):
     """sums[r, i] = (A, B, E, D) of resolution i = (windows[i], hops[i]) for every row of ``pred`` (..., L) against
     ``target`` (ops.stft_loss_sums, one call per resolution) -> (R, n_res, 4).  The tape holds pred, target and the windows
@@ -912,18 +936,12 @@ class StftLossSumsFn(torch.autograd.Function):
     def forward(ctx, pred, target, eps, hops, *windows):
         if ctx.needs_input_grad[1]:
             raise ValueError("StftLossSumsFn: the target gets no gradient (detach it)")
-        ctx.save_for_backward(pred, target, *windows)
-        ctx.eps, ctx.hops = eps, tuple(hops)
-        return torch.stack([ops.stft_loss_sums(pred, target, w, hop, eps) for w, hop in zip(windows, hops)], 1)
+        return _loss_sums_forward(ctx, pred, target, eps, hops, (False,) * len(hops), windows)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        pred, target, *windows = ctx.saved_tensors
-        gp = _sink_for(pred)
-        for i, (w, hop) in enumerate(zip(windows, ctx.hops)):
-            gp = ops.stft_loss_bwd(pred, target, w, hop, g[:, i, (0, 2, 3)].contiguous(), ctx.eps, out=gp, accumulate=i > 0)
-        return (gp, None, None, None, *(None for _ in windows))
+        return (_loss_sums_backward(ctx, g), None, None, None, *(None for _ in ctx.saved_tensors[2:]))
 
 
 class StftBandLossSumsFn(torch.autograd.Function):
@@ -935,36 +953,17 @@ class StftBandLossSumsFn(torch.autograd.Function):
     their bands -- nothing of a spectrogram's size.  The filterbanks get no gradient."""
 
     @staticmethod
-    def _calls(hops, banked, tensors):
-        """(window, hop, None or (fb, bands)) per resolution out of the flat tensor list."""
-        windows, rest = tensors[:len(hops)], list(tensors[len(hops):])
-        return [(w, hop, (rest.pop(0), tuple(rest.pop(0) for _ in range(4))) if has else None)
-                for w, hop, has in zip(windows, hops, banked)]
-
-    @staticmethod
     def forward(ctx, pred, target, eps, hops, banked, *tensors):
         if ctx.needs_input_grad[1]:
             raise ValueError("StftBandLossSumsFn: the target gets no gradient (detach it)")
         if any(ctx.needs_input_grad[5:]):
             raise ValueError("StftBandLossSumsFn: windows and filterbanks get no gradient (detach them)")
-        ctx.save_for_backward(pred, target, *tensors)
-        ctx.eps, ctx.hops, ctx.banked = eps, tuple(hops), tuple(banked)
-        return torch.stack([ops.stft_loss_sums(pred, target, w, hop, eps) if bank is None
-                            else ops.stft_band_loss_sums(pred, target, w, hop, *bank, eps)
-                            for w, hop, bank in StftBandLossSumsFn._calls(ctx.hops, ctx.banked, tensors)], 1)
+        return _loss_sums_forward(ctx, pred, target, eps, hops, banked, tensors)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        pred, target, *tensors = ctx.saved_tensors
-        gp = _sink_for(pred)
-        for i, (w, hop, bank) in enumerate(StftBandLossSumsFn._calls(ctx.hops, ctx.banked, tensors)):
-            coef = g[:, i, (0, 2, 3)].contiguous()
-            if bank is None:
-                gp = ops.stft_loss_bwd(pred, target, w, hop, coef, ctx.eps, out=gp, accumulate=i > 0)
-            else:
-                gp = ops.stft_band_loss_bwd(pred, target, w, hop, *bank, coef, ctx.eps, out=gp, accumulate=i > 0)
-        return (gp, None, None, None, None, *(None for _ in tensors))
+        return (_loss_sums_backward(ctx, g), None, None, None, None, *(None for _ in ctx.saved_tensors[2:]))
 
 
 class KWeightEnergyFn(torch.autograd.Function):

@@ -203,24 +203,6 @@ __global__ __launch_bounds__(THREADS) void stft_band_loss_sums_kernel(const floa
     }
 }
 
-// a row's partials in their order, in double (stft_loss_finish_kernel's text: a kernel of another file cannot be launched
-// from this one, and the plain loss's object stays what it was)
-__global__ __launch_bounds__(THREADS) void stft_band_loss_finish_kernel(const float4* __restrict__ partials,
-                                                                        float4* __restrict__ sums, int64_t R, int chunks) {
-    const int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-    if (row >= R) return;
-    double A = 0.0, B = 0.0, E = 0.0, D = 0.0;
-    const float4* q = partials + row * chunks;
-    for (int c = 0; c < chunks; ++c) {
-        const float4 v = q[c];
-        A += v.x;
-        B += v.y;
-        E += v.z;
-        D += v.w;
-    }
-    sums[row] = make_float4((float)A, (float)B, (float)E, (float)D);
-}
-
 // G of bin k of frame f from the band gradients gm of the frame: P scaled by sum_m W[m, k] g_m / |P|, nothing where the
 // bin is clamped or no row covers it
 template <int LOGN>
@@ -369,12 +351,11 @@ int gfx_stft_band_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const floa
     using namespace gfx::stftloss;
     Geometry g;
     int logn;
-    if (!pred || !target || !window || !fb || !row_lo || !row_hi || !sums || !ws || R <= 0 || !(eps > 0.0f) ||
-        pmap.inner <= 0 || tmap.inner <= 0 || !geometry(g, logn, L, n_fft, hop) || n_bins < 1 || n_bins > n_fft / 2 + 1)
-        return GFX_EINVAL;
-    const int64_t chunks = chunks_of(g, n_fft);
-    if (R > 0x7fffffffLL / chunks || ((uintptr_t)ws & 15)) return GFX_EINVAL;
-    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;
+    int64_t chunks;
+    const int rc =
+        check_entry(pred && target && window && fb && row_lo && row_hi && sums && n_bins >= 1 && n_bins <= n_fft / 2 + 1, pmap,
+                    tmap, R, L, n_fft, hop, eps, ws, ws_bytes, g, logn, chunks);
+    if (rc != GFX_OK) return rc;
     const Bands bd = {fb, row_lo, row_hi, nullptr, nullptr, (int)n_bins};
     hipStream_t s = (hipStream_t)stream;
 #define GFX_LAUNCH(LOGN)                                                                                                       \
@@ -382,8 +363,7 @@ int gfx_stft_band_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const floa
                        pmap, target, tmap, window, bd, (float4*)ws, g, (int)chunks, eps)
     GFX_STFT_LOSS_BY_SIZE(logn, GFX_LAUNCH)
 #undef GFX_LAUNCH
-    hipLaunchKernelGGL(stft_band_loss_finish_kernel, dim3((unsigned)((R + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
-                       (const float4*)ws, (float4*)sums, R, (int)chunks);
+    finish_sums(ws, sums, R, chunks, s);
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
@@ -395,13 +375,11 @@ int gfx_stft_band_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float
     using namespace gfx::stftloss;
     Geometry g;
     int logn;
-    if (!pred || !target || !window || !fb || !row_lo || !row_hi || !col_lo || !col_hi || !coef || !gpred || !ws || R <= 0 ||
-        !(eps > 0.0f) || pmap.inner <= 0 || tmap.inner <= 0 || gmap.inner <= 0 || !geometry(g, logn, L, n_fft, hop) ||
-        n_bins < 1 || n_bins > n_fft / 2 + 1)
-        return GFX_EINVAL;
-    const int64_t segs = (L + SEG - 1) / SEG, chunks = chunks_of(g, n_fft);
-    if (R > 0x7fffffffLL / segs || R > 0x7fffffffLL / chunks) return GFX_EINVAL;
-    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;      // one buffer serves both calls of a step
+    int64_t chunks, segs;
+    const int rc = check_entry(pred && target && window && fb && row_lo && row_hi && col_lo && col_hi && coef && gpred &&
+                                   gmap.inner > 0 && n_bins >= 1 && n_bins <= n_fft / 2 + 1,
+                               pmap, tmap, R, L, n_fft, hop, eps, ws, ws_bytes, g, logn, chunks, &segs);
+    if (rc != GFX_OK) return rc;
     const Bands bd = {fb, row_lo, row_hi, col_lo, col_hi, (int)n_bins};
 #define GFX_LAUNCH(LOGN)                                                                                                 \
     hipLaunchKernelGGL(stft_band_loss_bwd_kernel<LOGN>, dim3((unsigned)(R * segs)), dim3(THREADS), lds_bytes(n_fft),       \

@@ -112,6 +112,11 @@ __global__ __launch_bounds__(THREADS) void stft_loss_finish_kernel(const float4*
     sums[row] = make_float4((float)A, (float)B, (float)E, (float)D);
 }
 
+void finish_sums(const void* partials, float* sums, int64_t R, int64_t chunks, hipStream_t stream) {
+    hipLaunchKernelGGL(stft_loss_finish_kernel, dim3((unsigned)((R + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream,
+                       (const float4*)partials, (float4*)sums, R, (int)chunks);
+}
+
 // Gather form: the workgroup owns samples [s0, s0 + SEG) of one row, transforms every frame that reaches them -- directly
 // or through the reflection at either end -- and each thread adds, for its own CELLS samples, the windowed inverse of
 // every such frame at the (up to three) padded positions that fold onto the sample.
@@ -228,20 +233,17 @@ int gfx_stft_loss_sums_f32(const float* pred, gfx_rowmap_t pmap, const float* ta
     using namespace gfx::stftloss;
     Geometry g;
     int logn;
-    if (!pred || !target || !window || !sums || !ws || R <= 0 || !(eps > 0.0f) || pmap.inner <= 0 || tmap.inner <= 0 ||
-        !geometry(g, logn, L, n_fft, hop))
-        return GFX_EINVAL;
-    const int64_t chunks = chunks_of(g, n_fft);
-    if (R > 0x7fffffffLL / chunks || ((uintptr_t)ws & 15)) return GFX_EINVAL;
-    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;
+    int64_t chunks;
+    const int rc =
+        check_entry(pred && target && window && sums, pmap, tmap, R, L, n_fft, hop, eps, ws, ws_bytes, g, logn, chunks);
+    if (rc != GFX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
 #define GFX_LAUNCH(LOGN)                                                                                                  \
     hipLaunchKernelGGL(stft_loss_sums_kernel<LOGN>, dim3((unsigned)(R * chunks)), dim3(THREADS), lds_bytes(n_fft), s, pred, \
                        pmap, target, tmap, window, (float4*)ws, g, (int)chunks, eps)
     GFX_STFT_LOSS_BY_SIZE(logn, GFX_LAUNCH)
 #undef GFX_LAUNCH
-    hipLaunchKernelGGL(stft_loss_finish_kernel, dim3((unsigned)((R + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
-                       (const float4*)ws, (float4*)sums, R, (int)chunks);
+    finish_sums(ws, sums, R, chunks, s);
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
@@ -251,12 +253,10 @@ int gfx_stft_loss_bwd_f32(const float* pred, gfx_rowmap_t pmap, const float* tar
     using namespace gfx::stftloss;
     Geometry g;
     int logn;
-    if (!pred || !target || !window || !coef || !gpred || !ws || R <= 0 || !(eps > 0.0f) || pmap.inner <= 0 ||
-        tmap.inner <= 0 || gmap.inner <= 0 || !geometry(g, logn, L, n_fft, hop))
-        return GFX_EINVAL;
-    const int64_t segs = (L + SEG - 1) / SEG, chunks = chunks_of(g, n_fft);
-    if (R > 0x7fffffffLL / segs || R > 0x7fffffffLL / chunks) return GFX_EINVAL;
-    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;      // one buffer serves both calls of a step
+    int64_t chunks, segs;
+    const int rc = check_entry(pred && target && window && coef && gpred && gmap.inner > 0, pmap, tmap, R, L, n_fft, hop, eps,
+                               ws, ws_bytes, g, logn, chunks, &segs);
+    if (rc != GFX_OK) return rc;
 #define GFX_LAUNCH(LOGN)                                                                                               \
     hipLaunchKernelGGL(stft_loss_bwd_kernel<LOGN>, dim3((unsigned)(R * segs)), dim3(THREADS), lds_bytes(n_fft),          \
                        (hipStream_t)stream, pred, pmap, target, tmap, window, coef, gpred, gmap, g, (int)segs, eps, accumulate)

@@ -1,5 +1,6 @@
 // The frame transform of the STFT loss (stft_loss.hip, which describes it) and what its kernels share with the banded
-// loss of stft_band_loss.hip: the LDS image, the sample ring, the radix-2 passes, the per-bin formulas, the geometry.
+// loss of stft_band_loss.hip: the LDS image, the sample ring, the radix-2 passes, the per-bin formulas, the geometry, and on
+// the host the argument check of the four entries and the launch of the one finish kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -281,6 +282,24 @@ static inline int64_t chunks_of(const Geometry& g, int64_t n_fft) {
     const int64_t per = (int64_t)RUN * (SLOTS / n_fft);
     return (g.frames + per - 1) / per;
 }
+
+// What the four entries of the two losses check alike, and the codes they answer in their order.  `own`: the entry's own
+// pointers, row map and band count are in order.  `segs`: the backward's count of segments per row (its grid is limited as
+// well); nullptr for the sums, whose float4 partials need an aligned workspace.  Sets g, logn, chunks and *segs.
+static inline int check_entry(bool own, const gfx_rowmap_t& pmap, const gfx_rowmap_t& tmap, int64_t R, int64_t L,
+                              int64_t n_fft, int64_t hop, float eps, const void* ws, size_t ws_bytes, Geometry& g, int& logn,
+                              int64_t& chunks, int64_t* segs = nullptr) {
+    if (!own || !ws || R <= 0 || !(eps > 0.0f) || pmap.inner <= 0 || tmap.inner <= 0 || !geometry(g, logn, L, n_fft, hop))
+        return GFX_EINVAL;
+    chunks = chunks_of(g, n_fft);
+    if (segs) *segs = (L + SEG - 1) / SEG;
+    if (R > 0x7fffffffLL / chunks || (segs ? R > 0x7fffffffLL / *segs : ((uintptr_t)ws & 15) != 0)) return GFX_EINVAL;
+    if (ws_bytes < (size_t)R * (size_t)chunks * 16) return GFX_ENOSPC;      // one buffer serves both calls of a step
+    return GFX_OK;
+}
+
+// launches stft_loss_finish_kernel (stft_loss.hip): a row's partials summed in their order, in double
+void finish_sums(const void* partials, float* sums, int64_t R, int64_t chunks, hipStream_t stream);
 
 static inline size_t lds_bytes(int64_t n_fft) {
     return (size_t)ZSIZE * sizeof(float2) + (size_t)(n_fft / 2 + (1 << FINE)) * sizeof(float2) + (size_t)n_fft * sizeof(float) +

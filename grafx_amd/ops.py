@@ -12,8 +12,8 @@ from collections import namedtuple
 import torch
 
 from ._lib import RowMap, check, lib
-from ._plumbing import (_apart, _expect, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks, _state,  # noqa: F401
-                        _stream, _timed, profiling, rowmap)
+from ._plumbing import (_apart, _expect, _int_in, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks,  # noqa: F401
+                        _state, _stream, _taps, _timed, _want, _workspace, profiling, rowmap)
 
 
 # The aliasing rule (include/grafx_amd.h): no tensor a call writes shares an element with one it reads, with another it
@@ -1085,11 +1085,6 @@ def biquad_cascade_bwd(x, gy, Bs, As, zi=None, gzf=None, want=BIQUAD_GRADS, out=
         dest = _output(out, (R, Cin, L), x.device, what, apart=(*reads, ws))
         if "x" in want:
             gx, gxmap = dest
-    nbytes = lib().gfx_biquad_cascade_bwd_ws_bytes(R, Cout, K, L)
-    if ws is not None:
-        _apart(what, "ws", ws, reads)
-        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
-            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
     # More than two channels with a broadcast side: the kernel sums a broadcast inside a pair of row-channels, which is a
     # row's channels only when there are two.  The broadcast side goes in expanded instead -- the coefficients copied
     # (parameter-sized), x through a row map with a zero channel stride -- and the channels of the result are added here.
@@ -1107,7 +1102,7 @@ def biquad_cascade_bwd(x, gy, Bs, As, zi=None, gzf=None, want=BIQUAD_GRADS, out=
     gA = torch.empty_like(As) if "As" in want else None
     gzi = torch.empty((R, Cout, K, 2), dtype=torch.float32, device=x.device) if "zi" in want else None
     pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    wsarg = _workspace(what, ws, lib().gfx_biquad_cascade_bwd_ws_bytes(R, Cout, K, L), x.device, pin, reads)
     # x twice (both passes), g once, gx once
     with _timed("biquad_cascade_bwd_kernel", 4 * R * L * (2 * Cin + Cout + (kCin if gx is not None else 0))):
         check(lib().gfx_biquad_cascade_bwd_f32(_ptr(kx), kxmap, _ptr(gy), gmap, _ptr(kgx), kgxmap, _ptr(Bs), _ptr(As), _ptr(zi),
@@ -1173,9 +1168,7 @@ def noise_shaping_ir_bwd(grad_ir, noise, log_decay, log_gain, log_fade_in, z_fad
     for name, t in given.items():
         _expect(t, (R, C, K), f"{what}: {name}")
     _expect(ir, (R, C, ir_len), f"{what}: ir")
-    unknown = set(want) - set(NS_GRADS)
-    if unknown:
-        raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {NS_GRADS})")
+    _want(what, want, NS_GRADS)
     names = [k for k in NS_GRADS if k in want and given[k] is not None]
     if not names:
         raise ValueError(f"{what}: no gradient asked for ({tuple(want)})")
@@ -1185,18 +1178,15 @@ def noise_shaping_ir_bwd(grad_ir, noise, log_decay, log_gain, log_fade_in, z_fad
         if row_gain.numel() != R:
             raise ValueError(f"{what}: {row_gain.numel()} gains for {R} rows")
         row_gain = row_gain.reshape(R).contiguous()
-    nbytes = lib().gfx_noise_shaping_ir_bwd_ws_bytes(min(R, NS_BWD_ROWS), C, K, ir_len)
-    if ws is not None:
-        _apart(what, "ws", ws, (grad_ir, noise, *given.values(), ir, row_gain))
-        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
-            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
+    reads = (grad_ir, noise, *given.values(), ir, row_gain)
     grad_ir = grad_ir.contiguous()
     ir = None if ir is None else ir.contiguous()
     given = {k: None if t is None else t.contiguous() for k, t in given.items()}
     grads = {k: torch.empty((R, C, K), dtype=torch.float32, device=grad_ir.device) for k in names}
     cut = lambda t, r0, n: None if t is None else t[r0:r0 + n]  # noqa: E731
     pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, grad_ir.device)
+    wsarg = _workspace(what, ws, lib().gfx_noise_shaping_ir_bwd_ws_bytes(min(R, NS_BWD_ROWS), C, K, ir_len), grad_ir.device,
+                       pin, reads)
     with _timed("noise_shaping_ir_bwd_kernel", 4 * R * C * ir_len * (1 if ir is None else 2)):
         for r0, n in _row_chunks(R, NS_BWD_ROWS):
             check(
@@ -1242,23 +1232,72 @@ def _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, r
     return params, K, dc
 
 
+def _shape(what, x, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh, inverse_post_gain, remove_dc, out, dc, return_dc,
+           oversampling=None):
+    """The body of :func:`waveshaper` and, with ``oversampling`` = (factor, h_up, offset_up, h_dn, offset_dn), of
+    :func:`oversampled_waveshaper`."""
+    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
+    entry, kernel, taps, extra = "gfx_waveshaper_f32", "waveshaper_kernel", (), lambda pin: ()
+    if oversampling is not None:
+        entry, kernel = "gfx_oversampled_waveshaper_f32", "oversampled_waveshaper_kernel"
+        taps, extra = _oversampling_args(what, *oversampling)
+    xmap, R, C, L = rowmap(x)
+    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, dc, *taps))
+    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
+    pin = _Pin()
+    with _timed(kernel, 8 * R * C * L):
+        check(
+            getattr(lib(), entry)(_ptr(x), xmap, _ptr(out), ymap, R, C, L, *extra(pin), mode, int(use_tanh),
+                                  int(inverse_post_gain), *(_ptr(v) for v in params.values()), K, _ptr(dc), _stream()),
+            entry,
+        )
+    return (out, dc) if return_dc else out
+
+
+def _shape_bwd(what, x, gy, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh, inverse_post_gain, remove_dc, dc, out, want,
+               oversampling=None):
+    """The body of :func:`waveshaper_bwd` and, with ``oversampling`` as for :func:`_shape`, of
+    :func:`oversampled_waveshaper_bwd`."""
+    _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
+    entry, sized, kernel = "gfx_waveshaper_bwd_f32", "gfx_waveshaper_bwd_ws_bytes", "waveshaper_bwd_kernel"
+    factor, taps, extra = (), (), lambda pin: ()
+    if oversampling is not None:
+        entry, sized = "gfx_oversampled_waveshaper_bwd_f32", "gfx_oversampled_waveshaper_bwd_ws_bytes"
+        kernel, factor = "oversampled_waveshaper_bwd_kernel", oversampling[:1]
+        taps, extra = _oversampling_args(what, *oversampling)
+    xmap, R, C, L = rowmap(x)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    _want(what, want, WS_GRADS)
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, C, L), x.device, what, apart=(x, gy, dc, *taps))
+        if "x" in want:
+            gx, gxmap = dest
+    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
+    grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
+    pin = _Pin()
+    ws = pin.workspace((bool(grads) or (gx is not None and dc is not None))
+                       and getattr(lib(), sized)(R, C, L, K, *factor), x.device)
+    with _timed(kernel, (8 if gx is None else 12) * R * C * L):
+        check(
+            getattr(lib(), entry)(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, *extra(pin), mode, int(use_tanh),
+                                  int(inverse_post_gain), *(_ptr(v) for v in params.values()), K, _ptr(dc), _ptr(gx), gxmap,
+                                  *(_ptr(grads.get(k)) for k in params), *ws, _stream()),
+            entry,
+        )
+    return gx, grads
+
+
 @_on_device
 def waveshaper(x, mode, log_pre_gain=None, log_post_gain=None, p0=None, p1=None, use_tanh=False,
                inverse_post_gain=False, remove_dc=False, out=None, dc=None, return_dc=False):
     """Memoryless distortion of every row (see gfx_waveshaper_f32 in the header for the modes).
     ``dc``: the row-channel means of x when the caller already has them (``remove_dc``); ``return_dc``: -> (out, dc), the
     means this call subtracted (None without ``remove_dc``) -- what waveshaper_bwd needs of them."""
-    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
-    xmap, R, C, L = rowmap(x)
-    out, ymap = _output(out, (R, C, L), x.device, "waveshaper", apart=(x, dc))
-    params, K, dc = _waveshaper_args("waveshaper", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
-    with _timed("waveshaper_kernel", 8 * R * C * L):
-        check(
-            lib().gfx_waveshaper_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, mode, int(use_tanh), int(inverse_post_gain),
-                                     *(_ptr(v) for v in params.values()), K, _ptr(dc), _stream()),
-            "gfx_waveshaper_f32",
-        )
-    return (out, dc) if return_dc else out
+    return _shape("waveshaper", x, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh, inverse_post_gain, remove_dc, out, dc,
+                  return_dc)
 
 
 @_on_device
@@ -1270,32 +1309,8 @@ def waveshaper_bwd(x, gy, mode, log_pre_gain=None, log_post_gain=None, p0=None, 
     given is skipped).  ``gx`` is None unless "x" is wanted, else ``out`` (any view of the signal's shape, apart from x, gy
     and dc) or a new (R,C,L) tensor.  ``grads``: {name: (R, n) gradient} of the wanted parameters.
     ``dc``: the means the forward subtracted (``waveshaper(..., return_dc=True)``); recomputed when missing."""
-    _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
-    xmap, R, C, L = rowmap(x)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"waveshaper_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
-    unknown = set(want) - set(WS_GRADS)
-    if unknown:
-        raise ValueError(f"waveshaper_bwd: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, "waveshaper_bwd", apart=(x, gy, dc))
-        if "x" in want:
-            gx, gxmap = dest
-    params, K, dc = _waveshaper_args("waveshaper_bwd", x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
-    grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
-    pin = _Pin()
-    ws = pin.workspace((bool(grads) or (gx is not None and dc is not None)) and lib().gfx_waveshaper_bwd_ws_bytes(R, C, L, K),
-                       x.device)
-    with _timed("waveshaper_bwd_kernel", (8 if gx is None else 12) * R * C * L):
-        check(
-            lib().gfx_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, mode, int(use_tanh), int(inverse_post_gain),
-                                         *(_ptr(v) for v in params.values()), K, _ptr(dc), _ptr(gx), gxmap,
-                                         *(_ptr(grads.get(k)) for k in params), *ws, _stream()),
-            "gfx_waveshaper_bwd_f32",
-        )
-    return gx, grads
+    return _shape_bwd("waveshaper_bwd", x, gy, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh, inverse_post_gain,
+                      remove_dc, dc, out, want)
 
 
 # ----------------------------------------------------------------------------------------- oversampled waveshapers
@@ -1306,21 +1321,18 @@ OVERSAMPLE_MAX_TAPS = 1024
 def oversampled_waveshaper_tile(factor):
     """Base-rate samples of a row-channel that one workgroup of the oversampled kernels produces (os_tile in
     csrc/oversampled.hip): about 4096 / factor, a multiple of 64."""
-    if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= OVERSAMPLE_MAX_FACTOR:
-        raise ValueError(f"oversampled_waveshaper_tile: factor={factor!r} must be an integer in 1..{OVERSAMPLE_MAX_FACTOR}")
+    _int_in("oversampled_waveshaper_tile", "factor", factor, 1, OVERSAMPLE_MAX_FACTOR)
     return 4096 // factor // 64 * 64
 
 
 def _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn):
-    """The factor, the two filters and their offsets, checked before anything is allocated."""
+    """The factor, the two filters and their offsets, checked before anything is allocated -> (the taps, what the oversampled
+    entries take between L and the mode as a function of the launch's ``pin``)."""
     oversampled_waveshaper_tile(factor)
-    for name, h, offset in (("h_up", h_up, offset_up), ("h_dn", h_dn, offset_dn)):
-        if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32:
-            raise TypeError(f"{what}: {name} must be a float32 tensor on the GPU")
-        if h.ndim != 1 or not 1 <= h.numel() <= OVERSAMPLE_MAX_TAPS:
-            raise ValueError(f"{what}: {name} must hold 1..{OVERSAMPLE_MAX_TAPS} taps in one dimension, got {tuple(h.shape)}")
-        if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset < h.numel():
-            raise ValueError(f"{what}: the offset {offset!r} of {name} must be an integer in 0..N-1={h.numel() - 1}")
+    for name, h, offset_name, offset in (("h_up", h_up, "offset_up", offset_up), ("h_dn", h_dn, "offset_dn", offset_dn)):
+        _taps(what, name, h, OVERSAMPLE_MAX_TAPS)
+        _int_in(what, offset_name, offset, 0, h.numel() - 1)
+    return (h_up, h_dn), lambda pin: (factor, pin(h_up), h_up.numel(), offset_up, pin(h_dn), h_dn.numel(), offset_dn)
 
 
 @_on_device
@@ -1333,22 +1345,8 @@ def oversampled_waveshaper(x, mode, factor, h_up, offset_up, h_dn, offset_dn, lo
     ``h_up``, ``h_dn``: 1..1024 float32 taps on the GPU each, shared by every row; ``factor`` in 1..16.  Everything else as
     :func:`waveshaper`, except that ``out`` may never share memory with ``x``: tiles read each other's halos.  Equal bits
     from call to call; a row's result does not depend on the other rows."""
-    what = "oversampled_waveshaper"
-    _require_gpu(x, log_pre_gain, log_post_gain, p0, p1, out, dc)
-    _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn)
-    xmap, R, C, L = rowmap(x)
-    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, dc, h_up, h_dn))
-    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
-    pin = _Pin()
-    with _timed("oversampled_waveshaper_kernel", 8 * R * C * L):
-        check(
-            lib().gfx_oversampled_waveshaper_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, factor, pin(h_up), h_up.numel(),
-                                                 offset_up, pin(h_dn), h_dn.numel(), offset_dn, mode, int(use_tanh),
-                                                 int(inverse_post_gain), *(_ptr(v) for v in params.values()), K, _ptr(dc),
-                                                 _stream()),
-            "gfx_oversampled_waveshaper_f32",
-        )
-    return (out, dc) if return_dc else out
+    return _shape("oversampled_waveshaper", x, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh, inverse_post_gain,
+                  remove_dc, out, dc, return_dc, oversampling=(factor, h_up, offset_up, h_dn, offset_dn))
 
 
 @_on_device
@@ -1357,36 +1355,8 @@ def oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offse
                                want=WS_GRADS):
     """Backward of :func:`oversampled_waveshaper` in one fused pass (gfx_oversampled_waveshaper_bwd_f32) -> (gx, grads), with
     the arguments and results of :func:`waveshaper_bwd`; the taps get no gradient."""
-    what = "oversampled_waveshaper_bwd"
-    _require_gpu(x, gy, log_pre_gain, log_post_gain, p0, p1, out, dc)
-    _oversampling_args(what, factor, h_up, offset_up, h_dn, offset_dn)
-    xmap, R, C, L = rowmap(x)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
-    unknown = set(want) - set(WS_GRADS)
-    if unknown:
-        raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {WS_GRADS})")
-    gx, gxmap = None, xmap
-    if "x" in want or out is not None:
-        dest = _output(out, (R, C, L), x.device, what, apart=(x, gy, dc, h_up, h_dn))
-        if "x" in want:
-            gx, gxmap = dest
-    params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
-    grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
-    pin = _Pin()
-    ws = pin.workspace((bool(grads) or (gx is not None and dc is not None))
-                       and lib().gfx_oversampled_waveshaper_bwd_ws_bytes(R, C, L, K, factor), x.device)
-    with _timed("oversampled_waveshaper_bwd_kernel", (8 if gx is None else 12) * R * C * L):
-        check(
-            lib().gfx_oversampled_waveshaper_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, factor, pin(h_up), h_up.numel(),
-                                                     offset_up, pin(h_dn), h_dn.numel(), offset_dn, mode, int(use_tanh),
-                                                     int(inverse_post_gain), *(_ptr(v) for v in params.values()), K,
-                                                     _ptr(dc), _ptr(gx), gxmap, *(_ptr(grads.get(k)) for k in params), *ws,
-                                                     _stream()),
-            "gfx_oversampled_waveshaper_bwd_f32",
-        )
-    return gx, grads
+    return _shape_bwd("oversampled_waveshaper_bwd", x, gy, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh,
+                      inverse_post_gain, remove_dc, dc, out, want, oversampling=(factor, h_up, offset_up, h_dn, offset_dn))
 
 
 # ----------------------------------------------------------------------------------------- reverb IR
@@ -1487,7 +1457,8 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
     ``grad_ir``: dL/dh (R,2,ir_len).  With ``ir`` and ``row_gain`` (the forward's outputs) h = row_gain * ir, the
     normalised taps; without them h = ir.  The other arguments are the forward's; ``noise_stft`` per row must be the
     noise the forward used.  ``g_gain_env`` is computed when ``gain_env`` is given and ``want_gain_env`` is set.
-    ``ws``: a uint8 workspace of at least ``stft_reverb_ir_bwd_ws_bytes(min(R, 32767), ir_len)`` bytes to reuse."""
+    ``ws``: a uint8 workspace of at least ``stft_reverb_ir_bwd_ws_bytes(min(R, 32767), ir_len)`` bytes to reuse, apart from
+    everything the call reads."""
     _require_gpu(grad_ir, init_lm, delta_lm, gain_env, window, basis, ir, row_gain)
     R, _, ir_len = grad_ir.shape
     n_fft = window.numel()
@@ -1503,11 +1474,10 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
     row_gain = None if row_gain is None else row_gain.contiguous()
     g_init, g_delta = torch.empty_like(init_lm), torch.empty_like(delta_lm)
     g_env = torch.empty_like(gain_env) if (gain_env is not None and want_gain_env) else None
-    nbytes = lib().gfx_stft_reverb_ir_bwd_ws_bytes(min(R, GRID_ROWS_I16_MAX), ir_len)
-    if ws is None:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_ir.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
-        raise ValueError(f"stft_reverb_ir_bwd: the workspace must be {nbytes} contiguous uint8")
+    held = _Pin()                                # (the workspace serves every chunk of rows)
+    wsarg = _workspace("stft_reverb_ir_bwd", ws, lib().gfx_stft_reverb_ir_bwd_ws_bytes(min(R, GRID_ROWS_I16_MAX), ir_len),
+                       grad_ir.device, held, (grad_ir, noise_stft, init_lm, delta_lm, gain_env, window, basis, ir, row_gain,
+                                              g_init, g_delta, g_env))
     cut = lambda t, r0, n: None if t is None else t[r0:r0 + n]  # noqa: E731
     for r0, n in _row_chunks(R, GRID_ROWS_I16_MAX):
         pin = _Pin()
@@ -1516,7 +1486,7 @@ def stft_reverb_ir_bwd(grad_ir, noise_stft, init_lm, delta_lm, gain_env, window,
                                              *noise(r0, n), pin(init_lm[r0:r0 + n]),
                                              pin(delta_lm[r0:r0 + n]), pin(cut(gain_env, r0, n)), pin(window), pin(basis),
                                              _ptr(g_init[r0:r0 + n]), _ptr(g_delta[r0:r0 + n]), _ptr(cut(g_env, r0, n)), n,
-                                             ir_len, n_fft, hop, T, int(ms_to_lr), _ptr(ws), ws.numel(), _stream()),
+                                             ir_len, n_fft, hop, T, int(ms_to_lr), *wsarg, _stream()),
             "gfx_stft_reverb_ir_bwd_f32",
         )
     return g_init, g_delta, g_env
@@ -1555,7 +1525,7 @@ def _loss_rows(t, what, name, view_only=False):
     return t3, RowMap(max(t3.shape[1], 1), t3.stride(0), t3.stride(1), 0)
 
 
-def _loss_args(what, pred, target, window, hop, ws):
+def _loss_args(what, pred, target, window, hop):
     _require_gpu(pred, target, window)
     if pred.shape != target.shape:
         raise ValueError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
@@ -1567,9 +1537,53 @@ def _loss_args(what, pred, target, window, hop, ws):
     if not nbytes:
         raise ValueError(f"{what}: n_fft={n_fft} (the window's length), hop={hop}, L={L} with {B * C} rows is outside the "
                          f"native range: n_fft a power of two in [128, 2048], 1 <= hop <= n_fft, L > n_fft / 2")
-    if ws is not None and (not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes):
-        raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU")
     return p3, pmap, t3, tmap, B * C, L, n_fft, nbytes
+
+
+def _loss_sums(what, pred, target, window, hop, eps, ws, bank=None):
+    """The body of :func:`stft_loss_sums` and, with ``bank`` = (fb, bands), of :func:`stft_band_loss_sums`."""
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop)
+    entry, kernel, banked, bank_args = "gfx_stft_loss_sums_f32", "stft_loss_sums_kernel", (), ()
+    if bank is not None:
+        fb, bands, n_bins = _band_args(what, *bank, n_fft)
+        entry, kernel, banked = "gfx_stft_band_loss_sums_f32", "stft_band_loss_sums_kernel", (fb, *bands)
+        bank_args = (_ptr(fb), _ptr(bands[0]), _ptr(bands[1]), n_bins)
+    sums = torch.empty((R, 4), dtype=torch.float32, device=pred.device)
+    pin = _Pin()
+    wsarg = _workspace(what, ws, nbytes, pred.device, pin, (p3, t3, window, *banked), align=16)
+    with _timed(kernel, 4 * R * L * 2):
+        check(getattr(lib(), entry)(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), *bank_args, _ptr(sums), R, L, n_fft, hop, eps,
+                                    *wsarg, _stream()), entry)
+    return sums
+
+
+def _loss_bwd(what, pred, target, window, hop, coef, eps, out, accumulate, ws, bank=None):
+    """The body of :func:`stft_loss_bwd` and, with ``bank`` = (fb, bands), of :func:`stft_band_loss_bwd`."""
+    _require_gpu(coef, out)
+    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop)
+    entry, kernel, banked, bank_args = "gfx_stft_loss_bwd_f32", "stft_loss_bwd_kernel", (), ()
+    if bank is not None:
+        fb, bands, n_bins = _band_args(what, *bank, n_fft)
+        entry, kernel, banked = "gfx_stft_band_loss_bwd_f32", "stft_band_loss_bwd_kernel", (fb, *bands)
+        bank_args = (*(_ptr(b) for b in banked), n_bins)
+    _expect(coef, (R, 3), what + ": coef")
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate adds to a given out")
+    reads = (p3, t3, window, coef, *banked)
+    if out is not None:
+        if out.shape != pred.shape:
+            raise ValueError(f"{what}: out {tuple(out.shape)} does not match pred {tuple(pred.shape)}")
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+        _output(o3, tuple(p3.shape), pred.device, what, apart=(*reads, ws))
+    else:
+        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        o3, gmap = _loss_rows(out, what, "out", view_only=True)
+    pin = _Pin()
+    wsarg = _workspace(what, ws, nbytes, pred.device, pin, reads, align=16)
+    with _timed(kernel, 4 * R * L * (4 if accumulate else 3)):
+        check(getattr(lib(), entry)(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), *bank_args, pin(coef), _ptr(o3), gmap, R, L,
+                                    n_fft, hop, eps, int(bool(accumulate)), *wsarg, _stream()), entry)
+    return out
 
 
 @_on_device
@@ -1579,18 +1593,9 @@ def stft_loss_sums(pred, target, window, hop, eps=1e-8, ws=None):
     P = torch.stft(pred, n_fft, hop, window=window, center=True, pad_mode="reflect") and T likewise, magnitudes floored at
     sqrt(eps).  ``pred`` / ``target``: (..., L) of one shape, R = the product of the leading dimensions; a (B, C, L) slice
     of a larger buffer is read in place.  ``window``: n_fft floats, n_fft a power of two in [128, 2048].  ``ws``: a uint8
-    workspace of at least ``stft_loss_ws_bytes(R, L, n_fft, hop)`` bytes to reuse.  Nothing of a spectrogram's size is
-    allocated; equal bits from call to call."""
-    what = "stft_loss_sums"
-    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
-    _apart(what, "ws", ws, (p3, t3, window))
-    sums = torch.empty((R, 4), dtype=torch.float32, device=pred.device)
-    pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
-    with _timed("stft_loss_sums_kernel", 4 * R * L * 2):
-        check(lib().gfx_stft_loss_sums_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(sums), R, L, n_fft, hop, eps,
-                                           *wsarg, _stream()), "gfx_stft_loss_sums_f32")
-    return sums
+    workspace of at least ``stft_loss_ws_bytes(R, L, n_fft, hop)`` bytes to reuse, 16-byte aligned, apart from everything
+    the call reads.  Nothing of a spectrogram's size is allocated; equal bits from call to call."""
+    return _loss_sums("stft_loss_sums", pred, target, window, hop, eps, ws)
 
 
 @_on_device
@@ -1601,28 +1606,7 @@ def stft_loss_bwd(pred, target, window, hop, coef, eps=1e-8, out=None, accumulat
     any view whose leading dimensions fold into two strides), required with ``accumulate``, which adds to what it holds
     -- the resolutions of one loss sum into one tensor.  It may share memory with nothing the call reads.  ``ws``: as for
     :func:`stft_loss_sums`."""
-    what = "stft_loss_bwd"
-    _require_gpu(coef, out)
-    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
-    _expect(coef, (R, 3), what + ": coef")
-    if accumulate and out is None:
-        raise ValueError(f"{what}: accumulate adds to a given out")
-    reads = (p3, t3, window, coef)
-    _apart(what, "ws", ws, reads)
-    if out is not None:
-        if out.shape != pred.shape:
-            raise ValueError(f"{what}: out {tuple(out.shape)} does not match pred {tuple(pred.shape)}")
-        o3, gmap = _loss_rows(out, what, "out", view_only=True)
-        _output(o3, tuple(p3.shape), pred.device, what, apart=(*reads, ws))
-    else:
-        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
-        o3, gmap = _loss_rows(out, what, "out", view_only=True)
-    pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
-    with _timed("stft_loss_bwd_kernel", 4 * R * L * (4 if accumulate else 3)):
-        check(lib().gfx_stft_loss_bwd_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), pin(coef), _ptr(o3), gmap, R, L, n_fft,
-                                          hop, eps, int(bool(accumulate)), *wsarg, _stream()), "gfx_stft_loss_bwd_f32")
-    return out
+    return _loss_bwd("stft_loss_bwd", pred, target, window, hop, coef, eps, out, accumulate, ws)
 
 
 def _band_args(what, fb, bands, n_fft):
@@ -1651,18 +1635,7 @@ def stft_band_loss_sums(pred, target, window, hop, fb, bands, eps=1e-8, ws=None)
     E = sum |Tm-Pm|, D = sum |log Tm - log Pm| over the n_bins bands of all frames.  ``fb``: (n_bins, n_fft / 2 + 1)
     non-negative weights, staircase banded; ``bands``: what ``losses.filterbank_bands(fb)`` returned, on the GPU.  The
     rest as for :func:`stft_loss_sums`, the workspace included."""
-    what = "stft_band_loss_sums"
-    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
-    fb, bands, n_bins = _band_args(what, fb, bands, n_fft)
-    _apart(what, "ws", ws, (p3, t3, window, fb, *bands))
-    sums = torch.empty((R, 4), dtype=torch.float32, device=pred.device)
-    pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
-    with _timed("stft_band_loss_sums_kernel", 4 * R * L * 2):
-        check(lib().gfx_stft_band_loss_sums_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(fb), _ptr(bands[0]),
-                                                _ptr(bands[1]), n_bins, _ptr(sums), R, L, n_fft, hop, eps, *wsarg, _stream()),
-              "gfx_stft_band_loss_sums_f32")
-    return sums
+    return _loss_sums("stft_band_loss_sums", pred, target, window, hop, eps, ws, bank=(fb, bands))
 
 
 @_on_device
@@ -1670,30 +1643,7 @@ def stft_band_loss_bwd(pred, target, window, hop, fb, bands, coef, eps=1e-8, out
     """:func:`stft_loss_bwd` for the sums of :func:`stft_band_loss_sums` (gfx_stft_band_loss_bwd_f32): the gradient with
     respect to ``pred`` of sum_r (cA A + cE E + cD D)[r] -> a tensor of pred's shape.  ``fb`` and ``bands`` as in the
     forward (the filterbank gets no gradient), everything else as for :func:`stft_loss_bwd`."""
-    what = "stft_band_loss_bwd"
-    _require_gpu(coef, out)
-    p3, pmap, t3, tmap, R, L, n_fft, nbytes = _loss_args(what, pred, target, window, hop, ws)
-    fb, bands, n_bins = _band_args(what, fb, bands, n_fft)
-    _expect(coef, (R, 3), what + ": coef")
-    if accumulate and out is None:
-        raise ValueError(f"{what}: accumulate adds to a given out")
-    reads = (p3, t3, window, coef, fb, *bands)
-    _apart(what, "ws", ws, reads)
-    if out is not None:
-        if out.shape != pred.shape:
-            raise ValueError(f"{what}: out {tuple(out.shape)} does not match pred {tuple(pred.shape)}")
-        o3, gmap = _loss_rows(out, what, "out", view_only=True)
-        _output(o3, tuple(p3.shape), pred.device, what, apart=(*reads, ws))
-    else:
-        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
-        o3, gmap = _loss_rows(out, what, "out", view_only=True)
-    pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, pred.device)
-    with _timed("stft_band_loss_bwd_kernel", 4 * R * L * (4 if accumulate else 3)):
-        check(lib().gfx_stft_band_loss_bwd_f32(_ptr(p3), pmap, _ptr(t3), tmap, pin(window), _ptr(fb), *(_ptr(b) for b in bands),
-                                               n_bins, pin(coef), _ptr(o3), gmap, R, L, n_fft, hop, eps, int(bool(accumulate)),
-                                               *wsarg, _stream()), "gfx_stft_band_loss_bwd_f32")
-    return out
+    return _loss_bwd("stft_band_loss_bwd", pred, target, window, hop, coef, eps, out, accumulate, ws, bank=(fb, bands))
 
 
 # ----------------------------------------------------------------------------------------- loudness
@@ -1703,7 +1653,7 @@ def kweight_energy_ws_bytes(R, C, L):
     return lib().gfx_kweight_energy_ws_bytes(R, C, L)
 
 
-def _kweight_args(what, x, coef, hop, ws, reads):
+def _kweight_args(what, x, coef, hop):
     """What the two K-weighting entries share, checked: the signal's row map, the ten coefficients as a host array, the
     number of sub-blocks and the workspace's size."""
     xmap, R, C, L = rowmap(x)
@@ -1713,13 +1663,8 @@ def _kweight_args(what, x, coef, hop, ws, reads):
     _expect(coef, (2, 5), what + ": coef")
     if not torch.isfinite(coef).all():
         raise ValueError(f"{what}: coef holds a value that is not finite")
-    if isinstance(hop, bool) or not isinstance(hop, int) or not 1 <= hop <= L:
-        raise ValueError(f"{what}: hop={hop!r} must be an integer in 1..L={L}")
+    _int_in(what, "hop", hop, 1, L)
     nbytes = lib().gfx_kweight_energy_ws_bytes(R, C, L)
-    if ws is not None:
-        _apart(what, "ws", ws, reads)
-        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 16:
-            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU, 16-byte aligned")
     return xmap, R, C, L, (ctypes.c_double * 10)(*coef.reshape(-1).tolist()), L // hop, nbytes
 
 
@@ -1733,10 +1678,10 @@ def kweight_energy(x, coef, hop, ws=None):
     ``kweight_energy_ws_bytes(R, C, L)`` bytes to reuse.  Equal bits from call to call."""
     what = "kweight_energy"
     _require_gpu(x)
-    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop, ws, (x,))
+    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop)
     energy = torch.empty((R, C, n_sub), dtype=torch.float64, device=x.device)
     pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    wsarg = _workspace(what, ws, nbytes, x.device, pin, (x,), align=16)
     with _timed("kweight_energy_kernel", 4 * R * C * L * 2):     # x twice: the tiles' end states, then the energies
         check(lib().gfx_kweight_energy_f32(_ptr(x), xmap, c10, _ptr(energy), R, C, L, hop, *wsarg, _stream()),
               "gfx_kweight_energy_f32")
@@ -1757,13 +1702,13 @@ def kweight_energy_bwd(x, coef, genergy, hop, out=None, accumulate=False, ws=Non
     if accumulate and out is None:
         raise ValueError(f"{what}: accumulate adds to a given out")
     reads = (x, genergy)
-    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop, ws, reads)
+    xmap, R, C, L, c10, n_sub, nbytes = _kweight_args(what, x, coef, hop)
     _expect(genergy, (R, C, n_sub), what + ": genergy")
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     _, gmap = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
     pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    wsarg = _workspace(what, ws, nbytes, x.device, pin, reads, align=16)
     # x three times (end states, the adjoint's end states, the adjoint), gx once
     with _timed("kweight_energy_bwd_kernel", 4 * R * C * L * (5 if accumulate else 4)):
         check(lib().gfx_kweight_energy_bwd_f32(_ptr(x), xmap, c10, pin(genergy), _ptr(out), gmap, R, C, L, hop,
@@ -1786,16 +1731,11 @@ def upfirdn_absmax_ws_bytes(R, C, M):
 def _upfirdn_args(what, x, h, up, down, offset, n_out):
     """What the two polyphase entries share, checked before anything is allocated: the signal's row map, the taps, the
     ratio, the offset and the number of outputs -> (xmap, R, C, L, N, M)."""
-    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32:
-        raise TypeError(f"{what}: h must be a float32 tensor on the GPU")
-    if h.ndim != 1 or not 1 <= h.numel() <= UPFIRDN_MAX_TAPS:
-        raise ValueError(f"{what}: h must hold 1..{UPFIRDN_MAX_TAPS} taps in one dimension, got {tuple(h.shape)}")
+    _taps(what, "h", h, UPFIRDN_MAX_TAPS)
     N = h.numel()
-    for name, v in (("up", up), ("down", down)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= UPFIRDN_MAX_RATIO:
-            raise ValueError(f"{what}: {name}={v!r} must be an integer in 1..{UPFIRDN_MAX_RATIO}")
-    if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset < N:
-        raise ValueError(f"{what}: offset={offset!r} must be an integer in 0..N-1={N - 1}")
+    _int_in(what, "up", up, 1, UPFIRDN_MAX_RATIO)
+    _int_in(what, "down", down, 1, UPFIRDN_MAX_RATIO)
+    _int_in(what, "offset", offset, 0, N - 1)
     xmap, R, C, L = rowmap(x)
     if min(R, C, L) < 1:
         raise ValueError(f"{what}: x {tuple(x.shape)} holds no sample")
@@ -1836,15 +1776,10 @@ def upfirdn_absmax(x, h, up, down, offset=0, n_out=None, ws=None):
     what = "upfirdn_absmax"
     _require_gpu(x)
     xmap, R, C, L, N, M = _upfirdn_args(what, x, h, up, down, offset, n_out)
-    nbytes = lib().gfx_upfirdn_absmax_ws_bytes(R, C, M)
-    if ws is not None:
-        _apart(what, "ws", ws, (x, h))
-        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 16:
-            raise ValueError(f"{what}: the workspace must be {nbytes} contiguous uint8 on the GPU, 16-byte aligned")
     peak = torch.empty((R, C), dtype=torch.float32, device=x.device)
     index = torch.empty((R, C), dtype=torch.int64, device=x.device)
     pin = _Pin()
-    wsarg = (ws.data_ptr(), ws.numel()) if ws is not None else pin.workspace(nbytes, x.device)
+    wsarg = _workspace(what, ws, lib().gfx_upfirdn_absmax_ws_bytes(R, C, M), x.device, pin, (x, h), align=16)
     with _timed("upfirdn_absmax_kernel", 4 * R * C * L):
         check(lib().gfx_upfirdn_absmax_f32(_ptr(x), xmap, pin(h), N, up, down, offset, _ptr(peak), _ptr(index), R, C, L, M,
                                            *wsarg, _stream()), "gfx_upfirdn_absmax_f32")

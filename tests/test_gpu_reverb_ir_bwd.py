@@ -86,6 +86,13 @@ def test_run_to_run_bits_on_a_recycled_workspace():
     second = _native(m, m.noise_stft, init, delta, g, gh, True, True, ws=ws)
     for a, b in zip(first, second):
         assert torch.equal(a, b)
+    # a workspace cut from the gradient the call reads, and one on the host: refused before any launch
+    before = gh.clone()
+    with pytest.raises(ValueError, match="share memory"):
+        _native(m, m.noise_stft, init, delta, g, gh, True, True, ws=gh.view(torch.uint8).view(-1)[:ws.numel()])
+    assert torch.equal(gh, before)
+    with pytest.raises(ValueError, match="workspace"):
+        _native(m, m.noise_stft, init, delta, g, gh, True, True, ws=ws.cpu())
 
 
 def test_more_rows_than_one_launch_takes():

@@ -199,6 +199,14 @@ def test_accumulate_adds_to_the_buffer_and_a_plain_call_overwrites_all_of_it():
     assert torch.equal(buf, plain)
     with pytest.raises(ValueError, match="accumulate"):
         ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, accumulate=True)
+    # a workspace the entries would answer with a bare error code, 8 bytes off the 16 they need: refused by name
+    nbytes = ops.stft_loss_ws_bytes(f64.ROWS, L, n_fft, hop)
+    ws = torch.empty(nbytes + 16, dtype=torch.uint8, device="cuda")[8:]
+    with pytest.raises(ValueError, match="workspace"):
+        ops.stft_band_loss_sums(pred, target, w, hop, fb, bands, eps, ws=ws)
+    with pytest.raises(ValueError, match="workspace"):
+        ops.stft_band_loss_bwd(pred, target, w, hop, fb, bands, coef, eps, out=buf, ws=ws)
+    assert torch.equal(buf, plain)
 
 
 # ------------------------------------------------------------------------------------------------ 7: layouts

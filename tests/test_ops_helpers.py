@@ -4,7 +4,8 @@ import pytest
 import torch
 
 from grafx_amd import ops
-from grafx_amd.ops import _apart, _output, _read_mix, _row_chunks, _state, rowmap
+from grafx_amd.ops import (_apart, _int_in, _output, _Pin, _read_mix, _row_chunks, _state, _taps, _want, _workspace,
+                           rowmap)
 
 SHAPE = (2, 2, 64)
 CPU = torch.device("cpu")
@@ -87,6 +88,76 @@ def test_state_on_the_gpu():
     for bad in (good.double(), good[:, :, :63], torch.zeros(2, 64, 2, device="cuda").transpose(1, 2)):
         with pytest.raises(ValueError, match=r"entry: zf must be .*\(2, 2, 64\)"):
             _state(bad, SHAPE, "entry", "zf")
+
+
+def test_workspace_made_when_none_is_given():
+    pin = _Pin()
+    ptr, nbytes = _workspace("t", None, 64, CPU, pin, ())
+    assert nbytes == 64 and pin.ws.dtype == torch.uint8 and pin.ws.numel() == 64 and ptr == pin.ws.data_ptr() != 0
+    empty = _Pin()
+    assert _workspace("t", None, 0, CPU, empty, ()) == (0, 0) and empty.ws is None
+
+
+def test_workspace_of_the_caller():
+    pin, x = _Pin(), torch.zeros(SHAPE)
+    ws = torch.empty(64, dtype=torch.uint8)
+    assert _workspace("t", ws, 64, CPU, pin, (x, None)) == (ws.data_ptr(), 64) and pin.ws is None
+    longer = torch.empty(100, dtype=torch.uint8)
+    assert _workspace("t", longer, 64, CPU, pin, ()) == (longer.data_ptr(), 100)      # the entry is told all of it
+    with pytest.raises(ValueError, match="t: .*workspace.* 64 "):
+        _workspace("t", torch.empty(63, dtype=torch.uint8), 64, CPU, pin, ())
+    with pytest.raises(ValueError, match="uint8"):
+        _workspace("t", torch.empty(16, dtype=torch.float32), 64, CPU, pin, ())
+    with pytest.raises(ValueError, match="workspace"):
+        _workspace("t", torch.empty(128, dtype=torch.uint8)[::2], 64, CPU, pin, ())
+    with pytest.raises(ValueError, match="workspace"):                                  # everything right but the device
+        _workspace("t", ws, 64, torch.device("cuda", 0), pin, ())
+    off = torch.empty(80, dtype=torch.uint8)[8:72]
+    assert off.data_ptr() % 16 == 8
+    with pytest.raises(ValueError, match="workspace.*16-byte aligned"):
+        _workspace("t", off, 64, CPU, pin, (), align=16)
+    assert _workspace("t", off, 64, CPU, pin, (), align=1) == (off.data_ptr(), 64)
+    with pytest.raises(ValueError, match="workspace") as e:                             # (no alignment asked, none named)
+        _workspace("t", off[:63], 64, CPU, pin, ())
+    assert "aligned" not in str(e.value)
+    with pytest.raises(ValueError, match="t: ws must not share memory"):
+        _workspace("t", x.view(torch.uint8).view(-1)[64:128], 64, CPU, pin, (None, x))
+    with pytest.raises(ValueError, match="share memory"):                               # the aliasing rule comes first
+        _workspace("t", x.view(torch.uint8).view(-1)[:63], 64, CPU, pin, (x,))
+
+
+def test_int_in():
+    lo, hi = 1, 16
+    for good in (lo, hi, 7):
+        _int_in("t", "factor", good, lo, hi)
+    for bad in (True, 3.0, "3", None, lo - 1, hi + 1):
+        with pytest.raises(ValueError, match=r"t: factor=.* must be an integer in 1\.\.16") as e:
+            _int_in("t", "factor", bad, lo, hi)
+        assert f"factor={bad!r}" in str(e.value)
+
+
+class _SaysGpu(torch.Tensor):
+    """A CPU tensor that answers ``is_cuda`` with True: the shape and count checks of _taps come after the device's."""
+    is_cuda = property(lambda self: True)
+
+
+def test_taps():
+    on_gpu = lambda t: t.as_subclass(_SaysGpu)  # noqa: E731
+    _taps("t", "h", on_gpu(torch.zeros(1)), 8)
+    _taps("t", "h", on_gpu(torch.zeros(8)), 8)
+    for bad in ([0.0] * 4, None, torch.zeros(4), on_gpu(torch.zeros(4, dtype=torch.float64))):   # type, device, dtype
+        with pytest.raises(TypeError, match="t: h_up must be a float32 tensor on the GPU"):
+            _taps("t", "h_up", bad, 8)
+    for bad in (torch.zeros(2, 2), torch.zeros(0), torch.zeros(9)):                               # 2-D, no tap, one too many
+        with pytest.raises(ValueError, match=r"t: h must hold 1\.\.8 taps"):
+            _taps("t", "h", on_gpu(bad), 8)
+
+
+def test_want():
+    _want("t", (), ("x", "p0"))
+    _want("t", ["p0", "x"], ("x", "p0"))
+    with pytest.raises(ValueError, match=r"t: unknown gradients \['h_up'\] \(known: \('x', 'p0'\)\)"):
+        _want("t", ("x", "h_up"), ("x", "p0"))
 
 
 @pytest.mark.parametrize("limit", [1, 3, ops.GRID_ROWS_I16_MAX, ops.GRID_YZ_MAX])
