@@ -1,5 +1,6 @@
-// Shared pieces of the chirp-z transforms (czt.hip: one real row per transform; czt_pair.hip: two real rows packed
-// into one complex transform): precision traits, the geometry, the chirp tables and the column / tile kernels.
+// Shared pieces of the chirp-z transforms (czt.hip: one real row per transform; czt_pair.hpp: two real rows packed
+// into one complex transform): precision traits, the geometry, the vocabulary the column and radix-4 passes of both forms
+// are written in, and the host launchers of the kernels that both forms run (compiled in czt.hip, once).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,8 +64,19 @@ __device__ __forceinline__ float* czt_out_row(const CztGeom& g, float* y, int64_
 
 constexpr int CZT_MAX_LEVELS = 3;   // NFFT <= 2^24: P <= 11,184,811 (233 s of audio at 48 kHz plus the filter)
 
-static inline bool czt_geom(int64_t P, CztGeom& g) {
-    if (P < 3 || (P & 1) == 0) return false;
+// the pair form's column passes take up to 63 tiles at once (their kernels of more than 32 are czt_pair.hpp's)
+constexpr int CZT_PAIR_MAXC = 63;
+#define GFX_CZT_PAIR_SIZES(X) GFX_CZT_SIZES(X) X(35) X(36) X(40) X(42) X(45) X(48) X(49) X(50) X(54) X(56) X(60) X(63)
+
+// the pair's middle pass keeps two columns of C points in registers when fused with the next column pass: above 48 tiles
+// (36 in double precision) that no longer fits two waves per SIMD and it goes in two passes instead (one more sweep over the
+// buffer): czt_pair_mid_kernel, then this file's forward column pass
+template <typename T, int C> constexpr bool pair_mid_fused() { return sizeof(T) == 4 ? C <= 48 : C <= 36; }
+
+// The geometry of a transform of odd length P whose convolutions span `points`: up to `one_pass` tiles in one column
+// pass; beyond, outer radix-4 levels around sub-transforms of C <= 32 tiles.  C is rounded up to a count with prime factors
+// up to 7 (small_dft.hpp; 32 and 63 = 3 * 3 * 7 are supported: the loop ends at or below them).
+static inline bool czt_geom_points(int64_t P, int64_t points, int one_pass, CztGeom& g) {
     g.yC = 0;
     g.row0 = 0;
     g.rmax = nullptr;
@@ -73,22 +85,40 @@ static inline bool czt_geom(int64_t P, CztGeom& g) {
     g.P = P;
     g.Q = P - 1;
     g.K = (P + 1) / 2;
-    const int64_t need = P + g.K - 1;
-    const int64_t tiles = (need + TILE_M - 1) / TILE_M;
-    // C <= 32 tiles per (sub-)transform with prime factors up to 7 (small_dft.hpp); beyond 32, outer radix-4 levels
     g.levels = 0;
-    int64_t per = tiles;
-    while (per > CZT_MAXC) {
-        per = (per + 3) / 4;
-        ++g.levels;
-    }
-    int64_t C = per;
-    while (!sd_supported((int)C)) ++C;       // (32 is supported: the loop ends)
-    if (g.levels > CZT_MAX_LEVELS || C < 1) return false;
+    int64_t per = (points + TILE_M - 1) / TILE_M;
+    if (per > one_pass)
+        while (per > CZT_MAXC) {
+            per = (per + 3) / 4;
+            ++g.levels;
+        }
+    if (g.levels > CZT_MAX_LEVELS) return false;
+    int C = (int)per;
+    while (!sd_supported(C) || C == 64) ++C;
     g.S = 1 << (2 * g.levels);
-    g.C = (int)C;
+    g.C = C;
     g.NFFT = (int64_t)g.S * C * TILE_M;
     return true;
+}
+// one row per transform: P inputs and K outputs (or the other way round) under one circular convolution
+static inline bool czt_geom(int64_t P, CztGeom& g) {
+    return P >= 3 && (P & 1) && czt_geom_points(P, P + (P + 1) / 2 - 1, CZT_MAXC, g);
+}
+// two rows per transform: the bins on both sides, 2P - 1 points
+static inline bool czt_pair_geom(int64_t P, CztGeom& g) {
+    return P >= 3 && (P & 1) && czt_geom_points(P, 2 * P - 1, CZT_PAIR_MAXC, g);
+}
+
+// where the output goes: the slice [lo, lo + len) of the Q grid, rows ldy apart or (ymap) through a row map
+static inline bool czt_output_args(CztGeom& g, const gfx_rowmap_t* ymap, int yC, int64_t row0, int64_t rows, int64_t lo,
+                                   int64_t len, int64_t ldy) {
+    if (ymap) {
+        if (yC < 1 || row0 < 0 || ymap->inner <= 0 || ymap->inner > 0x7fffffffLL || (row0 + rows) / yC > 0x7fffffffLL)
+            return false;
+        g.yC = yC;
+        g.ymap = *ymap;
+    }
+    return lo >= 0 && len >= 1 && lo + len <= g.Q && ldy >= len;
 }
 
 // plan layout (float2 units): cP[P] | cQ[Q] | spectra [NFFT] each of bP, bQ (forward) and of bQ, bP placed for the
@@ -168,12 +198,6 @@ __device__ __forceinline__ typename Prec<T>::T2 chirp_d(int64_t j, int64_t den, 
     return Prec<T>::make((T)c, (T)(sign * s));
 }
 
-template <typename T>
-__global__ void czt_chirp_table_kernel(typename Prec<T>::T2* __restrict__ tab, int64_t n, int64_t den, float sign) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) tab[i] = chirp_d<T>(i, den, sign);
-}
-
 // e^{-+ 2 pi i r / N} for 0 <= r < N, N a multiple of 4 (N = C x 8192, not a power of two in general): the quarter turn is
 // taken off in integers and the rest, rem / (N / 2) <= 1/2 half-turns with rem < 2^24 exact, goes to sincospif -- the phase
 // is good to 1e-7 rad whatever N (for a power of two the quotient is exact, as before).
@@ -236,183 +260,41 @@ __device__ __forceinline__ void col_dft(V (&v)[C]) {
     else sdft<C, INV>(v);
 }
 
-// MODE 0: real rows, z[row, i - lo] tab[i] for lo <= i < lo + len (row stride ldz), zero elsewhere;  MODE 1: the complex
-// buffer itself;  MODE 2: a chirp sequence (plan building)
-template <typename T, int C, int MODE>
-__global__ __launch_bounds__(256) void czt_cols_fwd_kernel(const float* __restrict__ z,
-                                                          const typename Prec<T>::T2* __restrict__ tab,
-                                                          typename Prec<T>::T2* __restrict__ buf, CztGeom g, int64_t ldz,
-                                                          int64_t lo, int64_t len, ChirpSeq cs) {
-    using cx = typename Prec<T>::cxt;
-    const int n2 = blockIdx.x * 256 + threadIdx.x;          // column 0..8191
-    const int64_t row = blockIdx.y;                        // signal row * S + sub-transform
-    const int64_t NS = g.NFFT / g.S;                       // points of one sub-transform
-    typename Prec<T>::T2* b = buf + row * NS;
-    const ColBuf<T> cb(b, NS);
-    cx v[C];
-#pragma unroll
-    for (int n1 = 0; n1 < C; ++n1) {
-        const int64_t i = (int64_t)n1 * TILE_M + n2;
-        cx e = {0, 0};
-        if (MODE == 0) {
-            if (i >= lo && i < lo + len) e = to_cx(tab[i]) * (T)z[row * ldz + (i - lo)];
-        } else if (MODE == 1) {
-            e = cb.ld(n1, n2);
-        } else {
-            if (i <= cs.hi) e = to_cx(chirp_d<T>(i, cs.den, cs.sign));
-            else if (i >= g.NFFT - cs.lo) e = to_cx(chirp_d<T>(g.NFFT - i, cs.den, cs.sign));
-        }
-        v[n1] = e;
-    }
-    col_dft<C, false>(v);
-    ColTw<T, C> tw(n2, (int)NS, false);
-#pragma unroll
-    for (int k1 = 0; k1 < C; ++k1) {
-        const cx e = v[spos(C, k1)];
-        const cx o = k1 == 0 ? e : cmul(e, tw.at(k1));
-        cb.st(k1, n2, o);
-    }
+// ---- the passes' vocabulary, one point at a time (the loops stay in the kernels: as functions of the register array the
+// same passes compile to other schedules, EXPERIMENTS.md "Chirp-z transforms: every kernel compiled once") ---------------
+// A column pass's two ends for point k1 of the thread's column n2 (rows row0 + k1 of cb): in, the point times the
+// conjugate twiddle (tw built with conj) -- what col_dft<C, true> inverts; out, what col_dft<C, false> left at
+// v[spos(C, k1)] times the forward twiddle.  Call for k1 = 0 .. C-1 in turn: ColTw<double> counts on it.
+template <typename T, int C>
+__device__ __forceinline__ typename Prec<T>::cxt col_in(const ColBuf<T>& cb, ColTw<T, C>& tw, int k1, int n2, int row0 = 0) {
+    const typename Prec<T>::cxt e = cb.ld(row0 + k1, n2);
+    return k1 == 0 ? e : cmul(e, tw.at(k1));
 }
-
-// One tile per (row, k1): forward, times the chirp spectrum, inverse -- in place.  PLAN: forward only, spectrum stored
-// in thread layout.
-// float: the twiddles live through the tile, the spectrum is loaded up front and the tile goes through a descriptor (10.1
-// -> 9.3 ms per 4096 rows).  double: the split tile (fft_tile_f64.hpp: exchanges in two rounds, twiddles fetched per pass),
-// the spectrum eight values at a time and global accesses to the tile (measured 1 % better than the descriptor form).
-template <typename T, bool PLAN>
-__global__ __launch_bounds__(TILE_T, 2) void czt_rows_kernel(
-    typename Prec<T>::T2* __restrict__ buf, const typename Prec<T>::T2* __restrict__ spec,
-    typename Prec<T>::T2* __restrict__ spec_out, int C, const typename Prec<T>::T2* __restrict__ twtab) {
-    using cx = typename Prec<T>::cxt;
-    constexpr bool F32 = sizeof(T) == 4;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    cx* lds = reinterpret_cast<cx*>(lds_raw);
-    const int t = threadIdx.x;
-    const int64_t tile = blockIdx.x;                    // row * C + k1
-    const int k1 = (int)(tile % C);                       // C here = tiles per signal row = S * C
-    constexpr uint32_t TILE_BYTES = TILE_M * sizeof(cx);
-    const __amdgpu_buffer_rsrc_t rb = tile_rsrc(reinterpret_cast<cx*>(buf) + tile * TILE_M, TILE_BYTES);
-    TileTw tw;
-    if constexpr (F32) tile_twiddles(tw, twtab, t);
-    cx v[32], w[2][16];
-    cx* b = reinterpret_cast<cx*>(buf) + tile * TILE_M;
-#pragma unroll
-    for (int a = 0; a < 32; ++a) {
-        if constexpr (F32) v[a] = tile_ld<CZT_NT>(rb, t, a, (cx*)nullptr);
-        else v[a] = __builtin_nontemporal_load(&b[t + 256 * a]);
-    }
-    // float: the spectrum's loads go out with the tile's, up front, as in fftconv1_kernel -- left to itself the compiler
-    // issues each one right before its product and waits for it, 32 L2 round trips in the middle of the tile (in double the
-    // 128 registers are not there)
-    cx sreg[32];
-    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(reinterpret_cast<const cx*>(spec) + (PLAN ? 0 : (int64_t)k1 * TILE_M), TILE_BYTES);
-    if constexpr (F32 && !PLAN) {
-#pragma unroll
-        for (int q = 0; q < 32; ++q) sreg[q] = tile_ld<0>(rs, t, q, (cx*)nullptr);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (F32) tile_forward(v, w, tw, lds, t);
-    else tile_forward(v, w, twtab, lds, t);
-    if (PLAN) {
-        cx* o = reinterpret_cast<cx*>(spec_out) + (int64_t)k1 * TILE_M;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) o[q * TILE_T + t] = w[q >> 4][q & 15];
-        return;
-    }
-    if constexpr (F32) {
-#pragma unroll
-        for (int q = 0; q < 32; ++q) w[q >> 4][q & 15] = cmul(w[q >> 4][q & 15], sreg[q]);
-    } else {
-        // eight spectrum values at a time, fenced: left to itself the scheduler requests all 32 (128 registers) on top of the
-        // 128 of the tile, and at two workgroups per CU there are 256 in all
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_barrier(0);
-            cx sp[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) sp[q] = tile_ld<0>(rs, t, 8 * g + q, (cx*)nullptr);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) w[(8 * g + q) >> 4][(8 * g + q) & 15] = cmul(w[(8 * g + q) >> 4][(8 * g + q) & 15], sp[q]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-    if constexpr (F32) tile_inverse(w, v, tw, lds, t);
-    else tile_inverse(w, v, twtab, lds, t);
-#pragma unroll
-    for (int a = 0; a < 32; ++a) {
-        if constexpr (F32) tile_st<CZT_NT>(rb, t, a, v[brev(a, 5)]);
-        else __builtin_nontemporal_store(v[brev(a, 5)], &b[t + 256 * a]);
-    }
+template <typename T, int C>
+__device__ __forceinline__ void col_out(const ColBuf<T>& cb, ColTw<T, C>& tw, int k1, int n2, typename Prec<T>::cxt e, int row0 = 0) {
+    const typename Prec<T>::cxt o = k1 == 0 ? e : cmul(e, tw.at(k1));
+    cb.st(row0 + k1, n2, o);
 }
-
-// MODE 0 (after the first convolution): buf[k] <- conv[k] cP[k] w_k cQ[k] / NFFT for k < K, zero beyond
-// MODE 1 (after the second):            y[row, n - lo] <- Re(conv[n] cQ[n]) / (NFFT Q)  for lo <= n < lo + len
-// MODE 3: MODE 0 and the second convolution's column pass (cols_fwd MODE 1) in one -- the same thread owns the column in
-//         both, so the buffer is read and written once instead of twice
-// (the adjoint passes cP in cQ's place for MODE 1: its output lives on the P grid, still divided by Q)
-template <typename T, int C, int MODE>
-__global__ __launch_bounds__(256) void czt_cols_inv_kernel(typename Prec<T>::T2* __restrict__ buf,
-                                                          const typename Prec<T>::T2* __restrict__ cP,
-                                                          const typename Prec<T>::T2* __restrict__ cQ,
-                                                          float* __restrict__ y, int64_t ldy, int64_t lo, int64_t len,
-                                                          CztGeom g) {
-    using cx = typename Prec<T>::cxt;
-    const int n2 = blockIdx.x * 256 + threadIdx.x;
-    const int64_t row = blockIdx.y;
-    const int64_t NS = g.NFFT / g.S;
-    typename Prec<T>::T2* b = buf + row * NS;
-    const ColBuf<T> cb(b, NS);
-    cx v[C];
-    ColTw<T, C> twi(n2, (int)NS, true);
-#pragma unroll
-    for (int k1 = 0; k1 < C; ++k1) {
-        const cx e = cb.ld(k1, n2);
-        v[k1] = k1 == 0 ? e : cmul(e, twi.at(k1));
+// the one-row form between its convolutions: bin i < K times cP[i] w_i cQ[i], zero beyond
+template <typename T>
+__device__ __forceinline__ typename Prec<T>::cxt bin_factor(typename Prec<T>::cxt e, int64_t i, const CztGeom& g,
+                                                            const typename Prec<T>::T2* cP,
+                                                            const typename Prec<T>::T2* cQ, T sc = (T)1) {
+    typename Prec<T>::cxt o = {0, 0};
+    if (i < g.K) {
+        const T wk = (i == 0 || i == g.K - 1) ? (T)1 : (T)2;
+        o = cmul(cmul(e * sc, to_cx(cP[i])), to_cx(cQ[i])) * wk;
     }
-    col_dft<C, true>(v);
-    const T sc = (T)1 / (T)NS;
-    if (MODE == 3) {   // the step between the two convolutions (S = 1): MODE 0's values, then cols_fwd's MODE 1 on them
-        cx u[C];
-#pragma unroll
-        for (int n1 = 0; n1 < C; ++n1) {
-            const int64_t i = (int64_t)n1 * TILE_M + n2;
-            cx o = {0, 0};
-            if (i < g.K) {
-                const T wk = (i == 0 || i == g.K - 1) ? (T)1 : (T)2;
-                o = cmul(cmul(v[spos(C, n1)] * sc, to_cx(cP[i])), to_cx(cQ[i])) * wk;
-            }
-            u[n1] = o;
-        }
-        col_dft<C, false>(u);
-        ColTw<T, C> twf(n2, (int)NS, false);
-#pragma unroll
-        for (int k1 = 0; k1 < C; ++k1) {
-            const cx e = u[spos(C, k1)];
-            const cx o = k1 == 0 ? e : cmul(e, twf.at(k1));
-            cb.st(k1, n2, o);
-        }
-        return;
-    }
-#pragma unroll
-    for (int n1 = 0; n1 < C; ++n1) {
-        const int64_t i = (int64_t)n1 * TILE_M + n2;
-        const cx e = v[spos(C, n1)] * sc;
-        if (MODE == 2) {                                   // plain inverse of a sub-transform (outer level follows)
-            cb.st(n1, n2, e);
-        } else if (MODE == 0) {
-            cx o = {0, 0};
-            if (i < g.K) {
-                const T wk = (i == 0 || i == g.K - 1) ? (T)1 : (T)2;
-                o = cmul(cmul(e, to_cx(cP[i])), to_cx(cQ[i])) * wk;
-            }
-            cb.st(n1, n2, o);
-        } else {
-            if (i >= lo && i < lo + len) {
-                const cx c = to_cx(cQ[i]);
-                czt_out_row(g, y, ldy, row)[i - lo] = (float)((e.x * c.x - e.y * c.y) / (T)g.Q);
-            }
-        }
+    return o;
+}
+// the one-row form's last step: y[row, i - lo] <- Re(e cQ[i]) / Q for lo <= i < lo + len
+template <typename T>
+__device__ __forceinline__ void real_out(typename Prec<T>::cxt e, int64_t i, const CztGeom& g,
+                                         const typename Prec<T>::T2* cQ, float* y, int64_t ldy,
+                                         int64_t lo, int64_t len, int64_t row) {
+    if (i >= lo && i < lo + len) {
+        const typename Prec<T>::cxt c = to_cx(cQ[i]);
+        czt_out_row(g, y, ldy, row)[i - lo] = (float)((e.x * c.x - e.y * c.y) / (T)g.Q);
     }
 }
 
@@ -429,28 +311,44 @@ __device__ __forceinline__ typename Prec<T>::cxt outer_twiddle(int64_t np, int k
     }
 }
 
-// the passes below the outermost level of a transform with outer levels (g.levels >= 1), in place on `rows` buffers of
-// g.NFFT points: inner radix-4 levels and the column pass (forward), the inverse column pass and the inner levels
-// (inverse, scaled by 4^(levels-1) / NFFT: the outermost level's 1/4 is the caller's); and a chirp sequence's spectrum
-// in the tile pass's layout.  Defined in czt.hip.
+// a radix-4 pass's two ends for the thread's point np + k3 NS of the buffer b, as col_in / col_out (out: the result for k3
+// is what dif<4, false> left at v[brev(k3, 2)])
+template <typename T>
+__device__ __forceinline__ typename Prec<T>::cxt r4_in(const typename Prec<T>::T2* b, int64_t NS, int64_t np, int64_t NFFT, int k3) {
+    const typename Prec<T>::cxt e = buf_load<T>(&b[k3 * NS + np]);
+    return k3 == 0 ? e : cmul(e, outer_twiddle<T>(np, k3, NFFT, true));
+}
+template <typename T>
+__device__ __forceinline__ void r4_out(typename Prec<T>::T2* b, int64_t NS, int64_t np, int64_t NFFT, int k3, typename Prec<T>::cxt e) {
+    const typename Prec<T>::cxt o = k3 == 0 ? e : cmul(e, outer_twiddle<T>(np, k3, NFFT, false));
+    buf_store<T>(&b[k3 * NS + np], o);
+}
+// ---- the kernels both forms run, compiled once: their host launchers (czt.hip), per working precision ------------------
+// the passes below the outermost level of a transform, in place on `rows` buffers of g.NFFT points: inner radix-4 levels
+// and the column pass (forward; with no levels just that column pass, of up to 63 tiles where the pair form takes its
+// middle step in two passes), the inverse column pass and the inner levels (inverse, scaled by 4^(levels-1) / NFFT: the
+// outermost level's 1/4 is the caller's)
 void czt_levels_fwd(const CztGeom& g, float2* buf, int64_t rows, hipStream_t st);
 void czt_levels_fwd(const CztGeom& g, double2* buf, int64_t rows, hipStream_t st);
 void czt_levels_inv(const CztGeom& g, float2* buf, int64_t rows, hipStream_t st);
 void czt_levels_inv(const CztGeom& g, double2* buf, int64_t rows, hipStream_t st);
-void czt_levels_chirp_spectrum(const CztGeom& g, ChirpSeq cs, float2* buf, float2* spec, const float2* tw, hipStream_t st);
-void czt_levels_chirp_spectrum(const CztGeom& g, ChirpSeq cs, double2* buf, double2* spec, const double2* tw, hipStream_t st);
+// the tile pass: its twiddle table (null: not to be had) with the LDS it needs allowed -- `plan`: for czt_chirp_spectrum
+const float2* czt_tile_setup(bool plan, hipStream_t st, const float2*);
+const double2* czt_tile_setup(bool plan, hipStream_t st, const double2*);
+// `tiles` tiles of buf, ctot per transform: forward, times spec, inverse
+void czt_tile_pass(float2* buf, const float2* spec, int64_t tiles, int ctot, const float2* tw, hipStream_t st);
+void czt_tile_pass(double2* buf, const double2* spec, int64_t tiles, int ctot, const double2* tw, hipStream_t st);
+// cP[i] = e^{-i pi i^2 / P}, i < P, and cQ[i] = e^{+i pi i^2 / Q}, i < Q = P - 1
+void czt_chirp_tables(float2* cP, float2* cQ, int64_t P, hipStream_t st);
+void czt_chirp_tables(double2* cP, double2* cQ, int64_t P, hipStream_t st);
+// a chirp sequence's spectrum in the tile pass's layout (buf: g.NFFT points of scratch), with or without outer levels
+void czt_chirp_spectrum(const CztGeom& g, ChirpSeq cs, float2* buf, float2* spec, const float2* tw, hipStream_t st);
+void czt_chirp_spectrum(const CztGeom& g, ChirpSeq cs, double2* buf, double2* spec, const double2* tw, hipStream_t st);
 
 template <typename K>
 static bool czt_allow_lds(K kernel, int bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
            hipSuccess;
 }
-
-// the double tile's twiddles, one table per device (czt.hip)
-const double2* tile_twiddle_table_f64(hipStream_t stream);
-
-template <typename T> inline const typename Prec<T>::T2* czt_twiddles(hipStream_t st);
-template <> inline const float2* czt_twiddles<float>(hipStream_t st) { return tile_twiddle_table(st); }
-template <> inline const double2* czt_twiddles<double>(hipStream_t st) { return tile_twiddle_table_f64(st); }
 
 }  // namespace gfx

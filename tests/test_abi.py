@@ -128,6 +128,57 @@ def test_size_queries_need_no_gpu():
     assert lib.gfx_odd_alias_pair_plan_bytes(4000) == 0 and lib.gfx_odd_alias_plan_bytes(8388609) > 0
 
 
+CZT_ONE_ROW_TILES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 15, 16, 18, 20, 21, 24, 25, 27, 28, 30, 32)
+CZT_PAIR_TILES = CZT_ONE_ROW_TILES + (35, 36, 40, 42, 45, 48, 49, 50, 54, 56, 60, 63)
+CZT_SIZE_ROWS = (1, 2, 3, 1024)
+CZT_SIZE_ENTRIES = [f"gfx_odd_alias{pair}{precise}_{what}_bytes" for pair in ("", "_pair") for precise in ("", "_precise")
+                    for what in ("plan", "workspace")]
+
+
+def czt_size_lengths():
+    """For every supported tile count of each form the largest odd P that fits it and the next odd one (32 and 63 tiles: the
+    last lengths before an outer radix-4 level), and the ends of the range: the smallest length, an even one, the last
+    lengths of the pair form (2P - 1 <= 2^24) and of the one-row form ((3P - 1) / 2 <= 2^24) and the first beyond each."""
+    lengths = {3, 4000, 8388607, 8388609, 11184811, 11184813}
+    for C in CZT_ONE_ROW_TILES:              # P + (P + 1) / 2 - 1 <= 8192 C
+        P = (2 * 8192 * C + 1) // 3
+        P -= 1 - P % 2
+        assert P + (P + 1) // 2 - 1 <= 8192 * C < P + 2 + (P + 3) // 2 - 1
+        lengths |= {P, P + 2}
+    for C in CZT_PAIR_TILES:                 # 2 P - 1 <= 8192 C
+        P = (8192 * C + 1) // 2
+        P -= 1 - P % 2
+        assert 2 * P - 1 <= 8192 * C < 2 * (P + 2) - 1
+        lengths |= {P, P + 2}
+    return sorted(lengths)
+
+
+def czt_size_table(lib):
+    return {name: [[getattr(lib, name)(P)] if name.endswith("plan_bytes") else [getattr(lib, name)(rows, P) for rows in CZT_SIZE_ROWS]
+                   for P in czt_size_lengths()] for name in CZT_SIZE_ENTRIES}
+
+
+def test_chirp_z_sizes_are_the_recorded_ones():
+    """The eight size entries of the odd-length aliasing over every supported tile count of both forms, either side of
+    every boundary of the geometry, against the table recorded before the two forms' geometries were folded into one
+    function (tests/golden/czt_sizes.json: per entry and length, the plan's bytes or the workspace's for 1, 2, 3, 1024 rows)."""
+    import json
+
+    from grafx_amd import _lib
+
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "czt_sizes.json")))
+    assert golden["lengths"] == czt_size_lengths() and golden["rows"] == list(CZT_SIZE_ROWS)
+    assert sorted(golden["bytes"]) == sorted(CZT_SIZE_ENTRIES)
+    table = czt_size_table(_lib.lib())
+    wrong = [(name, P, got, want) for name in CZT_SIZE_ENTRIES
+             for P, got, want in zip(golden["lengths"], table[name], golden["bytes"][name]) if got != want]
+    assert not wrong, wrong[:10]
+    # the table is not all zeros where a plan exists: both forms accept 3 and refuse an even length
+    i3, i4000 = golden["lengths"].index(3), golden["lengths"].index(4000)
+    for name in CZT_SIZE_ENTRIES:
+        assert all(v > 0 for v in golden["bytes"][name][i3]) and not any(golden["bytes"][name][i4000])
+
+
 def test_processors_refuse_cpu_tensors_and_missing_library(monkeypatch):
     import torch
 

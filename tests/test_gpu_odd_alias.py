@@ -171,6 +171,29 @@ def test_every_supported_tile_count(C):
     assert abs(lhs - rhs) <= 1e-5 * (z.double().norm() * g.double().norm()), f"C={C}: <Az, g> {lhs} vs <z, A'g> {rhs}"
 
 
+@pytest.mark.parametrize("C", _TILE_COUNTS)
+def test_every_supported_tile_count_one_row_per_transform(C):
+    """Two rows go two per transform by default (czt_pair), so the test above runs the pair form's kernels: the same
+    lengths with ops.ALIAS_PAIRS off, on the one-row kernels of C tiles themselves, both precisions, same tolerances."""
+    from grafx_amd import ops
+
+    P = (2 * C * 8192 + 1) // 3
+    P -= 1 - (P & 1)
+    assert ops.lib().gfx_odd_alias_workspace_bytes(1, P) == C * 8192 * 8, "the geometry did not pick this tile count"
+    torch.manual_seed(C)
+    z = torch.randn(2, P, device="cuda")
+    want = torch.fft.irfft(torch.fft.rfft(z.double()))
+    old = ops.ALIAS_PAIRS
+    ops.ALIAS_PAIRS = False
+    try:
+        for precise, tol in ((False, 3e-6), (True, 2e-7)):
+            got = ops.odd_alias(z, precise=precise)
+            err = (got.double() - want).abs().max() / want.abs().max()
+            assert err <= tol, f"C={C} P={P} precise={precise}: {err:.2e}"
+    finally:
+        ops.ALIAS_PAIRS = old
+
+
 @pytest.mark.parametrize("P,C", [(4607, 1), (135071, 2), (191071, 2)])
 def test_odd_alias_writes_strided_buffer_rows_in_place(P, C):
     """gfx_odd_alias_f32 with a row map: the aliased rows land directly in a strided (B, n, C, length) view of a signal buffer (the

@@ -50,6 +50,25 @@ def test_every_tile_count_of_the_pair_form(C):
     assert (got - single).abs().max() <= 3e-6 * single.abs().max()
 
 
+@pytest.mark.parametrize("C", PAIR_SIZES)
+def test_every_tile_count_of_the_pair_form_in_double_precision(C):
+    """The same lengths with precise=True: every column kernel of the double pair form, and above 36 tiles its middle step
+    in two passes (czt_pair_mid_kernel, then czt.hip's forward column pass), held to the bound the one-row double
+    transforms are held to (test_every_supported_tile_count: 2e-7 of the peak)."""
+    from grafx_amd import ops
+    from grafx_amd._lib import lib
+
+    P = (C * 8192 + 1) // 2
+    P -= 1 - (P & 1)
+    assert lib().gfx_odd_alias_pair_precise_workspace_bytes(2, P) == 2 * (C * 8192 * 8 + 256), (C, P)
+    torch.manual_seed(C)
+    z = torch.randn(5, P, device="cuda")
+    got = ops.odd_alias(z, precise=True)
+    want = _want(z)
+    err = (got.double() - want).abs().max() / want.abs().max()
+    assert err <= 2e-7, f"C={C} P={P}: {err:.2e}"
+
+
 @pytest.mark.parametrize("P", [3, 5, 7, 101, 4001, 8191, 8193, 135071, 147455, 191071, 258047])
 def test_pairs_match_float64_fft_and_slices_are_bit_equal(P):
     from grafx_amd import ops

@@ -38,12 +38,9 @@ done
 python3 $R/tools/ballistics_bench.py > $OUT/ballistics_bench.md 2> $OUT/ballistics_bench.err
 # the compressor stage + routing sum alone, fast and long poles
 ( python3 $R/tools/mix_bench.py; MIX_BENCH_Z=6 python3 $R/tools/mix_bench.py ) > $OUT/mix_bench.txt 2>&1
-# the odd-length aliasing alone: one row against two rows per chirp-z transform, with and without the per-row scaling
+# the odd-length aliasing alone: one row against two rows per chirp-z transform
 python3 $R/tools/alias_bench.py 2> /dev/null | grep "^|" > $OUT/alias_bench.md
 python3 $R/tools/alias_bench.py --rows 1024 --P 483999 299999 2> /dev/null | grep "^| [0-9]" >> $OUT/alias_bench.md
-echo "without the per-row scaling of a pair (GRAFX_ALIAS_PAIR_SCALE=0):" >> $OUT/alias_bench.md
-GRAFX_ALIAS_PAIR_SCALE=0 python3 $R/tools/alias_bench.py 2> /dev/null | grep "^| [0-9]" >> $OUT/alias_bench.md
-GRAFX_ALIAS_PAIR_SCALE=0 python3 $R/tools/alias_bench.py --rows 1024 --P 483999 299999 2> /dev/null | grep "^| [0-9]" >> $OUT/alias_bench.md
 # the compressor backward with its output gradient per row / in block form (training)
 python3 $R/tools/dyn_bwd_share_bench.py 2> /dev/null | grep -v amdgpu > $OUT/dyn_bwd_block_bench.txt
 ls $OUT | head -80
