@@ -696,6 +696,41 @@ class OversampledWaveshaperFn(torch.autograd.Function):
         return (*_waveshaper_backward(ctx, gy), None, None, None, None, None, None)
 
 
+class LimiterFn(torch.autograd.Function):
+    """The look-ahead limiter (ops.limiter, without a state) as one autograd node: forward is the fused inference kernel,
+    backward its one-pass adjoint (gfx_limiter_bwd_f32), which rebuilds the peaks, the windows' maxima and the gains in LDS
+    -- instead of the (R, L) detector, pooled maximum, gain and smoothed gain of a torch composition on autograd's tape.
+    Saved: x, log_ceiling and the taps.  ``taps``: float32 on the GPU; they get no gradient.  There is no double
+    backward."""
+
+    @staticmethod
+    def forward(ctx, x, log_ceiling, taps, lookahead, hold, compensate):
+        if taps.requires_grad:
+            raise ValueError("LimiterFn: the taps get no gradient (detach them)")
+        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+            x = x.contiguous()
+        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
+            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+        else:
+            y = ops.limiter(x, log_ceiling, taps, lookahead, hold, compensate)
+        ctx.save_for_backward(x, log_ceiling, taps)
+        ctx.cfg = (lookahead, hold, compensate)
+        return y.view(x.shape) if four else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, log_ceiling, taps = ctx.saved_tensors
+        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+            gy = gy.contiguous()
+        want = [name for name, need in zip(ops.LIMITER_GRADS, ctx.needs_input_grad) if need]
+        gx, gc = ops.limiter_bwd(x, gy, log_ceiling, taps, *ctx.cfg, out=_sink_for(x) if "x" in want else None, want=want)
+        return (None if gx is None else gx.view(x.shape), None if gc is None else gc.reshape(log_ceiling.shape), None, None,
+                None, None)
+
+
 class StftReverbIrFn(torch.autograd.Function):
     """The taps of STFTMaskedNoiseReverb (reverb.py:161-200, ms_to_lr, normalize_impulse) for n_fft = 384, hop = 192 as one
     autograd node: forward is the inference kernel (``ops.stft_reverb_ir``, "fft" schedule; times ``row_gain`` when

@@ -1359,6 +1359,99 @@ def oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offse
                       inverse_post_gain, remove_dc, dc, out, want, oversampling=(factor, h_up, offset_up, h_dn, offset_dn))
 
 
+# ----------------------------------------------------------------------------------------- look-ahead limiter
+LIMITER_MAX_TAPS = 1024
+LIMITER_MAX_WINDOW = 4096
+LIMITER_GRADS = ("x", "log_ceiling")
+
+
+def limiter_tile(window):
+    """Samples of a row that one workgroup of the limiter kernels produces (lim_tile in csrc/limiter.hip) for a window of
+    ``window`` = lookahead + 1 + hold samples: 4096 up to a window of 2795, falling to 1024 at 4096 (the backward tile
+    holds the peaks of tile + 2 window samples in LDS)."""
+    _int_in("limiter_tile", "window", window, 1, LIMITER_MAX_WINDOW)
+    return min(4096, max(1024, (155000 - 32 * window) // 16 // 512 * 512))
+
+
+def _limiter_args(what, x, log_ceiling, h, lookahead, hold, compensate):
+    """The configuration of the limiter pair, checked before anything is allocated -> (the signal's row map, R, C, L, the
+    (R,) ceilings, sigma, the samples a state carries)."""
+    _int_in(what, "lookahead", lookahead, 0, LIMITER_MAX_WINDOW - 1)
+    _int_in(what, "hold", hold, 0, LIMITER_MAX_WINDOW - 1 - lookahead)
+    _taps(what, "h", h, min(LIMITER_MAX_TAPS, lookahead + 1))
+    xmap, R, C, L = rowmap(x)
+    if log_ceiling.numel() != R:
+        raise ValueError(f"{what}: {log_ceiling.numel()} ceilings for {R} rows")
+    return xmap, R, C, L, log_ceiling.reshape(R), lookahead if compensate else 0, lookahead + hold + h.numel() - 1
+
+
+@_on_device
+def limiter(x, log_ceiling, h, lookahead, hold=0, compensate=False, out=None, state=None, return_state=False,
+            return_gain=False):
+    """Look-ahead peak limiter in one fused pass (gfx_limiter_f32): with T = exp(log_ceiling) per row, D = ``lookahead``,
+    M = D + 1 + ``hold`` and the N <= D + 1 smoothing taps ``h`` (float32 on the GPU, shared by every row, non-negative
+    and summing to one), p[k] = max_c |x[c,k]|, pk[q] = the largest of p[q-M+1 .. q], m[q] = T / pk[q] where pk[q] > T,
+    else 1, s[n] = sum_j h[j] m[n-j], and y[c,n] = x[c,n-D] s[n] -- or, with ``compensate``, y[c,n] = x[c,n] s[n+D], the
+    output aligned with the input and x taken as zero beyond its end.  |y| <= T up to rounding.
+
+    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``out`` may never share memory with ``x``.  ``state``: the
+    last M + N - 2 input samples, contiguous (R, C, M + N - 2), oldest first (None: silence); with ``state`` or
+    ``return_state`` the new state comes back too, and blocks cut anywhere give the bits of the one-call output (not with
+    ``compensate``, whose output needs samples the next block brings).  ``return_gain``: also the applied gain, (R, L).
+    -> y, or (y, [state], [gain]).  Equal bits from call to call; a row's result does not depend on the other rows."""
+    what = "limiter"
+    _require_gpu(x, log_ceiling, out)
+    xmap, R, C, L, log_ceiling, sigma, S = _limiter_args(what, x, log_ceiling, h, lookahead, hold, compensate)
+    stateful = state is not None or return_state
+    if stateful and compensate:
+        raise ValueError(f"{what}: compensate=True needs samples the next block brings; a state goes with compensate=False")
+    zi = _state(state, (R, C, S), what, "state")
+    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, zi, h))
+    zf = torch.empty((R, C, S), dtype=torch.float32, device=x.device) if stateful else None
+    gain = torch.empty((R, L), dtype=torch.float32, device=x.device) if return_gain else None
+    pin = _Pin()
+    with _timed("limiter_kernel", 8 * R * C * L):
+        check(lib().gfx_limiter_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, pin(log_ceiling), pin(h), h.numel(), lookahead, hold,
+                                    sigma, _ptr(zi), _ptr(zf), _ptr(gain), _stream()), "gfx_limiter_f32")
+    extra = (*((zf,) if stateful else ()), *((gain,) if return_gain else ()))
+    return (out, *extra) if extra else out
+
+
+@_on_device
+def limiter_bwd(x, gy, log_ceiling, h, lookahead, hold=0, compensate=False, out=None, want=LIMITER_GRADS, ws=None):
+    """Backward of :func:`limiter` (a call without a state) in one fused pass (gfx_limiter_bwd_f32) -> (gx, g_log_ceiling),
+    None for what ``want`` (any of LIMITER_GRADS) leaves out.  Nothing of the forward is needed but its arguments.
+
+    ``x``, ``gy``: (R,C,L) or strided (B,n,C,L) views; ``gx`` is ``out`` (any view of the signal's shape, apart from x and
+    gy) or a new (R,C,L) tensor, g_log_ceiling (R,).  The gradient of a window's maximum goes to its earliest sample, in
+    the lowest channel that holds the peak.  ``ws``: a uint8 workspace of at least gfx_limiter_bwd_ws_bytes(R, L,
+    lookahead, hold) bytes to reuse, 8-byte aligned.  The taps get no gradient.  Equal bits from call to call."""
+    what = "limiter_bwd"
+    _require_gpu(x, gy, log_ceiling, out)
+    xmap, R, C, L, log_ceiling, sigma, _ = _limiter_args(what, x, log_ceiling, h, lookahead, hold, compensate)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    _want(what, want, LIMITER_GRADS)
+    if not want:
+        raise ValueError(f"{what}: no gradient asked for")
+    reads = (x, gy, h)
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
+        if "x" in want:
+            gx, gxmap = dest
+    gc = torch.empty(R, dtype=torch.float32, device=x.device) if "log_ceiling" in want else None
+    pin = _Pin()
+    wsarg = (0, 0)
+    if gc is not None:
+        wsarg = _workspace(what, ws, lib().gfx_limiter_bwd_ws_bytes(R, L, lookahead, hold), x.device, pin, reads, align=8)
+    with _timed("limiter_bwd_kernel", (8 if gx is None else 12) * R * C * L):
+        check(lib().gfx_limiter_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, pin(log_ceiling), pin(h), h.numel(), lookahead,
+                                        hold, sigma, _ptr(gx), gxmap, _ptr(gc), *wsarg, _stream()), "gfx_limiter_bwd_f32")
+    return gx, gc
+
+
 # ----------------------------------------------------------------------------------------- reverb IR
 @_on_device
 def istft_basis(window):

@@ -30,6 +30,7 @@ from .filter import (
     PeakingFilter,
     StateVariableFilter,
 )
+from .limiter import Limiter, limiter_window
 from .nonlinear import (ChebyshevDistortion, PiecewiseTanhDistortion, PowerDistortion, TanhDistortion,
                         oversampling_filters)
 from .reverb import FilteredNoiseShapingReverb, STFTMaskedNoiseReverb

@@ -711,6 +711,39 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
                                        float* g_log_post_gain, float* g_p0, float* g_p1, void* ws, size_t ws_bytes,
                                        void* stream);
 
+/* ---- look-ahead peak limiter with hold and FIR smoothing, in one tile kernel each way ----
+ * For every row r of C channels, with T = exp(log_ceiling[r]), look-ahead D >= 0, hold H >= 0, window M = D + 1 + H and N
+ * smoothing taps w (a device array shared by every row; the caller's: non-negative, summing to one):
+ *   p[k]  = max_c |x[c, k]|                              x zero outside [0, L), or the state zi below 0
+ *   pk[q] = max_{0 <= j < M} p[q - j]                    ties take the earliest index a(q)
+ *   m[q]  = pk[q] > T ? T / pk[q] : 1
+ *   s[n]  = sum_{0 <= j < N} w[j] m[n - j]               float32, from 0.0, ascending j
+ *   y[c, n] = x[c, n + sigma - D] s[n + sigma]           0 <= n < L
+ * sigma = 0 is the causal limiter of latency D, sigma = D the delay-compensated one.  N <= D + 1 makes |y| <= T up to
+ * rounding.  zi / zf (null: none): the last S = M + N - 2 input samples, (R, C, S) contiguous, oldest first; zf is a copy of
+ * the last S samples of zi || x, and blocks cut anywhere, each entering with the zf of the one before, give the bits of
+ * the one-call output.  gain (null: not wanted): (R, L) contiguous, the applied s[n + sigma].  y is addressed through its
+ * own row map and may not share memory with x (tiles read each other's halos of x).  Everything between x and y exists
+ * in LDS only: 8 bytes of traffic per sample and channel.  Tile: T(M) = min(4096, max(1024, (155000 - 32 M) / 16 rounded
+ * down to a multiple of 512)) samples of a row per workgroup; rows times tiles ride on grid.x.
+ * gfx_limiter_bwd_f32 is the adjoint for a call without a state (gy, gx through their own row maps; either of gx and
+ * g_log_ceiling (R) may be null, not both): the gradient of a window's maximum goes to the sample a(q), in the channel
+ * of the lowest index that holds the peak.  The taps get no gradient.  The ceiling's sums are stored per tile in ws,
+ *   gfx_limiter_bwd_ws_bytes = 8 R ceil(L / T(M)),   0 for a bad argument,
+ * as doubles (ws 8-byte aligned) -- a tile's sum can be a thousand times the row's -- and added in a fixed order.  No atomics in either entry: equal bits from run to run, and a row's result does
+ * not depend on the other rows of the call.
+ * GFX_EINVAL before any launch: a null x, y / gy, log_ceiling or w; R, C or L <= 0; D or H < 0; M > 4096; N outside
+ * 1 .. 1024 or above D + 1; sigma other than 0 and D; a state together with sigma > 0; zi overlapping zf; an empty row map
+ * or one with a negative stride; an output that overlaps an input; more than 2^31 - 1 row-channels or workgroups; a
+ * ceiling gradient without a workspace or with a misaligned one.  A workspace that is too small is GFX_ENOSPC. */
+int gfx_limiter_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, int64_t R, int64_t C, int64_t L,
+                    const float* log_ceiling, const float* w, int64_t N, int64_t D, int64_t H, int64_t sigma, const float* zi,
+                    float* zf, float* gain, void* stream);
+size_t gfx_limiter_bwd_ws_bytes(int64_t R, int64_t L, int64_t D, int64_t H);
+int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R, int64_t C, int64_t L,
+                        const float* log_ceiling, const float* w, int64_t N, int64_t D, int64_t H, int64_t sigma, float* gx,
+                        gfx_rowmap_t omap, float* g_log_ceiling, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- multi-resolution STFT magnitude loss, one resolution per call ------------------------
  * replaces the call site of a training step's loss: torch.stft of the prediction and of the target, their magnitudes
  * and logs, and autograd through all of them.  For rows p = pred[r], t = target[r] of L samples,
