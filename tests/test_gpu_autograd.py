@@ -229,11 +229,14 @@ def test_native_dynamics_backward_matches_torch_autograd_of_the_same_formulas(ga
     g = diff.log_gain(torch.log(e + 1e-5), p["log_threshold"] - 6, p["log_ratio"], p["log_knee"], knee, gate)
     y_torch = torch.exp(g)[:, None, :] * x
     assert (y_native - y_torch).abs().max() <= 2e-5 * y_torch.abs().max()
-    # No float64 arbiter here: a double-precision evaluation of the same expressions takes the other knee branch for the
-    # few samples that sit on a boundary, and the gradients jump there (measured: both float32 results 3e-2 .. 3e-1 of
-    # the peak away from it, 1e-5 from each other).  Flat bounds instead, at three times the largest error measured on
-    # MI355X (round 5: 3.5e-5 for the input gradient, 1.1e-5 for the parameters; most configurations ~1e-6) -- they were
-    # 2e-3 through round 4.
+    # The float64 arbiter of these kernels is tests/test_gpu_dynamics_bwd_float64.py: every launch path of ops.dynamics_bwd,
+    # ops.dyn_gain_bwd and ops.dyn_dx against float64 autograd at 1e-5 of each row, on inputs whose thresholds are placed in
+    # a gap of the row's log-envelope.  THESE thresholds are drawn at random, so a double-precision evaluation of the same
+    # expressions takes the other knee branch for the few samples that sit on a boundary, and the gradients jump there
+    # (measured: both float32 results 3e-2 .. 3e-1 of the peak away from it, 1e-5 from each other).  What this test adds is
+    # DynamicsFn itself (the node, its chain rule, the default launch path) on such inputs: flat bounds, at three times the
+    # largest error measured on MI355X (round 5: 3.5e-5 for the input gradient, 1.1e-5 for the parameters; most
+    # configurations ~1e-6) -- they were 2e-3 through round 4.
     for name, a, b in zip(["x"] + list(p), grads(y_native), grads(y_torch)):
         if b is None or (knee == "hard" and name == "log_knee") or (not smoother and name == "z"):
             continue
