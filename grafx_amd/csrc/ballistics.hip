@@ -27,11 +27,7 @@
 // The output is therefore ALWAYS the float32 sequential recursion; speculation only decides how fast it is produced.
 // Tiles of 64 rows x 64 samples go through LDS so that HBM sees 256-byte segments while each lane walks its own row;
 // the next tile's loads are in flight (registers) while the current one is walked.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "dyn_gain.hpp"
 
 // every product and sum of this file rounds on its own, as numpy / numba / torch's CPU kernels do: a fused multiply-add
@@ -70,11 +66,6 @@ struct BlArgs {
     const float* zi;
     float* zf;
 };
-
-__device__ __forceinline__ int64_t row_off(const gfx_rowmap_t& m, int64_t r, int c) {
-    const int64_t q = r / m.inner, rem = r - q * m.inner;
-    return q * m.stride_outer + rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
 
 // one step; both candidates are formed and the comparison picks one -- the same values as
 // `c = x < y ? at : rt; y = (1 - c) * y + c * x` with separately rounded products, on a dependency chain of three
@@ -199,8 +190,8 @@ __global__ __launch_bounds__(64) void ballistics_walk_kernel(BlArgs a) {
         const int64_t v = vbase + p * RPP + cr;
         const int64_t rrow = v >> a.lg;
         const int64_t pos0 = (int64_t)(int)(v & (nchunk - 1)) * a.T - warm + cc;
-        yoff[p] = DST == 1 ? row_off(a.ymap, rrow < a.R ? rrow : 0, 0) + pos0 : rrow * a.L + pos0;
-        if (SRC == 1) soff[p] = row_off(a.xmap, rrow < a.R ? rrow : 0, 0) + pos0;
+        yoff[p] = DST == 1 ? row_off64(a.ymap, rrow < a.R ? rrow : 0, 0) + pos0 : rrow * a.L + pos0;
+        if (SRC == 1) soff[p] = row_off64(a.xmap, rrow < a.R ? rrow : 0, 0) + pos0;
     }
     const unsigned chunk_c = (unsigned)((vbase + cr) & (nchunk - 1));
     auto pass_pos = [&](int p, int ti, bool& live) {      // position in its row of pass p's samples at tile ti
@@ -363,7 +354,6 @@ static int launch_walk(int rpw, const BlArgs& a, hipStream_t st) {
     return GFX_OK;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // u: SRC 0 rows / SRC 1 signal.  Without a workspace (the flags of the two-pass form) every row is walked whole.
 template <int SRC, int DST = 0>

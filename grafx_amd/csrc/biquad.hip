@@ -32,12 +32,6 @@
 // ssm_quirk: upstream's "ssm" backend drives the recursive part of every section with the ORIGINAL input
 // instead of the previous section's output (core/iir.py:226-246 index `input_signal`, not `x`); for K = 1
 // the two backends agree, for K > 1 this flag reproduces what "ssm" actually returns.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
-
 #include "biquad_common.hpp"
 
 namespace gfx {
@@ -58,10 +52,6 @@ struct BqArgs {
 static inline size_t bq_lds_bytes(int64_t K, int RL) {
     return (size_t)(BQ_T / RL) * K * sizeof(SecConst) + (RL == 64 ? (size_t)K * 16 * 4 * sizeof(f2) : 0);
 }
-static inline bool bq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool bq_map_vec(const gfx_rowmap_t& m) {
-    return m.stride_outer % 4 == 0 && m.stride_inner % 4 == 0 && m.stride_ch % 4 == 0;
-}
 
 template <bool STATE>
 static int bq_launch(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, const float* Bs, const float* As,
@@ -74,7 +64,7 @@ static int bq_launch(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t y
     a.xmap = xmap; a.ymap = ymap; a.L = L;
     a.Cin = (int)C_in; a.Cf = (int)C_f; a.Cout = (int)(C_in > C_f ? C_in : C_f);
     a.K = (int)K; a.quirk = ssm_quirk ? 1 : 0;
-    a.vec = bq_aligned16(x) && bq_aligned16(y) && bq_map_vec(xmap) && bq_map_vec(ymap);
+    a.vec = aligned16(x) && aligned16(y) && map_vec(xmap) && map_vec(ymap);
     a.total = R * a.Cout;
     const int64_t pairs = (a.total + 1) / 2;
     // sixteen lanes per pair where such waves fill the chip, else the whole wave
@@ -85,15 +75,11 @@ static int bq_launch(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t y
     const size_t lds = bq_lds_bytes(K, RL);
     if constexpr (STATE) {
         auto kern = narrow ? biquad_cascade_state_kernel<16, false> : biquad_cascade_state_kernel<64, true>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return GFX_ELAUNCH;
+        if (allow_lds(kern, lds) != GFX_OK) return GFX_ELAUNCH;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BQ_T), lds, (hipStream_t)stream, x, y, Bs, As, a, zi, zf);
     } else {
         auto kern = narrow ? biquad_cascade_kernel<16, false> : biquad_cascade_kernel<64, true>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return GFX_ELAUNCH;
+        if (allow_lds(kern, lds) != GFX_OK) return GFX_ELAUNCH;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BQ_T), lds, (hipStream_t)stream, x, y, Bs, As, a);
     }
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(BQ_T) void biquad_bwd_checkpoint_kernel(const float
     if (!p.live[0]) return;   // (the whole workgroup: one wave, one pair)
     const float* xr[2];
 #pragma unroll
-    for (int ch = 0; ch < 2; ++ch) xr[ch] = x + brow_off(a.xmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
+    for (int ch = 0; ch < 2; ++ch) xr[ch] = x + row_off(a.xmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
     f4* wsp = ws + (size_t)((a.pair0 + (int64_t)blockIdx.x) * a.ntiles) * a.K;
     for (int64_t t = 0; t < a.ntiles; ++t) {
         const bool last = t + 1 == a.ntiles;   // its entering states are all that is wanted of the last tile
@@ -318,9 +318,9 @@ __global__ __launch_bounds__(BQ_T) void biquad_bwd_adjoint_kernel(const float* _
     float* gxr[2];
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
-        xr[ch] = x + brow_off(a.xmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
-        gr[ch] = g + brow_off(a.gmap, p.r[ch], p.c[ch]);
-        gxr[ch] = gx == nullptr ? nullptr : gx + brow_off(a.gxmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
+        xr[ch] = x + row_off(a.xmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
+        gr[ch] = g + row_off(a.gmap, p.r[ch], p.c[ch]);
+        gxr[ch] = gx == nullptr ? nullptr : gx + row_off(a.gxmap, p.r[ch], a.Cin == 1 ? 0 : p.c[ch]);
     }
     const bool fold_x = a.Cin == 1 && a.Cout == 2;   // the pair is the two channels of one row, which read one x
     const f4* wsp = ws + (size_t)((a.pair0 + (int64_t)blockIdx.x) * a.ntiles) * a.K;
@@ -505,10 +505,6 @@ __global__ __launch_bounds__(BQ_T) void biquad_bwd_adjoint_kernel(const float* _
     }
 }
 
-static inline bool bb_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool bb_map_vec(const gfx_rowmap_t& m) {
-    return m.stride_outer % 4 == 0 && m.stride_inner % 4 == 0 && m.stride_ch % 4 == 0;
-}
 static inline int64_t bb_pairs(int64_t R, int64_t C_out) { return (R * C_out + 1) / 2; }
 static inline int64_t bb_tiles(int64_t L) { return (L + BB_TILE - 1) / BB_TILE; }
 constexpr int64_t BB_MAX_BLOCKS = 1 << 22;   // pairs per launch
@@ -535,7 +531,7 @@ int gfx_biquad_cascade_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* g
     const int64_t C_out = C_in > C_f ? C_in : C_f;
     // a broadcast channel's sum is taken inside the pair, which holds a row's channels only when there are two of them
     if (C_out > 2 && ((C_f == 1 && (gB || gA)) || (C_in == 1 && gx))) return GFX_EINVAL;
-    if (!ws ||!bb_aligned16(ws) || ws_bytes < gfx_biquad_cascade_bwd_ws_bytes(R, C_out, K, L)) return GFX_EINVAL;
+    if (!ws ||!aligned16(ws) || ws_bytes < gfx_biquad_cascade_bwd_ws_bytes(R, C_out, K, L)) return GFX_EINVAL;
     BbArgs a;
     a.xmap = xmap; a.gmap = gmap; a.gxmap = gx ? gxmap : xmap;
     a.L = L; a.total = R * C_out; a.ntiles = bb_tiles(L);
@@ -543,14 +539,11 @@ int gfx_biquad_cascade_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* g
     a.G = 1;
     while (a.G * a.G < a.K) ++a.G;   // ceil(sqrt(K)) sections a group
     a.NG = (a.K + a.G - 1) / a.G;
-    a.xvec = bb_aligned16(x) && bb_map_vec(xmap);
-    a.gvec = bb_aligned16(g) && bb_map_vec(gmap);
-    a.gxvec = gx && bb_aligned16(gx) && bb_map_vec(gxmap);
+    a.xvec = aligned16(x) && map_vec(xmap);
+    a.gvec = aligned16(g) && map_vec(gmap);
+    a.gxvec = gx && aligned16(gx) && map_vec(gxmap);
     const size_t lds_a = bb_checkpoint_lds_bytes(K), lds_b = bb_adjoint_lds_bytes(K, a.G, a.NG);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(biquad_bwd_checkpoint_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(biquad_bwd_adjoint_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) != hipSuccess)
+    if (allow_lds(biquad_bwd_checkpoint_kernel, lds_a) != GFX_OK || allow_lds(biquad_bwd_adjoint_kernel, lds_b) != GFX_OK)
         return GFX_ELAUNCH;
     const int64_t pairs = bb_pairs(R, C_out);
     for (int64_t p0 = 0; p0 < pairs; p0 += BB_MAX_BLOCKS) {

@@ -1,10 +1,6 @@
 // What the biquad cascade kernels share: biquad.hip (forward) and biquad_bwd.hip (backward) both include it.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 
 namespace gfx {
 
@@ -55,12 +51,6 @@ __device__ __forceinline__ f2 last_lane(f2 v) {
     const float x = v.x, y = v.y;
     return f2{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63)),
               __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y), 63))};
-}
-
-__device__ __forceinline__ int64_t brow_off(const gfx_rowmap_t& m, int64_t r, int c) {
-    const unsigned inner = (unsigned)m.inner, rr = (unsigned)r;
-    const unsigned q = rr / inner, rem = rr - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
 }
 
 }  // namespace gfx

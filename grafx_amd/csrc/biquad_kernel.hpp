@@ -38,8 +38,8 @@ __global__ __launch_bounds__(BQ_T) void biquad_cascade_kernel(const float* __res
         const int64_t rc = live[ch] ? rc0 + ch : (live[0] ? rc0 : 0);   // a missing partner re-reads its neighbour, stores nothing
         const int64_t r = rc / a.Cout;
         const int c = (int)(rc - r * a.Cout);
-        xr[ch] = x + brow_off(a.xmap, r, a.Cin == 1 ? 0 : c);
-        yr[ch] = y + brow_off(a.ymap, r, c);
+        xr[ch] = x + row_off(a.xmap, r, a.Cin == 1 ? 0 : c);
+        yr[ch] = y + row_off(a.ymap, r, c);
         B[ch] = Bs + ((r * a.Cf + (a.Cf == 1 ? 0 : c)) * a.K) * 3;
         A[ch] = As + ((r * a.Cf + (a.Cf == 1 ? 0 : c)) * a.K) * 3;
     }

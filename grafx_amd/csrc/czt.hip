@@ -351,8 +351,8 @@ template <typename T> static const typename Prec<T>::T2* czt_twiddles(hipStream_
 template <typename T>
 static const typename Prec<T>::T2* tile_setup(bool plan, hipStream_t st) {
     const typename Prec<T>::T2* tw = czt_twiddles<T>(st);
-    const bool ok = tw && (plan ? czt_allow_lds(czt_rows_kernel<T, true>, Prec<T>::lds_bytes)
-                                : czt_allow_lds(czt_rows_kernel<T, false>, Prec<T>::lds_bytes));
+    const bool ok = tw && (plan ? allow_lds(czt_rows_kernel<T, true>, Prec<T>::lds_bytes) == GFX_OK
+                                : allow_lds(czt_rows_kernel<T, false>, Prec<T>::lds_bytes) == GFX_OK);
     return ok ? tw : nullptr;
 }
 

@@ -6,7 +6,7 @@
 
 #include <cstdint>
 
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "fft_tile.hpp"
 #include "fft_tile_f64.hpp"
 #include "small_dft.hpp"
@@ -344,11 +344,5 @@ void czt_chirp_tables(double2* cP, double2* cQ, int64_t P, hipStream_t st);
 // a chirp sequence's spectrum in the tile pass's layout (buf: g.NFFT points of scratch), with or without outer levels
 void czt_chirp_spectrum(const CztGeom& g, ChirpSeq cs, float2* buf, float2* spec, const float2* tw, hipStream_t st);
 void czt_chirp_spectrum(const CztGeom& g, ChirpSeq cs, double2* buf, double2* spec, const double2* tw, hipStream_t st);
-
-template <typename K>
-static bool czt_allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
-           hipSuccess;
-}
 
 }  // namespace gfx

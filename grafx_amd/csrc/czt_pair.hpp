@@ -559,8 +559,8 @@ static int pair_chain_one_level(const CztGeom& g, const PairTables<T>& t, const 
                                 int64_t len, int64_t rows, hipStream_t st) {
     using T2 = typename Prec<T>::T2;
     constexpr size_t LV = lv_lds_bytes<CC>(), LVH = lv_lds_bytes<CC>(lv_half<CC>());
-    if (!czt_allow_lds(czt_pair_lv_in_kernel<T, CC>, (int)LVH) || !czt_allow_lds(czt_pair_lv_mid_kernel<T, CC>, (int)LV) ||
-        !czt_allow_lds(czt_pair_lv_out_kernel<T, CC>, (int)LVH))
+    if (allow_lds(czt_pair_lv_in_kernel<T, CC>, LVH) != GFX_OK || allow_lds(czt_pair_lv_mid_kernel<T, CC>, LV) != GFX_OK ||
+        allow_lds(czt_pair_lv_out_kernel<T, CC>, LVH) != GFX_OK)
         return GFX_ELAUNCH;
     const int64_t pairs = (rows + 1) / 2;
     const dim3 grid(TILE_M / LV_COLS, (unsigned)pairs), blk(256);

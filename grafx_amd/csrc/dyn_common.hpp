@@ -3,12 +3,9 @@
 // scan, the bounded 4-sample loads / stores, the launch arguments, the pole-table layout and the host-side launch helpers.
 // Device code is __forceinline__, host code static inline, the rest constexpr.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <type_traits>
 
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "dyn_gain.hpp"
 
 namespace gfx {
@@ -26,12 +23,6 @@ constexpr int DP_ONESHOT = 80, DP_HIST = 81, DP_LOOKBACK = 82, DP_LB_TILES = 83,
 constexpr int OS_SUB = 2;                  // 256-sample sub-tiles per wave tile (1: 5.1, 2: 6.0, 4: 5.6 TB/s -- profiles/r3/dyn_oneshot_ablation.txt)
 constexpr int OS_WTILE = 64 * DE * OS_SUB; // 512 samples per wave (a multiple of 256: the history offsets assume it)
 constexpr int OS_GTILE = OS_WTILE * (DT / 64);   // 2048 samples per workgroup
-
-__device__ __forceinline__ int64_t drow_off(const gfx_rowmap_t& m, int64_t r, int c) {
-    const unsigned inner = (unsigned)m.inner, rr = (unsigned)r;  // both fit 32 bits (launchers check)
-    const unsigned q = rr / inner, rem = rr - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
 
 // a^k for integer k >= 0, rounded once from double (keeps long decays accurate)
 __device__ __forceinline__ float powk(double log_a, double k) { return (float)exp(k * log_a); }

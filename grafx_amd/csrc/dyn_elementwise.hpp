@@ -12,8 +12,8 @@ namespace gfx {
 __global__ void energy_kernel(const float* __restrict__ x, gfx_rowmap_t xmap, float* __restrict__ e, int64_t R, int64_t L, int C) {
     const float invC = 1.0f / (float)C;
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
-        const float* x0 = x + drow_off(xmap, r, 0);
-        const float* x1 = x + drow_off(xmap, r, C == 2 ? 1 : 0);
+        const float* x0 = x + row_off(xmap, r, 0);
+        const float* x1 = x + row_off(xmap, r, C == 2 ? 1 : 0);
         for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < L; n += (int64_t)gridDim.x * blockDim.x) {
             const float a = x0[n], b = x1[n];
             e[r * L + n] = (C == 2 ? (a * a + b * b) : a * a) * invC;
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(DT) void onepole_kernel(const float* __restrict__ u
     const int64_t r = blockIdx.x;
     OnePole p;
     onepole_setup(p, z_alpha[r], N, t & 63);
-    const float* in0 = ESRC ? u + drow_off(xmap, r, 0) : u + r * L;
-    const float* in1 = ESRC ? u + drow_off(xmap, r, C == 2 ? 1 : 0) : nullptr;
+    const float* in0 = ESRC ? u + row_off(xmap, r, 0) : u + r * L;
+    const float* in1 = ESRC ? u + row_off(xmap, r, C == 2 ? 1 : 0) : nullptr;
     uint32_t* rm = rowmax ? rowmax + r : nullptr;
     // the FIR has exactly N taps: when Lout > L the tail still needs the a^N term once n >= N
     if (p.trunc)
@@ -138,8 +138,8 @@ __global__ void apply_gain_kernel(const float* __restrict__ x, gfx_rowmap_t xmap
                                   int exp_gain) {
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y)
     for (int c = 0; c < C; ++c) {
-        const float* xr = x + drow_off(xmap, r, c);
-        float* yr = y + drow_off(ymap, r, c);
+        const float* xr = x + row_off(xmap, r, c);
+        float* yr = y + row_off(ymap, r, c);
         for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < L; n += (int64_t)gridDim.x * blockDim.x) {
             const float gv = g[r * L + n];
             yr[n] = (exp_gain ? expf(gv) : gv) * xr[n];
@@ -160,10 +160,10 @@ __global__ __launch_bounds__(256) void dyn_gain_apply_kernel(const float* __rest
         const unsigned pr = (unsigned)r % prows;
         Knee q;
         knee_setup(q, log_threshold[pr], log_ratio[pr], log_knee ? log_knee[pr] : 0.0f, knee, gate);
-        const float* x0 = x + drow_off(xmap, r, 0);
-        const float* x1 = x + drow_off(xmap, r, C == 2 ? 1 : 0);
-        float* y0 = y + drow_off(ymap, r, 0);
-        float* y1 = y + drow_off(ymap, r, C == 2 ? 1 : 0);
+        const float* x0 = x + row_off(xmap, r, 0);
+        const float* x1 = x + row_off(xmap, r, C == 2 ? 1 : 0);
+        float* y0 = y + row_off(ymap, r, 0);
+        float* y1 = y + row_off(ymap, r, C == 2 ? 1 : 0);
         const float* er = env + r * L;
         for (int64_t n = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * DE; n < L; n += (int64_t)gridDim.x * blockDim.x * DE) {
             float e[DE], a[DE], b[DE] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -188,8 +188,8 @@ __global__ void stereo_gain_kernel(const float* __restrict__ x, gfx_rowmap_t xma
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y)
     for (int c = 0; c < 2; ++c) {
         const float g = expf(log_gain[2 * r + c]);
-        const float* xr = x + drow_off(xmap, r, Cin == 2 ? c : 0);
-        float* yr = y + drow_off(ymap, r, c);
+        const float* xr = x + row_off(xmap, r, Cin == 2 ? c : 0);
+        float* yr = y + row_off(ymap, r, c);
         for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < L; n += (int64_t)gridDim.x * blockDim.x)
             yr[n] = xr[n] * g;
     }

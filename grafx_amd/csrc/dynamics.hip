@@ -139,10 +139,10 @@ __global__ __launch_bounds__(DT, 1) void dyn_fused_kernel(const float* __restric
     if (a.smoother == 1) onepole_setup(p, z_alpha[pr], a.N, t & 63);
     Knee q;
     knee_setup(q, log_threshold[pr], log_ratio[pr], log_knee ? log_knee[pr] : 0.0f, a.knee, a.gate);
-    const float* x0 = x + drow_off(a.xmap, r, 0);
-    const float* x1 = x + drow_off(a.xmap, r, a.C == 2 ? 1 : 0);
-    float* y0 = y + drow_off(a.ymap, r, 0);
-    float* y1 = y + drow_off(a.ymap, r, a.C == 2 ? 1 : 0);
+    const float* x0 = x + row_off(a.xmap, r, 0);
+    const float* x1 = x + row_off(a.xmap, r, a.C == 2 ? 1 : 0);
+    float* y0 = y + row_off(a.ymap, r, 0);
+    float* y1 = y + row_off(a.ymap, r, a.C == 2 ? 1 : 0);
     const int64_t ntiles = (a.L + DTILE - 1) / DTILE;
     const int64_t t_lo = chunk * a.chunk_tiles, t_hi = min(t_lo + a.chunk_tiles, ntiles);
     if (t_lo >= t_hi) return;
@@ -481,8 +481,8 @@ __global__ __launch_bounds__(DT) void dyn_oneshot_kernel(const float* __restrict
     Knee q;
     knee_setup(q, log_threshold[pr], log_ratio[pr], log_knee ? log_knee[pr] : 0.0f, a.knee, a.gate);
     float ga[OS_SUB][DE], gb[OS_SUB][DE];
-    os_tile(a, x + drow_off(a.xmap, r, 0), x + drow_off(a.xmap, r, a.C == 2 ? 1 : 0), y + drow_off(a.ymap, r, 0),
-            y + drow_off(a.ymap, r, a.C == 2 ? 1 : 0), u1 ? u1 + (int64_t)r * a.L : nullptr, tb, q, s, lane, ga, gb,
+    os_tile(a, x + row_off(a.xmap, r, 0), x + row_off(a.xmap, r, a.C == 2 ? 1 : 0), y + row_off(a.ymap, r, 0),
+            y + row_off(a.ymap, r, a.C == 2 ? 1 : 0), u1 ? u1 + (int64_t)r * a.L : nullptr, tb, q, s, lane, ga, gb,
             looks_back ? lb.gran + (size_t)r * lb.ntiles : nullptr);
 }
 
@@ -641,15 +641,15 @@ __global__ __launch_bounds__(DT, 1) void dyn_oneshot_mix_kernel(const float* __r
             const unsigned pr = r % a.prows;
             const float* tb = tab + (size_t)pr * DP_TAB;
             const uint64_t code = (uint64_t)m.sched[jr];
-            float* y0 = y + drow_off(a.ymap, r, 0);
-            float* y1 = y + drow_off(a.ymap, r, STEREO ? 1 : 0);
+            float* y0 = y + row_off(a.ymap, r, 0);
+            float* y1 = y + row_off(a.ymap, r, STEREO ? 1 : 0);
             float ga[OS_SUB][DE], gb[OS_SUB][DE];
             const bool looks_back = tb[DP_LOOKBACK] != 0.0f;
             if (tb[DP_ONESHOT] != 0.0f || looks_back) {   // uniform
                 Knee q;
                 knee_setup(q, log_threshold[pr], log_ratio[pr], KIND != 0 ? log_knee[pr] : 0.0f, KIND, GATE ? 1 : 0);
                 OsIn in;
-                os_load<true>(a, x + drow_off(a.xmap, r, 0), x + drow_off(a.xmap, r, STEREO ? 1 : 0), true, tb, s, lane, in);
+                os_load<true>(a, x + row_off(a.xmap, r, 0), x + row_off(a.xmap, r, STEREO ? 1 : 0), true, tb, s, lane, in);
                 os_finish<true>(a, in, m.skip_rows ? nullptr : y0, y1, true, u1 ? u1 + (int64_t)r * a.L : nullptr, tb, q, s, lane,
                                 ga, gb, looks_back ? lb.gran + (size_t)r * lb.ntiles : nullptr);
             } else if (((unsigned)code & 15u) != 0u) {   // the row kernel's row: read back what it wrote
@@ -681,8 +681,8 @@ __global__ __launch_bounds__(DT, 1) void dyn_oneshot_mix_kernel(const float* __r
                 knee_setup(q, log_threshold[pr], log_ratio[pr], KIND != 0 ? log_knee[pr] : 0.0f, KIND, GATE ? 1 : 0);
                 const float carry = pkind == 2 ? os_lookback(tb, s, lane, lb.gran + (size_t)prow * lb.ntiles) : pcarry;
                 float ga[OS_SUB][DE], gb[OS_SUB][DE];
-                os_emit_lean<true>(a, pxa, pxb, pexcl, ptotal, carry, m.skip_rows ? nullptr : y + drow_off(a.ymap, prow, 0),
-                                   y + drow_off(a.ymap, prow, STEREO ? 1 : 0), u1 ? u1 + (int64_t)prow * a.L : nullptr, tb, q, s,
+                os_emit_lean<true>(a, pxa, pxb, pexcl, ptotal, carry, m.skip_rows ? nullptr : y + row_off(a.ymap, prow, 0),
+                                   y + row_off(a.ymap, prow, STEREO ? 1 : 0), u1 ? u1 + (int64_t)prow * a.L : nullptr, tb, q, s,
                                    lane, ga, gb);
                 settle(pcode, ga, gb);
             } else {
@@ -701,7 +701,7 @@ __global__ __launch_bounds__(DT, 1) void dyn_oneshot_mix_kernel(const float* __r
             float cexcl[OS_SUB], ctotal[OS_SUB], ccarry = 0.0f;
             int ckind = 3;
             if ((NA != 0 && tb[DP_ONESHOT] != 0.0f) || looks_back) {   // uniform
-                os_load<true>(a, x + drow_off(a.xmap, r, 0), x + drow_off(a.xmap, r, STEREO ? 1 : 0), true, tb, s, lane, in);
+                os_load<true>(a, x + row_off(a.xmap, r, 0), x + row_off(a.xmap, r, STEREO ? 1 : 0), true, tb, s, lane, in);
                 OsMid cmid;
                 os_scan<true>(a, in, tb, s, lane, cmid, looks_back ? lb.gran + (size_t)r * lb.ntiles : nullptr);
 #pragma unroll
@@ -712,8 +712,8 @@ __global__ __launch_bounds__(DT, 1) void dyn_oneshot_mix_kernel(const float* __r
                 ccarry = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cmid.carry)));
                 ckind = looks_back ? 2 : 1;
             } else if (NA != 0 && ((unsigned)code & 15u) != 0u) {   // the row kernel's row: read back what it wrote
-                const float* y0 = y + drow_off(a.ymap, r, 0);
-                const float* y1 = y + drow_off(a.ymap, r, STEREO ? 1 : 0);
+                const float* y0 = y + row_off(a.ymap, r, 0);
+                const float* y1 = y + row_off(a.ymap, r, STEREO ? 1 : 0);
 #pragma unroll
                 for (int k = 0; k < OS_SUB; ++k) {
                     ld4<true>(y0, n0 + 256 * k, a.L, true, in.xa[k]);

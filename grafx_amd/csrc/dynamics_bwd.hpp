@@ -138,7 +138,7 @@ __global__ __launch_bounds__(DT) void dyn_bwd_u1_kernel(const float* __restrict_
     if (tab && tab[(size_t)r * DP_TAB + DP_ONESHOT] != 0.0f) return;   // a one-shot row rebuilds its scan in its own tiles
     OnePole p;
     onepole_setup(p, z_alpha[r], a.N, t & 63);
-    dyn_bwd_u1_stream(a, p, x + drow_off(a.xmap, r, 0), x + drow_off(a.xmap, r, a.C == 2 ? 1 : 0), u1 + r * a.L, slots, t);
+    dyn_bwd_u1_stream(a, p, x + row_off(a.xmap, r, 0), x + row_off(a.xmap, r, a.C == 2 ? 1 : 0), u1 + r * a.L, slots, t);
 }
 
 // dL/d(smoothed energy) at four (reversed-walk) positions from the samples, output gradients and scan values there;
@@ -280,12 +280,12 @@ __global__ __launch_bounds__(DT) void dyn_bwd_c_kernel(const float* __restrict__
     if (oneshot_tab && oneshot_tab[(size_t)r * DP_TAB + DP_ONESHOT] != 0.0f) return;   // dyn_bwd_oneshot_kernel's row
     OnePole p;
     onepole_setup(p, z_alpha[r], a.N, t & 63);
-    const float* x0 = x + drow_off(a.xmap, r, 0);
-    const float* x1 = x + drow_off(a.xmap, r, a.C == 2 ? 1 : 0);
-    const float* g0 = gy + drow_off(gmap, r, 0);
-    const float* g1 = gy + drow_off(gmap, r, a.C == 2 ? 1 : 0);
-    float* o0 = gx + drow_off(a.ymap, r, 0);
-    float* o1 = gx + drow_off(a.ymap, r, a.C == 2 ? 1 : 0);
+    const float* x0 = x + row_off(a.xmap, r, 0);
+    const float* x1 = x + row_off(a.xmap, r, a.C == 2 ? 1 : 0);
+    const float* g0 = gy + row_off(gmap, r, 0);
+    const float* g1 = gy + row_off(gmap, r, a.C == 2 ? 1 : 0);
+    float* o0 = gx + row_off(a.ymap, r, 0);
+    float* o1 = gx + row_off(a.ymap, r, a.C == 2 ? 1 : 0);
     Knee q;
     knee_setup(q, log_threshold[r], log_ratio[r], log_knee ? log_knee[r] : 0.0f, a.knee, a.gate);
     double pole = 0.0, acc[3] = {0.0, 0.0, 0.0};    // per-thread sums over the whole row: double (hundreds of terms of both signs)
@@ -358,12 +358,12 @@ __global__ __launch_bounds__(DT, 3) void dyn_bwd_oneshot_kernel(const float* __r
     if (tb[DP_ONESHOT] == 0.0f) return;                 // dyn_bwd_c_kernel's row (uniform)
     const int64_t s = (int64_t)grp * OS_GTILE + (int64_t)wave * OS_WTILE;     // first WALK position of this wave's tile
     const int64_t L = s < a.L ? a.L : 0;                // a wave past the row end reads zeros and stores nothing
-    const float* x0 = x + drow_off(a.xmap, r, 0);
-    const float* x1 = x + drow_off(a.xmap, r, a.C == 2 ? 1 : 0);
-    const float* g0 = gy + drow_off(gmap, r, 0);
-    const float* g1 = gy + drow_off(gmap, r, a.C == 2 ? 1 : 0);
-    float* o0 = gx + drow_off(a.ymap, r, 0);
-    float* o1 = gx + drow_off(a.ymap, r, a.C == 2 ? 1 : 0);
+    const float* x0 = x + row_off(a.xmap, r, 0);
+    const float* x1 = x + row_off(a.xmap, r, a.C == 2 ? 1 : 0);
+    const float* g0 = gy + row_off(gmap, r, 0);
+    const float* g1 = gy + row_off(gmap, r, a.C == 2 ? 1 : 0);
+    float* o0 = gx + row_off(a.ymap, r, 0);
+    float* o1 = gx + row_off(a.ymap, r, a.C == 2 ? 1 : 0);
     const float* ur = RESCAN ? nullptr : u1 + (int64_t)r * a.L;
     const bool stereo = a.C == 2;
     const int64_t j0 = s + DE * lane;
@@ -586,10 +586,10 @@ __global__ __launch_bounds__(256) void dyn_gain_bwd_kernel(const float* __restri
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
         Knee q;
         knee_setup(q, log_threshold[r], log_ratio[r], log_knee ? log_knee[r] : 0.0f, knee, gate);
-        const float* x0 = x + drow_off(xmap, r, 0);
-        const float* x1 = x + drow_off(xmap, r, C == 2 ? 1 : 0);
-        const float* g0 = gy + drow_off(gmap, r, 0);
-        const float* g1 = gy + drow_off(gmap, r, C == 2 ? 1 : 0);
+        const float* x0 = x + row_off(xmap, r, 0);
+        const float* x1 = x + row_off(xmap, r, C == 2 ? 1 : 0);
+        const float* g0 = gy + row_off(gmap, r, 0);
+        const float* g1 = gy + row_off(gmap, r, C == 2 ? 1 : 0);
         float sT = 0.0f, sR = 0.0f, sK = 0.0f;
         for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < L; n += (int64_t)gridDim.x * blockDim.x) {
             const float e = env[r * L + n];
@@ -657,8 +657,8 @@ __global__ void dyn_dx_kernel(const float* __restrict__ x, gfx_rowmap_t xmap, co
     const float k = 2.0f / (float)C;
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y)
     for (int c = 0; c < C; ++c) {
-        const float* xr = x + drow_off(xmap, r, c);
-        const float* gr = gy + drow_off(gmap, r, c);
+        const float* xr = x + row_off(xmap, r, c);
+        const float* gr = gy + row_off(gmap, r, c);
         float* o = gx + (r * C + c) * L;
         for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < L; n += (int64_t)gridDim.x * blockDim.x)
             o[n] = fmaf(gain[r * L + n], gr[n], k * de[r * L + n] * xr[n]);

@@ -21,7 +21,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "fft_tile.hpp"
 
 namespace gfx {
@@ -71,14 +71,6 @@ struct ConvArgs {
     int Cin, Cf, Cout;
     unsigned hrows;          // filter rows: row r convolves with filter r % hrows (batch-major rows sharing filters)
 };
-
-// rows and row counts fit 32 bits (checked by the launchers): 32-bit division is ~5x cheaper than
-// the 64-bit software divide and stays on the scalar unit.
-__device__ __forceinline__ int64_t row_off(const gfx_rowmap_t& m, unsigned r, int c) {
-    const unsigned inner = (unsigned)m.inner;
-    const unsigned q = r / inner, rem = r - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
 
 // workgroup b runs on XCD b % 8 (observed): give each XCD a contiguous run of logical
 // indices so tiles of one row-channel (which share the filter spectrum) meet in one L2.
@@ -837,14 +829,6 @@ static int auto_schedule() {
 
 static thread_local const char* t_last_kernel = "";   // see gfx_fftconv_last_kernel
 
-template <typename K>
-static int allow_lds(K kernel, int bytes = TILE_LDS_BYTES) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               bytes) == hipSuccess
-               ? 0
-               : GFX_ELAUNCH;
-}
-
 }  // namespace gfx
 
 using namespace gfx;
@@ -881,7 +865,7 @@ int gfx_fir_spectrum_f32(const float* h, const float* gain, int64_t gain_div, vo
     const ConvGeom g = conv_geom(N, 1, part_len);
     if (!g.ok) return GFX_EINVAL;
     if (RCf * g.nparts > 0x7fffffffLL) return GFX_EINVAL;
-    if (allow_lds(hspec_kernel<false>)) return GFX_ELAUNCH;
+    if (allow_lds(hspec_kernel<false>, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     const float2* tw = tile_twiddle_table((hipStream_t)stream);
     if (!tw) return GFX_ELAUNCH;
     const gfx_rowmap_t none = {1, 0, 0, 0};
@@ -896,7 +880,7 @@ int gfx_fir_spectrum_rev_f32(const float* x, gfx_rowmap_t xmap, int64_t R, int64
     const ConvGeom g = conv_geom(L, 1, part_len);
     if (!g.ok) return GFX_EINVAL;
     if (R * C * g.nparts > 0x7fffffffLL) return GFX_EINVAL;
-    if (allow_lds(hspec_kernel<true>)) return GFX_ELAUNCH;
+    if (allow_lds(hspec_kernel<true>, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     const float2* tw = tile_twiddle_table((hipStream_t)stream);
     if (!tw) return GFX_ELAUNCH;
     hipLaunchKernelGGL(hspec_kernel<true>, dim3((unsigned)(R * C * g.nparts)), dim3(TILE_T), TILE_LDS_BYTES,
@@ -930,7 +914,7 @@ int gfx_fir_grad_f32(const float* x, gfx_rowmap_t xmap, const float* g, gfx_rowm
     if (!tw) return GFX_ELAUNCH;
     PipeModule* pm = pipe_module();
     if (pm && corr_pipe_ok(a) && auto_schedule() != GFX_SCHED_TILE) return launch_corr_pipe(pm, x, g, gh, a, tw, st);
-    if (allow_lds(corr1_kernel)) return GFX_ELAUNCH;
+    if (allow_lds(corr1_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     hipLaunchKernelGGL(corr1_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, g, gh, a, tw);
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
@@ -1006,9 +990,9 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
         return rc;
     }
     if (g.nparts == 1) {
-        if (allow_lds(fftconv1_kernel<false>) || allow_lds(fftconv1_kernel<true>)) return GFX_ELAUNCH;
+        if (allow_lds(fftconv1_kernel<false>, TILE_LDS_BYTES) || allow_lds(fftconv1_kernel<true>, TILE_LDS_BYTES)) return GFX_ELAUNCH;
         if (zi) {
-            if (allow_lds(fftconv1_state_kernel<false>)) return GFX_ELAUNCH;
+            if (allow_lds(fftconv1_state_kernel<false>, TILE_LDS_BYTES)) return GFX_ELAUNCH;
             hipLaunchKernelGGL(fftconv1_state_kernel<false>, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x,
                                (const float4*)Hs, y, (float*)nullptr, a, tw, (uint32_t*)nullptr, zi, N);
             if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
@@ -1028,14 +1012,14 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
     }
     if (g.ntiles == 1) {
         if (zi) {
-            if (allow_lds(winmac_state_kernel)) return GFX_ELAUNCH;
+            if (allow_lds(winmac_state_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
             hipLaunchKernelGGL(winmac_state_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x,
                                (const float4*)Hs, y, a, tw, zi, N);
             if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
             t_last_kernel = "winmac_state_kernel";
             return GFX_OK;
         }
-        if (allow_lds(winmac_kernel)) return GFX_ELAUNCH;
+        if (allow_lds(winmac_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
         hipLaunchKernelGGL(winmac_kernel, dim3(pad8(a.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (const float4*)Hs, y,
                            a, tw);
         if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
@@ -1045,12 +1029,12 @@ static int fftconv_sched(const float* x, gfx_rowmap_t xmap, const void* Hs, int6
     const int64_t nwin = g.ntiles + g.nparts - 1;
     const size_t need = (size_t)R * C_in * nwin * H_TILE_F4 * sizeof(float4);
     if (!ws || ws_bytes < need) return GFX_ENOSPC;
-    if (allow_lds(xspec_kernel) || allow_lds(macinv_kernel)) return GFX_ELAUNCH;
+    if (allow_lds(xspec_kernel, TILE_LDS_BYTES) || allow_lds(macinv_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     ConvArgs ax = a;
     ax.nblocks = R * C_in * nwin;
     if (ax.nblocks > 0x7ffffff0LL) return GFX_EINVAL;
     if (zi) {
-        if (allow_lds(xspec_state_kernel)) return GFX_ELAUNCH;
+        if (allow_lds(xspec_state_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
         hipLaunchKernelGGL(xspec_state_kernel, dim3(pad8(ax.nblocks)), dim3(TILE_T), TILE_LDS_BYTES, st, x, (float2*)ws, ax,
                            nwin, tw, zi, N);
         // The product kernels consume spectra and know the signal only through which windows exist.  With a history every

@@ -19,11 +19,7 @@
 //
 // Roofline: MFMA-bound above ~64 taps (N / 64 matrix-core cycles per output sample and CU), HBM-bound below; the FFT
 // tile kernel takes over beyond the crossover measured in profiles/r2/fir_mfma_crossover.txt.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 
 namespace gfx {
 
@@ -40,12 +36,6 @@ struct FirArgs {
     unsigned hrows;
 };
 
-__device__ __forceinline__ int64_t fm_row_off(const gfx_rowmap_t& m, unsigned r, int c) {
-    const unsigned inner = (unsigned)m.inner;
-    const unsigned q = r / inner, rem = r - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
-
 __global__ __launch_bounds__(FM_T) void fir_mfma_kernel(const float* __restrict__ x, const float* __restrict__ h,
                                                         float* __restrict__ y, FirArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -59,8 +49,8 @@ __global__ __launch_bounds__(FM_T) void fir_mfma_kernel(const float* __restrict_
     const int seg = (int)(b - rco * (unsigned)a.nseg);
     const unsigned r = rco / (unsigned)a.Cout;
     const int c = (int)(rco - r * (unsigned)a.Cout);
-    const float* xrow = x + fm_row_off(a.xmap, r, a.Cin == 1 ? 0 : c);
-    float* yrow = y + fm_row_off(a.ymap, r, c);
+    const float* xrow = x + row_off(a.xmap, r, a.Cin == 1 ? 0 : c);
+    float* yrow = y + row_off(a.ymap, r, c);
     const float* hrow = h + ((int64_t)(r % a.hrows) * a.Cf + (a.Cf == 1 ? 0 : c)) * a.N;
     const int64_t seg0 = (int64_t)seg * FM_SEG;
     const int64_t xbase = seg0 + a.off - 16 * (nub - 1);      // signal index of window position 0

@@ -17,7 +17,7 @@
 
 #include <cstdint>
 
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "fft_tile.hpp"
 
 #define NAT(arr, i) arr[(i) >> 4][brev((i) & 15, 4)]
@@ -354,14 +354,6 @@ __global__ void biquad_coeffs_kernel(const float* __restrict__ Bin, const float*
     Bs[3 * i + 2] = Bin[3 * i + 2];
 }
 
-template <typename K>
-static int allow_lds(K kernel) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               TILE_LDS_BYTES) == hipSuccess
-               ? 0
-               : GFX_ELAUNCH;
-}
-
 }  // namespace gfx
 
 using namespace gfx;
@@ -446,7 +438,7 @@ size_t gfx_iir_fsm_plan_bytes(int64_t N) { return (N < 1 || N > FSM_MAX_N) ? 0 :
 
 int gfx_iir_fsm_plan_f32(void* plan, int64_t N, void* stream) {
     if (!plan || N < 1 || N > FSM_MAX_N) return GFX_EINVAL;
-    if (allow_lds(bluestein_plan_kernel)) return GFX_ELAUNCH;
+    if (allow_lds(bluestein_plan_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     const float2* tw = tile_twiddle_table((hipStream_t)stream);
     if (!tw) return GFX_ELAUNCH;
     hipLaunchKernelGGL(bluestein_plan_kernel, dim3(1), dim3(TILE_T), TILE_LDS_BYTES, (hipStream_t)stream,
@@ -458,7 +450,7 @@ static int iir_fsm_fir_launch(const float* Bs, const float* As, const double* Bs
                               float* h, int64_t RC, int64_t K, int64_t N, void* stream) {
     if (!h || RC <= 0 || K <= 0 || N < 1 || RC > 0x7fffffffLL) return GFX_EINVAL;
     if (fsm_pow2(N)) {  // no plan needed
-        if (allow_lds(iir_fsm_pow2_kernel)) return GFX_ELAUNCH;
+        if (allow_lds(iir_fsm_pow2_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
         const float2* tw2 = tile_twiddle_table((hipStream_t)stream);
         if (!tw2) return GFX_ELAUNCH;
         hipLaunchKernelGGL(iir_fsm_pow2_kernel, dim3((unsigned)RC), dim3(TILE_T), TILE_LDS_BYTES, (hipStream_t)stream, Bs,
@@ -466,7 +458,7 @@ static int iir_fsm_fir_launch(const float* Bs, const float* As, const double* Bs
         return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
     }
     if (!plan || N > FSM_MAX_N) return GFX_EINVAL;
-    if (allow_lds(iir_fsm_kernel)) return GFX_ELAUNCH;
+    if (allow_lds(iir_fsm_kernel, TILE_LDS_BYTES)) return GFX_ELAUNCH;
     const float2* tw = tile_twiddle_table((hipStream_t)stream);
     if (!tw) return GFX_ELAUNCH;
     hipLaunchKernelGGL(iir_fsm_kernel, dim3((unsigned)RC), dim3(TILE_T), TILE_LDS_BYTES, (hipStream_t)stream, Bs, As,

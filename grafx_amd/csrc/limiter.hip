@@ -25,7 +25,7 @@
 // and are added in double in a fixed order.  No atomics: equal bits from run to run.  Every s[n] is the same chain of fmaf
 // over the same m whatever the tile, the block or the call it falls in: blocks concatenate to the one-call output bit for
 // bit.  Base offsets are 64-bit, everything inside the tile 32-bit.
-#include "waveshaper.hpp"
+#include "common.hpp"
 
 namespace gfx {
 
@@ -33,7 +33,6 @@ constexpr int LIM_THREADS = 512;
 constexpr int LIM_WAVES = LIM_THREADS / 64;
 constexpr int LIM_MAX_TAPS = 1024;
 constexpr int LIM_MAX_WINDOW = 4096;
-constexpr int64_t LIM_MAX_BLOCKS = 0x7fffffffLL;
 // the backward tile holds 12 (T + 2 M) + 4 (T + M) + 4 N <= 16 T + 32 M bytes: under 160 KiB with room for the static arrays
 constexpr int64_t LIM_LDS_BUDGET = 155000;
 
@@ -145,12 +144,6 @@ __device__ __forceinline__ void lim_fir_runs(const float* w, int N, const float*
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(LIM_THREADS) void lim_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                               const float* __restrict__ log_ceiling,
                                                               const float* __restrict__ w, const float* __restrict__ zi,
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_fwd_kernel(const float* __res
     const int nm = left + N - 1;                         // gains m[q], q from n0 + sigma - (N - 1)
     const int np = nm + M - 1;                           // peaks under them
     const int64_t kbase = n0 + a.sigma - (N - 1) - (M - 1);
-    const float* xrow = x + nrow_off(a.xmap, r, 0);
+    const float* xrow = x + row_off(a.xmap, r, 0);
     const int64_t sch = a.xmap.stride_ch;
     const float* zrow = zi ? zi + r * a.C * (int64_t)a.S : nullptr;
     lim_stage_peaks(pa, xrow, sch, zrow, a.C, a.S, kbase, np, a.L);
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_fwd_kernel(const float* __res
     }
     __syncthreads();
 
-    float* yrow = y + nrow_off(a.ymap, r, 0);
+    float* yrow = y + row_off(a.ymap, r, 0);
     const int64_t ysch = a.ymap.stride_ch;
     const int shift = a.sigma - a.D;
     auto emit = [&](int tt, float s) {
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(256) void lim_state_kernel(const float* __restrict_
                                                         int S) {
     const int64_t rc = blockIdx.x;
     const int64_t r = rc / C;
-    const float* xrow = x + nrow_off(xmap, r, (int)(rc - r * C));
+    const float* xrow = x + row_off(xmap, r, (int)(rc - r * C));
     const float* zrow = zi ? zi + rc * S : nullptr;
     for (int i = threadIdx.x; i < S; i += 256) zf[rc * S + i] = lim_sample(xrow, zrow, L - S + i, L, S);
 }
@@ -242,8 +235,8 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_bwd_kernel(const float* __res
     const int64_t k0 = tile * a.T;
     const int left = (int)(a.L - k0 < a.T ? a.L - k0 : a.T);
     const int nq = left + M - 1, np = nq + M - 1, ng = nq + N - 1;
-    const float* xrow = x + nrow_off(a.xmap, r, 0);
-    const float* grow = gy + nrow_off(a.gmap, r, 0);
+    const float* xrow = x + row_off(a.xmap, r, 0);
+    const float* grow = gy + row_off(a.gmap, r, 0);
     const int64_t sch = a.xmap.stride_ch, gsch = a.gmap.stride_ch;
     lim_stage_peaks(pa, xrow, sch, nullptr, a.C, 0, k0 - (M - 1), np, a.L);
     for (int i = t; i < np; i += LIM_THREADS) ia[i] = (uint16_t)i;
@@ -301,7 +294,7 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_bwd_kernel(const float* __res
         if (lane == 0) bs[b] = s;
     }
     if (part) {
-        acc = wave_sum_f64(acc);
+        acc = wave_sum(acc);
         if (lane == 0) red[wave] = acc;
     }
     __syncthreads();
@@ -312,7 +305,7 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_bwd_kernel(const float* __res
     }
     if (!gx) return;
 
-    float* orow = gx + nrow_off(a.ymap, r, 0);
+    float* orow = gx + row_off(a.ymap, r, 0);
     const int64_t osch = a.ymap.stride_ch;
     auto emit = [&](int tt, float s) {
         const int64_t k = k0 + tt, n = k + D - a.sigma;
@@ -376,8 +369,6 @@ __global__ __launch_bounds__(256) void lim_bwd_finish_kernel(const double* __res
     }
 }
 
-static inline bool lim_neg(const gfx_rowmap_t& m) { return m.stride_outer < 0 || m.stride_inner < 0 || m.stride_ch < 0; }
-
 // the checks both entries share, then the tile geometry
 static int lim_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, const float* log_ceiling,
                        const float* w, int64_t N, int64_t D, int64_t H, int64_t sigma, LimArgs& a) {
@@ -390,7 +381,7 @@ static int lim_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, 
     const int64_t M = D + 1 + H;
     const int T = lim_tile(M);
     const int64_t ntiles = (L + T - 1) / T;
-    if (ntiles > LIM_MAX_BLOCKS / R) return GFX_EINVAL;                    // grid.x of the tile kernels
+    if (ntiles > MAX_GRID_X / R) return GFX_EINVAL;                    // grid.x of the tile kernels
     a.xmap = a.ymap = a.gmap = xmap;
     a.L = L; a.ntiles = ntiles;
     a.C = (int)C; a.D = (int)D; a.M = (int)M; a.N = (int)N; a.S = (int)(M + N - 2); a.sigma = (int)sigma; a.T = T;
@@ -399,17 +390,6 @@ static int lim_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, 
     a.pwords = a.qwords = 0;
     return GFX_OK;
 }
-
-template <typename Kernel>
-static int lim_lds_attribute(Kernel kernel, size_t lds) {
-    if (lds <= 65536) return GFX_OK;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
-                   hipSuccess
-               ? GFX_OK
-               : GFX_ELAUNCH;
-}
-
-static inline bool lim_ranges_meet(const float* a, int64_t na, const float* b, int64_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace gfx
 
@@ -426,13 +406,13 @@ int gfx_limiter_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     if (rc != GFX_OK) return rc;
     if ((zi || zf) && sigma > 0) return GFX_EINVAL;    // the compensated output needs samples the next block brings
     // tiles read each other's halos of x: never in place
-    if (lim_neg(xmap) || lim_neg(ymap) || ws_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
+    if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
     const int64_t nstate = R * C * a.S;
-    if (zi && zf && nstate > 0 && lim_ranges_meet(zi, nstate, zf, nstate)) return GFX_EINVAL;
+    if (zi && zf && nstate > 0 && ranges_meet(zi, nstate, zf, nstate)) return GFX_EINVAL;
     a.ymap = ymap;
     a.pwords = a.T + a.N - 1 + a.M - 1;
     const size_t lds = sizeof(float) * ((size_t)a.N + 2 * (size_t)a.pwords);
-    if (lim_lds_attribute(lim_fwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
+    if (allow_lds(lim_fwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lim_fwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, y, log_ceiling, w, zi, gain,
                        a);
@@ -458,10 +438,10 @@ int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     const int rc = lim_prepare(x, xmap, R, C, L, log_ceiling, w, N, D, H, sigma, a);
     if (rc != GFX_OK) return rc;
     if (!gx && !g_log_ceiling) return GFX_EINVAL;
-    if (lim_neg(xmap) || lim_neg(gmap)) return GFX_EINVAL;
+    if (map_negative(xmap) || map_negative(gmap)) return GFX_EINVAL;
     if (gx) {
-        if (omap.inner <= 0 || lim_neg(omap)) return GFX_EINVAL;
-        if (ws_overlap(gx, omap, x, xmap, R, C, L) || ws_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
+        if (omap.inner <= 0 || map_negative(omap)) return GFX_EINVAL;
+        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
     }
     double* part = nullptr;
     if (g_log_ceiling) {
@@ -475,7 +455,7 @@ int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     a.pwords += a.pwords & 1;                            // (the 16-bit indices behind the floats stay 4-byte aligned)
     a.qwords = a.T + a.M - 1;
     const size_t lds = sizeof(float) * ((size_t)a.N + 2 * (size_t)a.pwords + (size_t)a.qwords) + 2 * sizeof(uint16_t) * (size_t)a.pwords;
-    if (lim_lds_attribute(lim_bwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
+    if (allow_lds(lim_bwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lim_bwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, gy, gx, log_ceiling, w, part,
                        a);

@@ -32,7 +32,7 @@
 // the workspace is 64 bytes per tile: the forward state (32 B) and the adjoint state or the two energy parts.
 // No atomics, every sum in a fixed order: two calls give the same bits, and a tile's arithmetic depends on its own
 // row-channel alone.
-#include "biquad_common.hpp"
+#include "common.hpp"
 
 namespace gfx {
 
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kw_tile_state_kernel(const floa
     if (!w.live) return;   // (a whole wave; the kernel has no barrier)
     const int lane = threadIdx.x & 63;
     float e[KW_E];
-    kw_load(x + brow_off(a.xmap, w.r, w.c), w.n, a.L, a.xvec, e);
+    kw_load(x + row_off(a.xmap, w.r, w.c), w.n, a.L, a.xvec, e);
     S4 z = {0.0, 0.0, 0.0, 0.0}, total;
 #pragma unroll
     for (int i = 0; i < KW_E; ++i) kw_step(k, z, (double)e[i]);
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kw_main_kernel(const float* __r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double* wst = ws + (w.rc * a.ntiles + w.t) * KW_WS;
     float e[KW_E];
-    kw_load(x + brow_off(a.xmap, w.r, w.c), w.n, a.L, a.xvec, e);
+    kw_load(x + row_off(a.xmap, w.r, w.c), w.n, a.L, a.xvec, e);
     S4 z = {0.0, 0.0, 0.0, 0.0}, total;
 #pragma unroll
     for (int i = 0; i < KW_E; ++i) kw_step(k, z, (double)e[i]);
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kw_main_kernel(const float* __r
     float o[KW_E];
 #pragma unroll
     for (int i = KW_E - 1; i >= 0; --i) o[i] = (float)kw_step(k, z, y[i]);
-    float* dst = gx + brow_off(a.gmap, w.r, w.c);
+    float* dst = gx + row_off(a.gmap, w.r, w.c);
     if (a.gvec && w.n + KW_E <= a.L) {
 #pragma unroll
         for (int j = 0; j < KW_E / 4; ++j) {
@@ -359,9 +359,8 @@ static bool kw_constants(const double* coef, KwConst& k) {
 static inline int64_t kw_tiles(int64_t L) { return (L + KW_TILE - 1) / KW_TILE; }
 static inline bool kw_aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
 static inline bool kw_map_vec(const void* p, const gfx_rowmap_t& m) {
-    return kw_aligned(p, 16) && m.stride_outer % 4 == 0 && m.stride_inner % 4 == 0 && m.stride_ch % 4 == 0;
+    return aligned16(p) && map_vec(m);
 }
-constexpr int64_t KW_MAX_BLOCKS = 0x7fffffffLL;
 
 // the checks both entries share, then the constants and the geometry; what the signal's rows need is left to the caller
 static int kw_prepare(const float* x, gfx_rowmap_t xmap, const double* coef, int64_t R, int64_t C, int64_t L, int64_t hop,
@@ -369,7 +368,7 @@ static int kw_prepare(const float* x, gfx_rowmap_t xmap, const double* coef, int
     if (!x || !coef || !ws || R <= 0 || C <= 0 || L <= 0 || hop < 1 || hop > L || xmap.inner <= 0) return GFX_EINVAL;
     if (R > 0x7fffffffLL || C > 0x7fffffffLL || !kw_aligned(ws, 16)) return GFX_EINVAL;
     const int64_t ntiles = kw_tiles(L);
-    if (R * C > KW_MAX_BLOCKS || ntiles > KW_MAX_BLOCKS * KW_WAVES / (R * C)) return GFX_EINVAL;   // grid.x of every launch
+    if (R * C > MAX_GRID_X || ntiles > MAX_GRID_X * KW_WAVES / (R * C)) return GFX_EINVAL;   // grid.x of every launch
     if (!kw_constants(coef, k)) return GFX_EINVAL;
     if (ws_bytes < gfx_kweight_energy_ws_bytes(R, C, L)) return GFX_ENOSPC;
     a.xmap = xmap;

@@ -32,8 +32,8 @@ __global__ __launch_bounds__(256) void waveshaper_kernel(const float* __restrict
         ws_row_setup<MODE>(q, sw, r, a.K, a.inverse_post, log_pre, log_post, p0, p1);
         for (int c = 0; c < a.C; ++c) {
             q.dc = dc ? dc[r * a.C + c] : 0.0f;
-            const float* xr = x + nrow_off(a.xmap, r, c);
-            float* yr = y + nrow_off(a.ymap, r, c);
+            const float* xr = x + row_off(a.xmap, r, c);
+            float* yr = y + row_off(a.ymap, r, c);
             const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
             if (vec) {
                 using f4 = float __attribute__((ext_vector_type(4)));
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void row_mean_kernel(const float* __restrict__
     __shared__ float part[4];
     for (int64_t rc = blockIdx.x; rc < R * C; rc += gridDim.x) {
         const int64_t r = rc / C;
-        const float* xr = x + nrow_off(xmap, r, (int)(rc - r * C));
+        const float* xr = x + row_off(xmap, r, (int)(rc - r * C));
         float s = 0.0f;
         for (int64_t n = threadIdx.x; n < L; n += 256) s += xr[n];
         for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
@@ -69,11 +69,6 @@ __global__ __launch_bounds__(256) void row_mean_kernel(const float* __restrict__
         if (threadIdx.x == 0) mean[rc] = (part[0] + part[1] + part[2] + part[3]) / (float)L;
         __syncthreads();
     }
-}
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool map_vec(const gfx_rowmap_t& m) {
-    return m.stride_outer % 4 == 0 && m.stride_inner % 4 == 0 && m.stride_ch % 4 == 0;
 }
 
 }  // namespace gfx
@@ -95,10 +90,7 @@ int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t
                        const float* log_post_gain, const float* p0, const float* p1, int64_t K, const float* dc,
                        void* stream) {
     if (!x || !y || R <= 0 || C <= 0 || L <= 0 || R > 0x7fffffffLL || xmap.inner <= 0 || ymap.inner <= 0) return GFX_EINVAL;
-    if (mode < GFX_WS_TANH || mode > GFX_WS_CHEBYSHEV) return GFX_EINVAL;
-    if (inverse_post_gain && !log_pre_gain) return GFX_EINVAL;
-    if (mode == GFX_WS_PIECEWISE && (!p0 || !p1)) return GFX_EINVAL;
-    if ((mode == GFX_WS_POWER || mode == GFX_WS_CHEBYSHEV) && (!p0 || K < 1 || K > WS_MAX_K)) return GFX_EINVAL;
+    if (ws_check_shaper(mode, inverse_post_gain, log_pre_gain, p0, p1, K) != GFX_OK) return GFX_EINVAL;
     WsArgs a;
     a.xmap = xmap; a.ymap = ymap; a.R = R; a.L = L; a.C = (int)C; a.mode = mode; a.K = (int)K;
     a.use_tanh = use_tanh; a.inverse_post = inverse_post_gain;
@@ -176,9 +168,9 @@ __global__ __launch_bounds__(256) void waveshaper_bwd_kernel(const float* __rest
         for (int j = 0; j < NA; ++j) acc[j] = 0.0f;
         for (int c = 0; c < a.C; ++c) {
             q.dc = dc ? dc[r * a.C + c] : 0.0f;
-            const float* xr = x + nrow_off(a.xmap, r, c);
-            const float* gr = gy + nrow_off(a.gmap, r, c);
-            float* outr = gx ? gx + nrow_off(a.omap, r, c) : nullptr;
+            const float* xr = x + row_off(a.xmap, r, c);
+            const float* gr = gy + row_off(a.gmap, r, c);
+            float* outr = gx ? gx + row_off(a.omap, r, c) : nullptr;
             const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
             float dsum = 0.0f;
             int64_t n0 = tid;                        // first sample of the scalar loop: the whole row, or the tail
@@ -218,6 +210,7 @@ __global__ __launch_bounds__(256) void waveshaper_bwd_kernel(const float* __rest
         }
         if (par) {
             __syncthreads();                         // red / tot free again
+            // (os_bwd_kernel of oversampled.hip ends alike: one shared function changed the code of both kernels)
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
                 if (j < nsum) {
@@ -260,12 +253,14 @@ __global__ __launch_bounds__(256) void waveshaper_bwd_kernel(const float* __rest
     }
 }
 
-// a row's partial sums -> the parameter gradients (double, fixed order); the row-channels' mean input gradient
+// a row's npart partials of every sum -> the parameter gradients, a row-channel's ndc partials -> its mean input gradient:
+// in double, in a fixed order.  For the streaming backward above (both counts its grid.x) and for the oversampled tile
+// backward (C ntiles and ntiles).
 __global__ __launch_bounds__(256) void ws_bwd_finish_kernel(const float* __restrict__ part, const float* __restrict__ dcpart,
                                                             float* __restrict__ gmean, float* __restrict__ g_pre,
                                                             float* __restrict__ g_post, float* __restrict__ g_p0,
                                                             float* __restrict__ g_p1, int64_t R, int C, int64_t L, int NS,
-                                                            int bx, int mode, int K) {
+                                                            int64_t npart, int64_t ndc, int mode, int K) {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     if (part) {
         for (int64_t i = tid; i < R * NS; i += nthr) {
@@ -279,17 +274,28 @@ __global__ __launch_bounds__(256) void ws_bwd_finish_kernel(const float* __restr
             else dst = g_p0 ? g_p0 + r * K + (j - 2) : nullptr;
             if (!dst) continue;
             double s = 0.0;
-            for (int b = 0; b < bx; ++b) s += (double)part[i * bx + b];
+            for (int64_t b = 0; b < npart; ++b) s += (double)part[i * npart + b];
             *dst = (float)s;
         }
     }
     if (dcpart) {
         for (int64_t i = tid; i < R * C; i += nthr) {
             double s = 0.0;
-            for (int b = 0; b < bx; ++b) s += (double)dcpart[i * bx + b];
+            for (int64_t b = 0; b < ndc; ++b) s += (double)dcpart[i * ndc + b];
             gmean[i] = (float)(s / (double)L);
         }
     }
+}
+
+int ws_bwd_finish(const WsBwdSpace& s, const WsGrads& g, int64_t R, int64_t C, int64_t L, int64_t K, int64_t npart, int64_t ndc,
+                  int mode, hipStream_t stream) {
+    if (!s.part && !s.dcpart) return GFX_OK;
+    const int NS = ws_nsums(K);
+    const int64_t items = R * (NS > (int)C ? NS : (int)C);
+    const int64_t nb = (items + 255) / 256;
+    hipLaunchKernelGGL(ws_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, stream, s.part,
+                       s.dcpart, s.gmean, g.pre, g.post, g.p0, g.p1, R, (int)C, L, NS, npart, ndc, mode, (int)K);
+    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
 // the adjoint of the centring x - mean(x): gx -= mean(gx) per row-channel
@@ -299,7 +305,7 @@ __global__ __launch_bounds__(256) void ws_sub_mean_kernel(float* __restrict__ gx
     for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
         for (int c = 0; c < C; ++c) {
             const float m = gmean[r * C + c];
-            float* outr = gx + nrow_off(omap, r, c);
+            float* outr = gx + row_off(omap, r, c);
             const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
             int64_t n0 = tid;
             if (vec) {
@@ -319,7 +325,7 @@ extern "C" {
 size_t gfx_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K) {
     if (R <= 0 || C <= 0 || L <= 0 || K < 0 || K > WS_MAX_K) return 0;
     const size_t bx = (size_t)ws_blocks(L);
-    return sizeof(float) * ((size_t)R * (size_t)ws_nsums(K) * bx + (size_t)R * (size_t)C * bx + (size_t)R * (size_t)C);
+    return sizeof(float) * ws_bwd_floats(R, C, K, bx, bx);
 }
 
 int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R, int64_t C,
@@ -328,69 +334,43 @@ int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, g
                            float* gx, gfx_rowmap_t omap, float* g_log_pre_gain, float* g_log_post_gain, float* g_p0,
                            float* g_p1, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !gy || R <= 0 || C <= 0 || L <= 0 || R > 0x7fffffffLL || xmap.inner <= 0 || gmap.inner <= 0) return GFX_EINVAL;
-    if (mode < GFX_WS_TANH || mode > GFX_WS_CHEBYSHEV) return GFX_EINVAL;
-    if (inverse_post_gain && !log_pre_gain) return GFX_EINVAL;
-    if (mode == GFX_WS_PIECEWISE && (!p0 || !p1)) return GFX_EINVAL;
-    const bool poly = mode == GFX_WS_POWER || mode == GFX_WS_CHEBYSHEV;
-    if (poly && (!p0 || K < 1 || K > WS_MAX_K)) return GFX_EINVAL;
-    if (!poly) K = 0;
-    const bool want_par = g_log_pre_gain || g_log_post_gain || g_p0 || g_p1;
-    if (!gx && !want_par) return GFX_EINVAL;
-    // a gradient of something that is not there (or, for the post gain under inverse_post_gain, not used)
-    if ((g_log_pre_gain && !log_pre_gain) || (g_log_post_gain && (!log_post_gain || inverse_post_gain)) || (g_p0 && !p0) ||
-        (g_p1 && mode != GFX_WS_PIECEWISE))
-        return GFX_EINVAL;
+    if (ws_check_shaper(mode, inverse_post_gain, log_pre_gain, p0, p1, K) != GFX_OK) return GFX_EINVAL;
+    const WsGrads grads{g_log_pre_gain, g_log_post_gain, g_p0, g_p1};
+    if (ws_check_grads(grads, gx, mode, inverse_post_gain, log_pre_gain, log_post_gain, p0) != GFX_OK) return GFX_EINVAL;
+    const bool want_par = grads.any();
     if (gx) {
-        if (omap.inner <= 0) return GFX_EINVAL;
-        if (xmap.stride_outer < 0 || xmap.stride_inner < 0 || xmap.stride_ch < 0 || gmap.stride_outer < 0 ||
-            gmap.stride_inner < 0 || gmap.stride_ch < 0 || omap.stride_outer < 0 || omap.stride_inner < 0 || omap.stride_ch < 0)
-            return GFX_EINVAL;
-        if (ws_overlap(gx, omap, x, xmap, R, C, L) || ws_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
+        if (omap.inner <= 0 || map_negative(xmap) || map_negative(gmap) || map_negative(omap)) return GFX_EINVAL;
+        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
     }
     const bool center = dc && gx;
     const int64_t bx = ws_blocks(L);
-    const int NS = ws_nsums(K);
-    float *part = nullptr, *dcpart = nullptr, *gmean = nullptr;
-    if (want_par || center) {
-        if (!ws) return GFX_EINVAL;
-        if (ws_bytes < gfx_waveshaper_bwd_ws_bytes(R, C, L, K)) return GFX_ENOSPC;
-        float* w = static_cast<float*>(ws);
-        if (want_par) part = w;
-        if (center) {
-            dcpart = w + (size_t)R * NS * bx;
-            gmean = dcpart + (size_t)R * C * bx;
-        }
-    }
+    WsBwdSpace sp;
+    const int rc = ws_bwd_carve(ws, ws_bytes, R, C, K, (size_t)bx, (size_t)bx, want_par, center, sp);
+    if (rc != GFX_OK) return rc;
     WsBwdArgs a;
-    a.xmap = xmap; a.gmap = gmap; a.omap = gx ? omap : xmap; a.R = R; a.L = L; a.C = (int)C; a.K = (int)K; a.NS = NS;
+    a.xmap = xmap; a.gmap = gmap; a.omap = gx ? omap : xmap; a.R = R; a.L = L; a.C = (int)C; a.K = (int)K; a.NS = ws_nsums(K);
     a.use_tanh = use_tanh; a.inverse_post = inverse_post_gain; a.want_par = want_par;
     const int vec = aligned16(x) && aligned16(gy) && map_vec(xmap) && map_vec(gmap) && (!gx || (aligned16(gx) && map_vec(omap)));
     const dim3 grid((unsigned)bx, (unsigned)(R > 65535 ? 65535 : R));
     hipStream_t st = (hipStream_t)stream;
     switch (mode) {
         case GFX_WS_TANH:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_TANH>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_TANH>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
             break;
         case GFX_WS_PIECEWISE:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_PIECEWISE>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_PIECEWISE>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
             break;
         case GFX_WS_POWER:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_POWER>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_POWER>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
             break;
         default:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_CHEBYSHEV>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, part, dcpart, a, vec);
+            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_CHEBYSHEV>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
             break;
     }
     if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    if (part || dcpart) {
-        const int64_t items = R * (NS > (int)C ? NS : (int)C);
-        const int64_t nb = (items + 255) / 256;
-        hipLaunchKernelGGL(ws_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, st, part, dcpart,
-                           gmean, g_log_pre_gain, g_log_post_gain, g_p0, g_p1, R, (int)C, L, NS, (int)bx, mode, (int)K);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (ws_bwd_finish(sp, grads, R, C, L, K, bx, bx, mode, st) != GFX_OK) return GFX_ELAUNCH;
     if (center) {
-        hipLaunchKernelGGL(ws_sub_mean_kernel, grid, dim3(256), 0, st, gx, omap, gmean, R, (int)C, L,
+        hipLaunchKernelGGL(ws_sub_mean_kernel, grid, dim3(256), 0, st, gx, omap, sp.gmean, R, (int)C, L,
                            (int)(aligned16(gx) && map_vec(omap)));
         if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
     }
@@ -491,10 +471,7 @@ __global__ __launch_bounds__(256) void rdft_kernel(const float* __restrict__ x, 
 extern "C" int gfx_rdft_f32(const float* x, float* X, int64_t rows, int64_t K, int64_t n, void* stream) {
     if (!x || !X || rows <= 0 || rows > 65535 || n < 1 || n > 8192 || K != n / 2 + 1) return GFX_EINVAL;
     const size_t lds = (size_t)n * (sizeof(float2) + sizeof(float));
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gfx::rdft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return GFX_ELAUNCH;
+    if (gfx::allow_lds(gfx::rdft_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipLaunchKernelGGL(gfx::rdft_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)rows), dim3(256), lds, (hipStream_t)stream, x, X,
                        (int)K, (int)n);
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
@@ -505,10 +482,7 @@ extern "C" int gfx_irdft_f32(const float* X, int is_real, float* y, int64_t rows
     if (!X || !y || rows <= 0 || rows > 0x7fffffffLL || n < 1 || n > 8192 || K != n / 2 + 1 || roll < 0 || roll >= n)
         return GFX_EINVAL;
     const size_t lds = (size_t)(n + K) * sizeof(float2);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gfx::irdft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return GFX_ELAUNCH;
+    if (gfx::allow_lds(gfx::irdft_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipLaunchKernelGGL(gfx::irdft_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, X, is_real, y, (int)K,
                        (int)n, (int)roll, window);
     return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;

@@ -35,7 +35,6 @@ constexpr int OS_THREADS = 256;
 constexpr int OS_MAX_FACTOR = 16;
 constexpr int OS_MAX_TAPS = 1024;
 constexpr int OS_SPAN = 4096;                    // high-rate samples of a tile, before the halo
-constexpr int64_t OS_MAX_BLOCKS = 0x7fffffffLL;
 
 static inline int os_tile(int64_t F) { return (int)(OS_SPAN / F / 64 * 64); }
 
@@ -77,16 +76,10 @@ __device__ __forceinline__ void os_stage_phases(float* hp, const float* __restri
     }
 }
 
-__device__ __forceinline__ int64_t os_floor_div(int64_t e, int F) {
-    int64_t q = e / F;
-    if (q * F > e) --q;
-    return q;
-}
-
 // the span of a base-rate row under the high-rate samples p_lo .. p_lo + nv - 1 of an interpolator: its first sample (what
 // slot 0 of the first of them reads) and its length in words
 __device__ __forceinline__ int64_t os_span_base(const OsFir& f, int F, int64_t p_lo) {
-    return os_floor_div(p_lo + f.offset, F) - (f.J - 1);
+    return floor_div(p_lo + f.offset, F) - (f.J - 1);
 }
 static __host__ __device__ __forceinline__ int os_span_words(int J, int F, int nv) { return (nv - 1) / F + J + 1; }
 
@@ -105,7 +98,7 @@ struct OsPhase {             // the high-rate samples p_lo + a + b F, b = 0, 1, 
 };
 
 __device__ __forceinline__ OsPhase os_phase(const float* hp, const OsFir& f, int F, int64_t p, int64_t kbase) {
-    const int64_t e = p + f.offset, q = os_floor_div(e, F);
+    const int64_t e = p + f.offset, q = floor_div(e, F);
     const int ph = (int)(e - q * F);
     return OsPhase{hp + ph * f.Jp, (int)(q - kbase) - (f.J - 1), ph < f.phs};
 }
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_fwd_kernel(const float* __restr
     const int nv = left * F + a.ND - 1;
     const int64_t p_lo = m0 * F - a.o_lo;
     const int64_t kbase = os_span_base(a.up, F, p_lo);
-    os_stage_span(xs, x + nrow_off(a.xmap, r, c), kbase, os_span_words(a.up.J, F, nv), a.L, dc ? dc[rc] : 0.0f);
+    os_stage_span(xs, x + row_off(a.xmap, r, c), kbase, os_span_words(a.up.J, F, nv), a.L, dc ? dc[rc] : 0.0f);
     __syncthreads();
 
     const int i_lo = p_lo < 0 ? (int)(-p_lo < nv ? -p_lo : nv) : 0;          // local samples inside [0, F L)
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_fwd_kernel(const float* __restr
     }
     __syncthreads();
 
-    float* yrow = y + nrow_off(a.ymap, r, c) + m0;
+    float* yrow = y + row_off(a.ymap, r, c) + m0;
     int tt = t;
     for (; tt + 3 * OS_THREADS < left; tt += 4 * OS_THREADS) {
         float acc[4];
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_fwd_kernel(const float* __restr
 // The backward tile: gx for T base samples.  Stage 2 forms gu over the F T + N_up - 1 high-rate samples its gx reaches
 // (u and gv by two interpolations, then bwd_samples); a sample adds to the parameter sums in exactly one tile, the one
 // whose [F m0, F (m0 + T)) holds it -- the halo serves gx only.  Partial sums: registers -> wave shuffles -> LDS -> one
-// store per sum and workgroup; os_bwd_finish_kernel adds them in double in a fixed order.
+// store per sum and workgroup; ws_bwd_finish_kernel (nonlinear.hip) adds them in double in a fixed order.
 template <int MODE>
 __global__ __launch_bounds__(OS_THREADS) void os_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                             float* __restrict__ gx, const float* __restrict__ h_up,
@@ -256,8 +249,8 @@ __global__ __launch_bounds__(OS_THREADS) void os_bwd_kernel(const float* __restr
     const int nv = left * F + a.ND - 1;
     const int64_t p_lo = m0 * F - a.o_lo;
     const int64_t kbx = os_span_base(a.up, F, p_lo), kbg = os_span_base(a.dn, F, p_lo);
-    os_stage_span(xs, x + nrow_off(a.xmap, r, c), kbx, os_span_words(a.up.J, F, nv), a.L, dc ? dc[rc] : 0.0f);
-    os_stage_span(gs, gy + nrow_off(a.gmap, r, c), kbg, os_span_words(a.dn.J, F, nv), a.L, 0.0f);
+    os_stage_span(xs, x + row_off(a.xmap, r, c), kbx, os_span_words(a.up.J, F, nv), a.L, dc ? dc[rc] : 0.0f);
+    os_stage_span(gs, gy + row_off(a.gmap, r, c), kbg, os_span_words(a.dn.J, F, nv), a.L, 0.0f);
     __syncthreads();
 
     const int i_lo = p_lo < 0 ? (int)(-p_lo < nv ? -p_lo : nv) : 0;
@@ -311,7 +304,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_bwd_kernel(const float* __restr
     __syncthreads();
 
     if (gx) {
-        float* orow = gx + nrow_off(a.ymap, r, c) + m0;
+        float* orow = gx + row_off(a.ymap, r, c) + m0;
         float dsum = 0.0f;
         int tt = t;
         for (; tt + 3 * OS_THREADS < left; tt += 4 * OS_THREADS) {
@@ -336,6 +329,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_bwd_kernel(const float* __restr
         }
     }
     if (want_par) {
+        // (waveshaper_bwd_kernel of nonlinear.hip ends alike: one shared function changed the code of both kernels)
         const int nsum = POLY ? 2 + a.K : NA;        // sums of this mode that are in use
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -376,40 +370,6 @@ __global__ __launch_bounds__(OS_THREADS) void os_bwd_kernel(const float* __restr
     }
 }
 
-// a row's partial sums (C ntiles of each) -> the parameter gradients, a row-channel's (ntiles) -> its mean input gradient:
-// in double, in a fixed order
-__global__ __launch_bounds__(256) void os_bwd_finish_kernel(const float* __restrict__ part, const float* __restrict__ dcpart,
-                                                            float* __restrict__ gmean, float* __restrict__ g_pre,
-                                                            float* __restrict__ g_post, float* __restrict__ g_p0,
-                                                            float* __restrict__ g_p1, int64_t R, int C, int64_t L, int NS,
-                                                            int64_t ntiles, int mode, int K) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    if (part) {
-        const int64_t nb = C * ntiles;
-        for (int64_t i = tid; i < R * NS; i += nthr) {
-            const int64_t r = i / NS;
-            const int j = (int)(i - r * NS);
-            float* dst = nullptr;
-            if (j == 0) dst = g_pre ? g_pre + r : nullptr;
-            else if (j == 1) dst = g_post ? g_post + r : nullptr;
-            else if (mode == GFX_WS_TANH) dst = (g_p0 && j == 2) ? g_p0 + r : nullptr;
-            else if (mode == GFX_WS_PIECEWISE) dst = j < 4 ? (g_p0 ? g_p0 + 2 * r + (j - 2) : nullptr) : (g_p1 ? g_p1 + 2 * r + (j - 4) : nullptr);
-            else dst = g_p0 ? g_p0 + r * K + (j - 2) : nullptr;
-            if (!dst) continue;
-            double s = 0.0;
-            for (int64_t b = 0; b < nb; ++b) s += (double)part[i * nb + b];
-            *dst = (float)s;
-        }
-    }
-    if (dcpart) {
-        for (int64_t i = tid; i < R * C; i += nthr) {
-            double s = 0.0;
-            for (int64_t b = 0; b < ntiles; ++b) s += (double)dcpart[i * ntiles + b];
-            gmean[i] = (float)(s / (double)L);
-        }
-    }
-}
-
 // the adjoint of the centring x - mean(x): gx -= mean(gx) per row-channel, tile by tile
 __global__ __launch_bounds__(OS_THREADS) void os_sub_mean_kernel(float* __restrict__ gx, gfx_rowmap_t omap,
                                                                  const float* __restrict__ gmean, int C, int64_t L, int T,
@@ -419,12 +379,10 @@ __global__ __launch_bounds__(OS_THREADS) void os_sub_mean_kernel(float* __restri
     const int64_t r = rc / C;
     const int64_t m0 = tile * T;
     const int left = (int)(L - m0 < T ? L - m0 : T);
-    float* orow = gx + nrow_off(omap, r, (int)(rc - r * C)) + m0;
+    float* orow = gx + row_off(omap, r, (int)(rc - r * C)) + m0;
     const float m = gmean[rc];
     for (int tt = threadIdx.x; tt < left; tt += OS_THREADS) orow[tt] -= m;
 }
-
-static inline bool os_neg(const gfx_rowmap_t& m) { return m.stride_outer < 0 || m.stride_inner < 0 || m.stride_ch < 0; }
 
 // the checks both entries share, then the tile geometry (the LDS words of the spans are the caller's: they differ)
 static int os_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, int64_t F, const float* h_up,
@@ -434,16 +392,11 @@ static int os_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, i
     if (F < 1 || F > OS_MAX_FACTOR || N_up < 1 || N_up > OS_MAX_TAPS || N_dn < 1 || N_dn > OS_MAX_TAPS || o_up < 0 ||
         o_up >= N_up || o_dn < 0 || o_dn >= N_dn)
         return GFX_EINVAL;
-    if (mode < GFX_WS_TANH || mode > GFX_WS_CHEBYSHEV) return GFX_EINVAL;
-    if (inverse_post_gain && !log_pre_gain) return GFX_EINVAL;
-    if (mode == GFX_WS_PIECEWISE && (!p0 || !p1)) return GFX_EINVAL;
-    const bool poly = mode == GFX_WS_POWER || mode == GFX_WS_CHEBYSHEV;
-    if (poly && (!p0 || K < 1 || K > WS_MAX_K)) return GFX_EINVAL;
-    if (!poly) K = 0;
+    if (ws_check_shaper(mode, inverse_post_gain, log_pre_gain, p0, p1, K) != GFX_OK) return GFX_EINVAL;
     if (C > 0x7fffffffLL || R * C > 0x7fffffffLL || L > INT64_MAX / (2 * OS_MAX_FACTOR)) return GFX_EINVAL;
     const int T = os_tile(F);
     const int64_t ntiles = (L + T - 1) / T;
-    if (ntiles > OS_MAX_BLOCKS / (R * C)) return GFX_EINVAL;               // grid.x of the tile kernels
+    if (ntiles > MAX_GRID_X / (R * C)) return GFX_EINVAL;               // grid.x of the tile kernels
     a.xmap = a.ymap = a.gmap = xmap;
     a.L = L; a.FL = F * L; a.ntiles = ntiles;
     a.C = (int)C; a.F = (int)F; a.T = T; a.K = (int)K; a.NS = ws_nsums(K);
@@ -465,15 +418,6 @@ static size_t os_layout(OsArgs& a, int ND, int o_lo, bool backward) {
     return sizeof(float) * ((size_t)a.up.words + (backward ? a.dn.words : 0) + ND + a.xwords + a.gwords + (size_t)a.F * a.vpitch);
 }
 
-template <typename Kernel>
-static int os_lds_attribute(Kernel kernel, size_t lds) {
-    if (lds <= 65536) return GFX_OK;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
-                   hipSuccess
-               ? GFX_OK
-               : GFX_ELAUNCH;
-}
-
 }  // namespace gfx
 
 using namespace gfx;
@@ -491,13 +435,13 @@ int gfx_oversampled_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, 
                               inverse_post_gain, log_pre_gain, p0, p1, K, a);
     if (rc != GFX_OK) return rc;
     // tiles read each other's halos of x: never in place
-    if (os_neg(xmap) || os_neg(ymap) || ws_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
+    if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
     a.ymap = ymap;
     const size_t lds = os_layout(a, (int)N_dn, (int)(N_dn - 1 - offset_dn), false);
     const dim3 grid((unsigned)(R * C * a.ntiles));
     hipStream_t st = (hipStream_t)stream;
 #define GFX_OS_FWD(M)                                                                                                          \
-    if (os_lds_attribute(os_fwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                 \
+    if (allow_lds(os_fwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                        \
     hipLaunchKernelGGL(os_fwd_kernel<M>, grid, dim3(OS_THREADS), lds, st, x, y, h_up, h_dn, log_pre_gain, log_post_gain, p0, p1, \
                        dc, a)
     switch (mode) {
@@ -513,8 +457,8 @@ int gfx_oversampled_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, 
 size_t gfx_oversampled_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K, int64_t factor) {
     if (R <= 0 || C <= 0 || L <= 0 || K < 0 || K > WS_MAX_K || factor < 1 || factor > OS_MAX_FACTOR) return 0;
     const int T = os_tile(factor);
-    const size_t nt = (size_t)((L + T - 1) / T), rcs = (size_t)R * (size_t)C;
-    return sizeof(float) * ((size_t)R * (size_t)ws_nsums(K) * (size_t)C * nt + rcs * nt + rcs);
+    const size_t nt = (size_t)((L + T - 1) / T);
+    return sizeof(float) * ws_bwd_floats(R, C, K, (size_t)C * nt, nt);
 }
 
 int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R,
@@ -529,28 +473,18 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
     const int rc = os_prepare(x, xmap, R, C, L, factor, h_up, N_up, offset_up, h_dn, N_dn, offset_dn, mode, use_tanh,
                               inverse_post_gain, log_pre_gain, p0, p1, K, a);
     if (rc != GFX_OK) return rc;
-    const bool want_par = g_log_pre_gain || g_log_post_gain || g_p0 || g_p1;
-    if (!gx && !want_par) return GFX_EINVAL;
-    // a gradient of something that is not there (or, for the post gain under inverse_post_gain, not used)
-    if ((g_log_pre_gain && !log_pre_gain) || (g_log_post_gain && (!log_post_gain || inverse_post_gain)) || (g_p0 && !p0) ||
-        (g_p1 && mode != GFX_WS_PIECEWISE))
-        return GFX_EINVAL;
+    const WsGrads grads{g_log_pre_gain, g_log_post_gain, g_p0, g_p1};
+    if (ws_check_grads(grads, gx, mode, inverse_post_gain, log_pre_gain, log_post_gain, p0) != GFX_OK) return GFX_EINVAL;
+    const bool want_par = grads.any();
     if (gx) {
-        if (omap.inner <= 0 || os_neg(xmap) || os_neg(gmap) || os_neg(omap)) return GFX_EINVAL;
-        if (ws_overlap(gx, omap, x, xmap, R, C, L) || ws_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
+        if (omap.inner <= 0 || map_negative(xmap) || map_negative(gmap) || map_negative(omap)) return GFX_EINVAL;
+        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
     }
     const bool center = dc && gx;
-    float *part = nullptr, *dcpart = nullptr, *gmean = nullptr;
-    if (want_par || center) {
-        if (!ws) return GFX_EINVAL;
-        if (ws_bytes < gfx_oversampled_waveshaper_bwd_ws_bytes(R, C, L, K, factor)) return GFX_ENOSPC;
-        float* w = static_cast<float*>(ws);
-        if (want_par) part = w;
-        if (center) {
-            dcpart = w + (size_t)R * a.NS * C * a.ntiles;
-            gmean = dcpart + (size_t)R * C * a.ntiles;
-        }
-    }
+    const int64_t npart = C * a.ntiles;              // partials of a row's sum, of a row-channel's: a.ntiles
+    WsBwdSpace sp;
+    const int src = ws_bwd_carve(ws, ws_bytes, R, C, K, (size_t)npart, (size_t)a.ntiles, want_par, center, sp);
+    if (src != GFX_OK) return src;
     a.gmap = gmap;
     a.ymap = gx ? omap : xmap;
     a.want_par = want_par;
@@ -558,9 +492,9 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
     const dim3 grid((unsigned)(R * C * a.ntiles));
     hipStream_t st = (hipStream_t)stream;
 #define GFX_OS_BWD(M)                                                                                                          \
-    if (os_lds_attribute(os_bwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                 \
+    if (allow_lds(os_bwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                        \
     hipLaunchKernelGGL(os_bwd_kernel<M>, grid, dim3(OS_THREADS), lds, st, x, gy, gx, h_up, h_dn, log_pre_gain, log_post_gain, \
-                       p0, p1, dc, part, dcpart, a)
+                       p0, p1, dc, sp.part, sp.dcpart, a)
     switch (mode) {
         case GFX_WS_TANH: GFX_OS_BWD(GFX_WS_TANH); break;
         case GFX_WS_PIECEWISE: GFX_OS_BWD(GFX_WS_PIECEWISE); break;
@@ -569,15 +503,9 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
     }
 #undef GFX_OS_BWD
     if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    if (part || dcpart) {
-        const int64_t items = R * (a.NS > (int)C ? a.NS : (int)C);
-        const int64_t nb = (items + 255) / 256;
-        hipLaunchKernelGGL(os_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, st, part, dcpart,
-                           gmean, g_log_pre_gain, g_log_post_gain, g_p0, g_p1, R, (int)C, L, a.NS, a.ntiles, mode, (int)K);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (ws_bwd_finish(sp, grads, R, C, L, K, npart, a.ntiles, mode, st) != GFX_OK) return GFX_ELAUNCH;
     if (center) {
-        hipLaunchKernelGGL(os_sub_mean_kernel, grid, dim3(OS_THREADS), 0, st, gx, omap, gmean, (int)C, L, a.T, a.ntiles);
+        hipLaunchKernelGGL(os_sub_mean_kernel, grid, dim3(OS_THREADS), 0, st, gx, omap, sp.gmean, (int)C, L, a.T, a.ntiles);
         if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
     }
     return GFX_OK;

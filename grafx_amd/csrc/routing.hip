@@ -8,11 +8,7 @@
 //   out[b, j, c, n] = sum_{e in [seg[j], seg[j+1])} buf[b, src[e], c, n]
 // Edges arrive sorted by (destination, source) (prepare.py:115-119), so every destination's
 // sources are one contiguous run and are added in that order.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 
 #ifndef GFX_GATHER_UNROLL
 #define GFX_GATHER_UNROLL 1
@@ -118,12 +114,6 @@ struct GainMixArgs {
     int64_t L4;
 };
 
-__device__ __forceinline__ int64_t gm_row_off(const gfx_rowmap_t& m, unsigned r, int c) {
-    const unsigned inner = (unsigned)m.inner;
-    const unsigned q = r / inner, rem = r - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
-
 template <int NA>
 __global__ __launch_bounds__(256) void gain_mix_kernel(GainMixArgs a) {
     const unsigned g = blockIdx.y;
@@ -158,12 +148,12 @@ __global__ __launch_bounds__(256) void gain_mix_kernel(GainMixArgs a) {
         for (int j = 0; j < a.inner; ++j) {
             const unsigned r = g * (unsigned)a.inner + (unsigned)j;
             const float g0 = expf(a.log_gain[2 * (int64_t)r]), g1 = expf(a.log_gain[2 * (int64_t)r + 1]);
-            const float4 x0 = reinterpret_cast<const float4*>(a.x + gm_row_off(a.xmap, r, 0))[i];
-            const float4 x1 = a.Cin == 2 ? reinterpret_cast<const float4*>(a.x + gm_row_off(a.xmap, r, 1))[i] : x0;
+            const float4 x0 = reinterpret_cast<const float4*>(a.x + row_off(a.xmap, r, 0))[i];
+            const float4 x1 = a.Cin == 2 ? reinterpret_cast<const float4*>(a.x + row_off(a.xmap, r, 1))[i] : x0;
             const float4 y0 = make_float4(x0.x * g0, x0.y * g0, x0.z * g0, x0.w * g0);
             const float4 y1 = make_float4(x1.x * g1, x1.y * g1, x1.z * g1, x1.w * g1);
-            nt_store(reinterpret_cast<float4*>(a.y + gm_row_off(a.ymap, r, 0)) + i, y0);
-            nt_store(reinterpret_cast<float4*>(a.y + gm_row_off(a.ymap, r, 1)) + i, y1);
+            nt_store(reinterpret_cast<float4*>(a.y + row_off(a.ymap, r, 0)) + i, y0);
+            nt_store(reinterpret_cast<float4*>(a.y + row_off(a.ymap, r, 1)) + i, y1);
             settle((uint64_t)a.sched[j], y0, y1);
         }
         for (int e = a.n_pre; e < a.n_pre + a.n_post; ++e) extra(e);

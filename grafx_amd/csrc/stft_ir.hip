@@ -16,11 +16,7 @@
 //
 // Three schedules: the full basis on the matrix cores (n_fft > 384), the half basis on the matrix cores (n_fft <= 384),
 // and frames by FFT with the overlap-add in LDS (n_fft = 384, hop = 192; its backward is stft_ir_bwd.hip).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "small_dft.hpp"
 #include "stft_ir.hpp"
 
@@ -554,9 +550,7 @@ int gfx_stft_reverb_ir_f32(const float* noise_stft, int64_t noise_rows, const fl
         static_assert(lds <= 160 * 1024, "LDS");
         const unsigned nwg = (unsigned)gfx::fft384_row_workgroups(ir_len);
         auto kern = gfx::stft_ir_fft384_kernel<FR, LN>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return GFX_ELAUNCH;
+        if (gfx::allow_lds(kern, lds) != GFX_OK) return GFX_ELAUNCH;
         hipLaunchKernelGGL(kern, dim3(nwg, (unsigned)R), dim3(FR * LN), lds, st, noise_stft, init_log_magnitude,
                            delta_log_magnitude, gain_env_log_magnitude, window, basis + gfx::basis_tables_off(n_fft), ir,
                            partial, a, ms_to_lr);

@@ -39,8 +39,8 @@ __global__ __launch_bounds__(THREADS) void stft_loss_sums_kernel(const float* __
     const Image im = carve<LOGN>(stft_loss_lds);
     const int64_t row = blockIdx.x / (unsigned)chunks;
     const int chunk = (int)(blockIdx.x % (unsigned)chunks);
-    const float* p = pred + row_off(pmap, row);
-    const float* t = target + row_off(tmap, row);
+    const float* p = pred + sig_row_off(pmap, row);
+    const float* t = target + sig_row_off(tmap, row);
     build_tables<LOGN>(im, window);
     Sums s = {0.0f, 0.0f, 0.0f, 0.0f};
     const int64_t m0 = (int64_t)chunk * RUN * NB;
@@ -131,9 +131,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 8)))
     const int64_t row = blockIdx.x / (unsigned)segs;
     const int64_t s0 = (int64_t)(blockIdx.x % (unsigned)segs) * SEG;
     const int64_t s1 = lo(s0 + SEG, g.L);          // one past the last owned sample
-    const float* p = pred + row_off(pmap, row);
-    const float* t = target + row_off(tmap, row);
-    float* out = gpred + row_off(gmap, row);
+    const float* p = pred + sig_row_off(pmap, row);
+    const float* t = target + sig_row_off(tmap, row);
+    float* out = gpred + sig_row_off(gmap, row);
     const float cA = coef[row * 3], cE = coef[row * 3 + 1], cD = coef[row * 3 + 2];
     const int64_t last = g.L - 1, half = HALF, n = N, hop = g.hop;
 

@@ -2,11 +2,7 @@
 // loss of stft_band_loss.hip: the LDS image, the sample ring, the radix-2 passes, the per-bin formulas, the geometry, and on
 // the host the argument check of the four entries and the launch of the one finish kernel.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 
 namespace gfx {
 namespace stftloss {
@@ -20,7 +16,8 @@ constexpr int CELLS = SEG / THREADS;        // this many per thread, in register
 __device__ __forceinline__ int64_t lo(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ int64_t hi(int64_t a, int64_t b) { return a > b ? a : b; }
 
-__device__ __forceinline__ int64_t row_off(const gfx_rowmap_t& m, int64_t r) {
+// (gfx::row_off64 with c = 0 changed the code of every kernel here by an instruction or two)
+__device__ __forceinline__ int64_t sig_row_off(const gfx_rowmap_t& m, int64_t r) {
     return (r / m.inner) * m.stride_outer + (r % m.inner) * m.stride_inner;
 }
 

@@ -27,7 +27,7 @@
 // read it down / up words apart, which is conflict-free except for decimation by an even factor (2-way for 2, 4-way for 4).
 // The first output's quotient and phase are the only divisions of a lane; the next ones follow by addition.
 //
-#include "biquad_common.hpp"
+#include "common.hpp"
 
 namespace gfx {
 
@@ -36,7 +36,6 @@ constexpr int UF_THREADS = 256;
 constexpr int UF_MAX_RATIO = 1024;
 constexpr int UF_MAX_TAPS = 16384;
 constexpr int UF_SPAN_PREF = 8192;               // samples of x a pass stages, where a pass of more than one output can choose
-constexpr int64_t UF_MAX_BLOCKS = 0x7fffffffLL;
 constexpr int UF_FIN_WAVES = 4;
 
 struct UfPart {          // a tile's largest |y| and the lowest output index that attains it
@@ -87,12 +86,11 @@ __global__ __launch_bounds__(UF_THREADS) void upfirdn_kernel(const float* __rest
     const int64_t m0 = tile * UF_TILE;
     // k up of the sample before the first one any output of the tile can reach, split into kbase up + r0
     const int64_t lo = m0 * a.down + a.offset - (a.N - 1) - up;
-    int64_t kbase = lo / up;
-    if (kbase * up > lo) --kbase;                                 // floor, also below zero
+    const int64_t kbase = floor_div(lo, up);
     const int r0 = (int)(lo - kbase * up);                        // 0 .. up - 1
     const int left = (int)(a.M - m0 < UF_TILE ? a.M - m0 : UF_TILE);
-    const float* xrow = x + brow_off(a.xmap, r, c);
-    float* yrow = PEAK ? nullptr : y + brow_off(a.ymap, r, c) + m0;
+    const float* xrow = x + row_off(a.xmap, r, c);
+    float* yrow = PEAK ? nullptr : y + row_off(a.ymap, r, c) + m0;
     const int sq = UF_THREADS * a.down / up, sr = UF_THREADS * a.down - sq * up;   // a lane's next output: 256 down further
     float bv = -1.0f;
     int bi = 0x7fffffff;
@@ -199,7 +197,7 @@ static int uf_prepare(const float* x, gfx_rowmap_t xmap, const float* h, int64_t
     if (R > 0x7fffffffLL || C > 0x7fffffffLL || R * C > 0x7fffffffLL) return GFX_EINVAL;
     if (M > INT64_MAX / (2 * UF_MAX_RATIO)) return GFX_EINVAL;             // m down + offset stays in 64 bits
     const int64_t ntiles = uf_tiles(M);
-    if (ntiles > UF_MAX_BLOCKS / (R * C)) return GFX_EINVAL;               // grid.x of the tile kernel
+    if (ntiles > MAX_GRID_X / (R * C)) return GFX_EINVAL;               // grid.x of the tile kernel
     int64_t sub = UF_TILE;
     while (sub > 1 && uf_span(sub, N, up, down) > UF_SPAN_PREF) sub /= 2;
     a.xmap = xmap;
@@ -218,9 +216,7 @@ static int uf_prepare(const float* x, gfx_rowmap_t xmap, const float* h, int64_t
 template <bool PEAK>
 static int uf_launch(const float* x, const float* h, float* y, UfPart* part, const UfArgs& a, int64_t rcs, size_t lds,
                      hipStream_t s) {
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(upfirdn_kernel<PEAK>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return GFX_ELAUNCH;
+    if (allow_lds(upfirdn_kernel<PEAK>, lds) != GFX_OK) return GFX_ELAUNCH;
     hipLaunchKernelGGL(upfirdn_kernel<PEAK>, dim3((unsigned)(rcs * a.ntiles)), dim3(UF_THREADS), lds, s, x, h, y, part, a);
     return GFX_OK;
 }

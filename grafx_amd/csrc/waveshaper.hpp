@@ -1,22 +1,13 @@
 // The per-sample math of the memoryless waveshapers, shared by the streaming kernels (nonlinear.hip) and the oversampled
 // tile kernels (oversampled.hip): the row's constants, the shape s with its gains, one backward step of NV samples with the
-// terms of every parameter sum, and the host-side test whether two mapped signals share an element.
+// terms of every parameter sum, and on the host the argument checks and the workspace layout that the entries of both
+// files share.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 
 namespace gfx {
 
 constexpr int WS_MAX_K = 32;
-
-__device__ __forceinline__ int64_t nrow_off(const gfx_rowmap_t& m, int64_t r, int c) {
-    const unsigned inner = (unsigned)m.inner, rr = (unsigned)r;
-    const unsigned q = rr / inner, rem = rr - q * inner;
-    return (int64_t)q * m.stride_outer + (int64_t)rem * m.stride_inner + (int64_t)c * m.stride_ch;
-}
 
 struct WsRow {
     float pre, post, dc;
@@ -204,57 +195,62 @@ __device__ __forceinline__ void bwd_samples(const float (&xs)[NV], const float (
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
+// ---- host side: what the streaming and the oversampled entries check and lay out alike ------------------------------
+// the shaper's own arguments; K becomes 0 for the shapers that have no polynomial
+static inline int ws_check_shaper(int mode, int inverse_post_gain, const float* log_pre_gain, const float* p0, const float* p1,
+                                  int64_t& K) {
+    if (mode < GFX_WS_TANH || mode > GFX_WS_CHEBYSHEV) return GFX_EINVAL;
+    if (inverse_post_gain && !log_pre_gain) return GFX_EINVAL;
+    if (mode == GFX_WS_PIECEWISE && (!p0 || !p1)) return GFX_EINVAL;
+    const bool poly = mode == GFX_WS_POWER || mode == GFX_WS_CHEBYSHEV;
+    if (poly && (!p0 || K < 1 || K > WS_MAX_K)) return GFX_EINVAL;
+    if (!poly) K = 0;
+    return GFX_OK;
 }
 
-// [lo, hi) in floats that a mapped (R, C, L) signal covers (strides >= 0)
-static inline void map_span(const float* p, const gfx_rowmap_t& m, int64_t R, int64_t C, int64_t L, const float*& lo,
-                            const float*& hi) {
-    const int64_t nin = R < m.inner ? R : m.inner;
-    lo = p;
-    hi = p + ((R - 1) / m.inner) * m.stride_outer + (nin - 1) * m.stride_inner + (C - 1) * m.stride_ch + L;
+struct WsGrads {                 // the parameter gradients a backward entry may be asked for
+    float *pre, *post, *p0, *p1;
+    bool any() const { return pre || post || p0 || p1; }
+};
+
+// something to compute, and no gradient of something that is not there (or, for the post gain under inverse_post_gain, not
+// used)
+static inline int ws_check_grads(const WsGrads& g, const float* gx, int mode, int inverse_post_gain, const float* log_pre_gain,
+                                 const float* log_post_gain, const float* p0) {
+    if (!gx && !g.any()) return GFX_EINVAL;
+    if ((g.pre && !log_pre_gain) || (g.post && (!log_post_gain || inverse_post_gain)) || (g.p0 && !p0) ||
+        (g.p1 && mode != GFX_WS_PIECEWISE))
+        return GFX_EINVAL;
+    return GFX_OK;
 }
 
-// Is `delta` a sum of d_i * stride_i with |d_i| < n_i over the dimensions from i on (strides sorted, largest first)?
-static inline bool ws_reachable(int64_t delta, const int64_t (*dims)[2], int nd, int i) {
-    if (i == nd) return delta == 0;
-    const int64_t st = dims[i][0], n = dims[i][1], qd = delta / st;
-    for (int64_t c = qd; c <= qd + 1; ++c) {
-        if (c >= n) continue;
-        const int64_t rest = delta - c * st;
-        if (ws_reachable(rest < 0 ? -rest : rest, dims, nd, i + 1)) return true;
+// The backward workspace, in floats: npart partials of each of a row's ws_nsums(K) sums, ndc partials of each row-channel's
+// sum of gx, the row-channels' means of gx.
+struct WsBwdSpace {
+    float *part, *dcpart, *gmean;
+};
+static inline size_t ws_bwd_floats(int64_t R, int64_t C, int64_t K, size_t npart, size_t ndc) {
+    const size_t rcs = (size_t)R * (size_t)C;
+    return (size_t)R * (size_t)ws_nsums(K) * npart + rcs * ndc + rcs;
+}
+static inline int ws_bwd_carve(void* ws, size_t ws_bytes, int64_t R, int64_t C, int64_t K, size_t npart, size_t ndc,
+                               bool want_par, bool center, WsBwdSpace& s) {
+    s.part = s.dcpart = s.gmean = nullptr;
+    if (!want_par && !center) return GFX_OK;
+    if (!ws) return GFX_EINVAL;
+    if (ws_bytes < sizeof(float) * ws_bwd_floats(R, C, K, npart, ndc)) return GFX_ENOSPC;
+    float* w = static_cast<float*>(ws);
+    if (want_par) s.part = w;
+    if (center) {
+        s.dcpart = w + (size_t)R * (size_t)ws_nsums(K) * npart;
+        s.gmean = s.dcpart + (size_t)R * (size_t)C * ndc;
     }
-    return false;
+    return GFX_OK;
 }
 
-// Do two mapped signals share an element?  Exact for two views with the same positive strides (two node ranges of one
-// render buffer interleave in memory without touching), the covered ranges otherwise.
-static inline bool ws_overlap(const float* a, const gfx_rowmap_t& am, const float* b, const gfx_rowmap_t& bm, int64_t R,
-                              int64_t C, int64_t L) {
-    const float *alo, *ahi, *blo, *bhi;
-    map_span(a, am, R, C, L, alo, ahi);
-    map_span(b, bm, R, C, L, blo, bhi);
-    if (!(alo < bhi && blo < ahi)) return false;
-    const int64_t nin = R < am.inner ? R : am.inner, nout = (R + am.inner - 1) / am.inner;
-    const bool same = am.inner == bm.inner && am.stride_outer == bm.stride_outer && am.stride_inner == bm.stride_inner &&
-                      am.stride_ch == bm.stride_ch && (nout == 1 || am.stride_outer > 0) &&
-                      (nin == 1 || am.stride_inner > 0) && (C == 1 || am.stride_ch > 0) && R % am.inner == 0;
-    if (!same) return true;
-    int64_t dims[4][2] = {{am.stride_outer, nout}, {am.stride_inner, nin}, {am.stride_ch, C}, {1, L}};
-    int nd = 0;
-    for (int i = 0; i < 4; ++i)
-        if (dims[i][1] > 1) { dims[nd][0] = dims[i][0]; dims[nd][1] = dims[i][1]; ++nd; }
-    for (int i = 1; i < nd; ++i)                       // insertion sort, largest stride first
-        for (int j = i; j > 0 && dims[j][0] > dims[j - 1][0]; --j) {
-            const int64_t s0 = dims[j][0], s1 = dims[j][1];
-            dims[j][0] = dims[j - 1][0]; dims[j][1] = dims[j - 1][1];
-            dims[j - 1][0] = s0; dims[j - 1][1] = s1;
-        }
-    const int64_t delta = a > b ? a - b : b - a;
-    return ws_reachable(delta, dims, nd, 0);
-}
+// a row's npart partials of every sum -> the parameter gradients, a row-channel's ndc partials -> its mean input gradient
+// (ws_bwd_finish_kernel, nonlinear.hip); nothing to do where both part and dcpart are null
+int ws_bwd_finish(const WsBwdSpace& s, const WsGrads& g, int64_t R, int64_t C, int64_t L, int64_t K, int64_t npart, int64_t ndc,
+                  int mode, hipStream_t stream);
 
 }  // namespace gfx
