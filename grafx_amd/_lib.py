@@ -130,6 +130,11 @@ SIGNATURES = {
     "gfx_limiter_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),
     "gfx_limiter_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, f32p, f32p, i64, i64, i64, i64, f32p, RowMap,
                                            f32p, vp, sz, vp]),
+    "gfx_moddelay_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, i64, i64, i64, f32p, f32p, f32p, f32p, f32p,
+                                        f32p, f32p, vp, f32p, vp, vp]),
+    "gfx_moddelay_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),
+    "gfx_moddelay_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, i64, i64, i64, f32p, f32p, f32p, f32p, f32p,
+                                            f32p, f32p, RowMap, f32p, f32p, f32p, f32p, f32p, f32p, vp, sz, vp]),
     "gfx_gather_sum_f32": (ctypes.c_int, [f32p, i64, i64, i64, vp, vp, f32p, i64, i64, i64, i64, i64, i64, i64, vp]),
     "gfx_gather_sum_fanout_f32": (ctypes.c_int, [f32p, i64, i64, i64, vp, vp, i64, f32p, i64, i64, i64, i64, i64, i64, i64, vp]),
     "gfx_istft_basis_bytes": (sz, [i64]),

@@ -731,6 +731,38 @@ class LimiterFn(torch.autograd.Function):
                 None, None)
 
 
+class ModulatedDelayFn(torch.autograd.Function):
+    """The modulated delay line (ops.moddelay, without a state) as one autograd node: forward is the fused inference
+    kernel, backward one gfx_moddelay_bwd_f32 call that asks only for what ``needs_input_grad`` wants -- instead of an
+    index tensor, taps x V gathers of the signal's size and their ``index_add_`` (float atomics) of a torch composition.
+    Saved: x and the six parameter arrays (the physical ones of ops.moddelay).  There is no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, delay, depth, rate, phase, gain, dry, max_delay, interp):
+        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+            x = x.contiguous()
+        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
+            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+        else:
+            y = ops.moddelay(x, delay, depth, rate, phase, gain, dry, max_delay, interp)
+        ctx.save_for_backward(x, delay, depth, rate, phase, gain, dry)
+        ctx.cfg = (max_delay, interp)
+        return y.view(x.shape) if four else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, *params = ctx.saved_tensors
+        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+            gy = gy.contiguous()
+        want = [name for name, need in zip(ops.MODDELAY_GRADS, ctx.needs_input_grad) if need]
+        gx, *gp = ops.moddelay_bwd(x, gy, *params, *ctx.cfg, out=_sink_for(x) if "x" in want else None, want=want)
+        return (None if gx is None else gx.view(x.shape), *(None if g is None else g.reshape(p.shape) for g, p in zip(gp, params)),
+                None, None)
+
+
 class StftReverbIrFn(torch.autograd.Function):
     """The taps of STFTMaskedNoiseReverb (reverb.py:161-200, ms_to_lr, normalize_impulse) for n_fft = 384, hop = 192 as one
     autograd node: forward is the inference kernel (``ops.stft_reverb_ir``, "fft" schedule; times ``row_gain`` when

@@ -1452,6 +1452,131 @@ def limiter_bwd(x, gy, log_ceiling, h, lookahead, hold=0, compensate=False, out=
     return gx, gc
 
 
+# ----------------------------------------------------------------------------------------- modulated delay line
+MODDELAY_MAX_DELAY = 8192
+MODDELAY_MAX_VOICES = 8
+MODDELAY_GRADS = ("x", "delay", "depth", "rate", "phase", "gain", "dry")
+_MODDELAY_INTERP = {"linear": 0, "cubic": 1}
+
+
+def moddelay_tile(max_delay, channels):
+    """Samples of a row that one workgroup of the modulated-delay kernels produces (MD_TILE in csrc/moddelay.hip): 2048
+    for every ``max_delay`` and channel count -- the channels pass through the same LDS one after the other, and the
+    largest backward tile (the read positions of 2048 + 8192 + 4 samples) is 60 KiB, two workgroups per CU."""
+    _int_in("moddelay_tile", "max_delay", max_delay, 2, MODDELAY_MAX_DELAY)
+    _int_in("moddelay_tile", "channels", channels, 1, 2 ** 31 - 1)
+    return 2048
+
+
+def _moddelay_args(what, x, delay, depth, rate, phase, gain, dry, max_delay, interp):
+    """The configuration and the parameter shapes of the modulated-delay pair, checked before anything is allocated ->
+    (the signal's row map, R, C, L, V, the interpolation's number, the six parameter arrays in the entries' shapes)."""
+    _int_in(what, "max_delay", max_delay, 2, MODDELAY_MAX_DELAY)
+    if interp not in _MODDELAY_INTERP:
+        raise ValueError(f"{what}: interp={interp!r} must be one of {sorted(_MODDELAY_INTERP)}")
+    xmap, R, C, L = rowmap(x)
+    if delay.ndim != 2 or delay.shape[0] != R or not 1 <= delay.shape[1] <= MODDELAY_MAX_VOICES:
+        raise ValueError(f"{what}: delay must be ({R}, V) with V in 1..{MODDELAY_MAX_VOICES}, got {tuple(delay.shape)}")
+    V = delay.shape[1]
+    for name, p, shape in (("depth", depth, (R, V)), ("rate", rate, (R, V)), ("phase", phase, (R, V, C)),
+                           ("gain", gain, (R, V, C))):
+        _expect(p, shape, f"{what}: {name}")
+    if dry.numel() != R:
+        raise ValueError(f"{what}: {dry.numel()} dry gains for {R} rows")
+    return xmap, R, C, L, V, _MODDELAY_INTERP[interp], (delay, depth, rate, phase, gain, dry.reshape(R))
+
+
+def _moddelay_position(pos, R, device, what):
+    """The position half of a modulated-delay state: a contiguous int64 (R,) tensor on the signal's device."""
+    if not isinstance(pos, torch.Tensor) or pos.device != device or pos.dtype != torch.int64 or tuple(pos.shape) != (R,) \
+            or not pos.is_contiguous():
+        got = f"{tuple(pos.shape)} {pos.dtype} on {pos.device}" if isinstance(pos, torch.Tensor) else type(pos).__name__
+        raise ValueError(f"{what}: the state's position must be a contiguous int64 tensor of shape ({R},) on {device}, got {got}")
+    return pos
+
+
+@_on_device
+def moddelay(x, delay, depth, rate, phase, gain, dry, max_delay, interp="cubic", out=None, state=None, return_state=False):
+    """Modulated delay line in one fused pass (gfx_moddelay_f32).  Per row r, channel c and voice v, at the absolute
+    position p of sample n (p = n, or the state's position + n):
+
+        theta = rate[r,v] p + phase[r,v,c]                             cycles; in double, reduced mod 1
+        d     = clamp(delay[r,v] + depth[r,v] sin(2 pi theta), 1, max_delay)   samples; in double
+        i = floor(d), f = d - i;   u[v,c,n] = sum_j l_j(f) x[c, n - i - j]
+        y[c,n] = dry[r] x[c,n] + sum_v gain[r,v,c] u[v,c,n]
+
+    with the linear (j = 0, 1) or third-order Lagrange (j = -1 .. 2) weights l_j of ``interp``.  ``delay``, ``depth``,
+    ``rate``: (R, V) with V <= 8, in samples, samples and cycles per sample; ``phase`` (cycles), ``gain``: (R, V, C);
+    ``dry``: (R,) or (R, 1); float32 on the GPU.  The caller's contract, which cannot be checked without reading the
+    parameters back: 2 pi rate depth <= 1/2 -- outside it nothing is read or written out of place, and the values (of
+    the backward in particular) are unspecified.
+
+    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``out`` may never share memory with ``x``.  ``state``:
+    the pair (history, position) -- the last max_delay + 2 input samples, contiguous float32 (R, C, max_delay + 2), oldest
+    first, and the samples rendered so far, contiguous int64 (R,) on the device (None: silence at position 0); with
+    ``state`` or ``return_state`` the new pair comes back too, and blocks cut anywhere give the bits of the one-call
+    output.  -> y, or (y, state).  Equal bits from call to call; a row's result does not depend on the other rows."""
+    what = "moddelay"
+    _require_gpu(x, delay, depth, rate, phase, gain, dry, out)
+    xmap, R, C, L, V, mode, params = _moddelay_args(what, x, delay, depth, rate, phase, gain, dry, max_delay, interp)
+    S = max_delay + 2
+    zi = pos = None
+    if state is not None:
+        if not isinstance(state, (tuple, list)) or len(state) != 2:
+            raise ValueError(f"{what}: state must be the pair (history, position)")
+        zi = _state(state[0], (R, C, S), what, "the state's history")
+        pos = _moddelay_position(state[1], R, x.device, what)
+        if zi is None:
+            raise ValueError(f"{what}: state must be the pair (history, position)")
+    stateful = state is not None or return_state
+    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, zi, pos, *params))
+    zf = torch.empty((R, C, S), dtype=torch.float32, device=x.device) if stateful else None
+    pos_out = torch.empty(R, dtype=torch.int64, device=x.device) if stateful else None
+    pin = _Pin()
+    with _timed("moddelay_kernel", 8 * R * C * L):
+        check(lib().gfx_moddelay_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, V, mode, max_delay, *(pin(p) for p in params),
+                                     _ptr(zi), _ptr(pos), _ptr(zf), _ptr(pos_out), _stream()), "gfx_moddelay_f32")
+    return (out, (zf, pos_out)) if stateful else out
+
+
+@_on_device
+def moddelay_bwd(x, gy, delay, depth, rate, phase, gain, dry, max_delay, interp="cubic", out=None, want=MODDELAY_GRADS,
+                 ws=None):
+    """Backward of :func:`moddelay` (a call without a state) in one call (gfx_moddelay_bwd_f32) -> (gx, g_delay, g_depth,
+    g_rate, g_phase, g_gain, g_dry), each shaped like its parameter (g_dry (R,)), None for what ``want`` (any of
+    MODDELAY_GRADS) leaves out.  Nothing of the forward is needed but its arguments.  The gradients are taken almost
+    everywhere: the clamp of the delay passes none where it binds.
+
+    ``x``, ``gy``: (R,C,L) or strided (B,n,C,L) views; ``gx`` is ``out`` (any view of the signal's shape, apart from x and
+    gy) or a new (R,C,L) tensor.  ``ws``: a uint8 workspace of at least gfx_moddelay_bwd_ws_bytes(R, C, L, V) bytes to
+    reuse, 8-byte aligned (only the parameter gradients need one).  Equal bits from call to call."""
+    what = "moddelay_bwd"
+    _require_gpu(x, gy, delay, depth, rate, phase, gain, dry, out)
+    xmap, R, C, L, V, mode, params = _moddelay_args(what, x, delay, depth, rate, phase, gain, dry, max_delay, interp)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    _want(what, want, MODDELAY_GRADS)
+    if not want:
+        raise ValueError(f"{what}: no gradient asked for")
+    reads = (x, gy, *params)
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
+        if "x" in want:
+            gx, gxmap = dest
+    shapes = {"delay": (R, V), "depth": (R, V), "rate": (R, V), "phase": (R, V, C), "gain": (R, V, C), "dry": (R,)}
+    grads = [torch.empty(shape, dtype=torch.float32, device=x.device) if name in want else None for name, shape in shapes.items()]
+    pin = _Pin()
+    wsarg = (0, 0)
+    if any(g is not None for g in grads):
+        wsarg = _workspace(what, ws, lib().gfx_moddelay_bwd_ws_bytes(R, C, L, V), x.device, pin, reads, align=8)
+    with _timed("moddelay_bwd_kernel", (8 if gx is None else 12) * R * C * L):
+        check(lib().gfx_moddelay_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, R, C, L, V, mode, max_delay, *(pin(p) for p in params),
+                                         _ptr(gx), gxmap, *(_ptr(g) for g in grads), *wsarg, _stream()), "gfx_moddelay_bwd_f32")
+    return (gx, *grads)
+
+
 # ----------------------------------------------------------------------------------------- reverb IR
 @_on_device
 def istft_basis(window):

@@ -31,6 +31,7 @@ from .filter import (
     StateVariableFilter,
 )
 from .limiter import Limiter, limiter_window
+from .moddelay import ModulatedDelay
 from .nonlinear import (ChebyshevDistortion, PiecewiseTanhDistortion, PowerDistortion, TanhDistortion,
                         oversampling_filters)
 from .reverb import FilteredNoiseShapingReverb, STFTMaskedNoiseReverb

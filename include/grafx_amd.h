@@ -744,6 +744,53 @@ int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
                         const float* log_ceiling, const float* w, int64_t N, int64_t D, int64_t H, int64_t sigma, float* gx,
                         gfx_rowmap_t omap, float* g_log_ceiling, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- modulated delay line (chorus, vibrato, doubling): a delay whose length moves under a sine oscillator ----
+ * For every row r of C channels and V voices, with p = pos_in[r] + n the absolute position of sample n (p = n without a
+ * state), interp 0 (linear, j in {0, 1}) or 1 (third-order Lagrange on the nodes j in {-1, 0, 1, 2}):
+ *   theta[v,c,n] = rate[r,v] p + phase[r,v,c]                            cycles; evaluated in double, reduced mod 1
+ *   d[v,c,n]     = clamp(delay[r,v] + depth[r,v] sin(2 pi theta), 1, Dmax)    samples; in double
+ *   i = floor(d),  f = float32(d - i)
+ *   u[v,c,n]     = sum_j l_j(f) x[c, n - i - j]                          x zero, or the history zi, below the row's start
+ *   y[c,n]       = dry[r] x[c,n] + sum_v gain[r,v,c] u[v,c,n]            0 <= n < L
+ * linear: l_0 = 1 - f, l_1 = f.  cubic: l_-1 = -f(f-1)(f-2)/6, l_0 = (f+1)(f-1)(f-2)/2, l_1 = -(f+1)f(f-2)/2,
+ * l_2 = (f+1)f(f-1)/6.  Dmax = max_delay, 2 .. 8192; V = 1 .. 8.  delay, depth, rate are (R, V), phase and gain (R, V, C),
+ * dry (R), all contiguous.  y is one fmaf chain per sample: dry x first, then the voices ascending, then j ascending,
+ * each term (gain l_j) x -- the same bits whatever tile, block or call a sample falls in.
+ * The contract: 2 pi rate depth <= 1/2 samples per sample.  Then the read position n - i(n) never decreases and takes
+ * each value at most twice, which the backward rests on.  Outside it (any finite parameters) every access stays inside
+ * its buffer and the values are unspecified.
+ * A state is the history zi / zf, the last S = Dmax + 2 input samples, (R, C, S) contiguous, oldest first, and the
+ * position pos_in / pos_out, (R) int64 on the device: zf is a copy of the last S samples of zi || x, pos_out = pos_in + L,
+ * and blocks cut anywhere, each entering with the state the one before left, give the bits of the one-call output.  zi
+ * and pos_in are given together or both null (silence at position 0), so are zf and pos_out (null: not wanted).
+ * y is addressed through its own row map and may not share memory with x.  Tile: 2048 samples of a row per workgroup,
+ * the channels in turn; rows times tiles ride on grid.x.
+ * gfx_moddelay_bwd_f32 is the adjoint for a call without a state (gy, gx through their own row maps).  Almost everywhere:
+ * the clamp passes no gradient where it binds.  With e = gy gain sum_j l'_j(f) x[c, n - i - j]:
+ *   gx[c,k] = dry gy[c,k] + sum_v gain sum_{n, j : n - i(n) - j = k} gy[c,n] l_j(f(n))    (float32, v then n ascending)
+ *   g_gain[v,c] = sum_n gy u,  g_dry = sum_c sum_n gy x,  g_delay[v] = sum_c sum_n e,  g_depth[v] = sum_c sum_n e sin(2 pi theta),
+ *   g_phase[v,c] = sum_n e depth 2 pi cos(2 pi theta),  g_rate[v] = sum_c sum_n e depth 2 pi cos(2 pi theta) p
+ * Each of gx and the six parameter gradients (shaped like their parameters) may be null, not all.  The parameter
+ * gradients are tile sums in double, stored in ws,
+ *   gfx_moddelay_bwd_ws_bytes = 8 R ceil(L / 2048) (1 + 3 V + 2 V C),   0 for a bad argument,
+ * (ws 8-byte aligned; not needed for gx alone) and added per row in a fixed order.  No atomics in either entry: equal bits
+ * from run to run, and a row's result does not depend on the other rows of the call.
+ * GFX_EINVAL before any launch: a null x, y / gy or parameter array; R, C or L <= 0; V outside 1 .. 8; interp other than
+ * 0 and 1; max_delay outside 2 .. 8192; a history without a position or the reverse; zi overlapping zf or pos_in
+ * pos_out; an empty row map or one with a negative stride; an output that overlaps an input; more than 2^31 - 1
+ * row-channels or workgroups; nothing asked for; a parameter gradient without a workspace or with a misaligned one.  A
+ * workspace that is too small is GFX_ENOSPC. */
+int gfx_moddelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, int64_t R, int64_t C, int64_t L, int64_t V,
+                     int64_t interp, int64_t max_delay, const float* delay, const float* depth, const float* rate,
+                     const float* phase, const float* gain, const float* dry, const float* zi, const int64_t* pos_in, float* zf,
+                     int64_t* pos_out, void* stream);
+size_t gfx_moddelay_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t V);
+int gfx_moddelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, int64_t R, int64_t C, int64_t L,
+                         int64_t V, int64_t interp, int64_t max_delay, const float* delay, const float* depth, const float* rate,
+                         const float* phase, const float* gain, const float* dry, float* gx, gfx_rowmap_t gxmap, float* g_delay,
+                         float* g_depth, float* g_rate, float* g_phase, float* g_gain, float* g_dry, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ---- multi-resolution STFT magnitude loss, one resolution per call ------------------------
  * replaces the call site of a training step's loss: torch.stft of the prediction and of the target, their magnitudes
  * and logs, and autograd through all of them.  For rows p = pred[r], t = target[r] of L samples,
