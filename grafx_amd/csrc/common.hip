@@ -3,7 +3,7 @@
 
 #include <mutex>
 
-#include "../../include/grafx_amd.h"
+#include "common.hpp"
 #include "fft_tile.hpp"
 
 namespace gfx {
@@ -44,7 +44,35 @@ const float2* tile_twiddle_table(hipStream_t stream) {
     return tables[dev];
 }
 
+// see common.hpp (launch_history_tail).  Workgroup b copies chunk b % chunks of state row b / chunks.
+__global__ __launch_bounds__(256) void history_tail_kernel(const float* __restrict__ x, gfx_rowmap_t xmap,
+                                                           const float* __restrict__ zi, float* __restrict__ zf, int C,
+                                                           int64_t L, int64_t S, unsigned chunks,
+                                                           const int64_t* __restrict__ pos_in, int64_t* __restrict__ pos_out) {
+    const unsigned rc = blockIdx.x / chunks, ch = blockIdx.x - rc * chunks;
+    const unsigned r = rc / (unsigned)C;
+    const int c = (int)(rc - r * (unsigned)C);
+    const float* xrow = x + row_off(xmap, r, c);
+    const float* zrow = zi ? zi + (int64_t)rc * S : nullptr;
+    float* out = zf + (int64_t)rc * S;
+#pragma unroll
+    for (int q = 0; q < HISTORY_CHUNK / 256; ++q) {
+        const int64_t i = (int64_t)ch * HISTORY_CHUNK + q * 256 + threadIdx.x;
+        if (i >= S) continue;
+        const int64_t k = i + L - S;                           // index into x; negative: still in the old history
+        out[i] = k >= 0 ? xrow[k] : (zrow ? zrow[S + k] : 0.0f);
+    }
+    if (pos_out && c == 0 && ch == 0 && threadIdx.x == 0) pos_out[r] = (pos_in ? pos_in[r] : 0) + L;
+}
 
+int launch_history_tail(const float* x, gfx_rowmap_t xmap, const float* zi, float* zf, int64_t R, int64_t C, int64_t L,
+                        int64_t S, const int64_t* pos_in, int64_t* pos_out, hipStream_t stream) {
+    const int64_t blocks = history_tail_blocks(R, C, S);
+    if (blocks <= 0 || blocks > MAX_GRID_X) return GFX_EINVAL;
+    hipLaunchKernelGGL(history_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, xmap, zi, zf, (int)C, L, S,
+                       (unsigned)((S + HISTORY_CHUNK - 1) / HISTORY_CHUNK), pos_in, pos_out);
+    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+}
 
 }  // namespace gfx
 

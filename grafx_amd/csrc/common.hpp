@@ -1,7 +1,8 @@
 // What every kernel file may need and no operation owns: the offset of a mapped row, the wave-wide sum, the floor of a
 // division, and on the host the dynamic-LDS opt-in and the checks on mapped signals (negative strides, shared elements).
 // A new kernel file starts from this header; it includes no other operation's header to reach one of these.
-// Device code is __forceinline__, host code static inline, the rest constexpr.
+// Device code is __forceinline__, host code static inline, the rest constexpr; the one kernel every streaming operation
+// shares (the history tail) is defined in common.hip and declared here by its launcher.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -111,5 +112,18 @@ static inline bool signals_overlap(const float* a, const gfx_rowmap_t& am, const
     const int64_t delta = a > b ? a - b : b - a;
     return map_reachable(delta, dims, nd, 0);
 }
+
+// ---- the history a streamed block leaves behind (common.hip: history_tail_kernel) ------------------------------------------
+// zf (R, C, S) = the last S samples of zi || x per row-channel, zi (R, C, S) nullable (zeros): zf[i] = k >= 0 ? x[k] :
+// zi[S + k] with k = L - S + i.  A copy, so bit-exact; for L < S the old history shifts down by L.  pos_in / pos_out
+// (nullable, one per row): pos_out[r] = (pos_in ? pos_in[r] : 0) + L, the row's running sample count.  One launch, of one
+// workgroup per HISTORY_CHUNK state samples; GFX_EINVAL when that grid does not fit (an entry that must refuse before
+// its first launch tests history_tail_blocks itself).
+constexpr int64_t HISTORY_CHUNK = 1024;
+static inline int64_t history_tail_blocks(int64_t R, int64_t C, int64_t S) {
+    return R * C * ((S + HISTORY_CHUNK - 1) / HISTORY_CHUNK);
+}
+int launch_history_tail(const float* x, gfx_rowmap_t xmap, const float* zi, float* zf, int64_t R, int64_t C, int64_t L,
+                        int64_t S, const int64_t* pos_in, int64_t* pos_out, hipStream_t stream);
 
 }  // namespace gfx

@@ -200,17 +200,6 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_fwd_kernel(const float* __res
     }
 }
 
-// zf = the last S samples of zi || x per row-channel (a copy: exact, also when L < S and the old state shifts)
-__global__ __launch_bounds__(256) void lim_state_kernel(const float* __restrict__ x, gfx_rowmap_t xmap,
-                                                        const float* __restrict__ zi, float* __restrict__ zf, int C, int64_t L,
-                                                        int S) {
-    const int64_t rc = blockIdx.x;
-    const int64_t r = rc / C;
-    const float* xrow = x + row_off(xmap, r, (int)(rc - r * C));
-    const float* zrow = zi ? zi + rc * S : nullptr;
-    for (int i = threadIdx.x; i < S; i += 256) zf[rc * S + i] = lim_sample(xrow, zrow, L - S + i, L, S);
-}
-
 // The backward tile: gx for T samples k0 .. k0 + left - 1 of a row.  Local q index j stands for q = k0 + j, 0 <= j < nq =
 // left + M - 1 (every q whose window holds a sample of the tile); the peaks under them start M - 1 earlier, so q = k0 + j
 // sits at peak index j + M - 1, and a(q) is kept as a peak index.
@@ -409,6 +398,7 @@ int gfx_limiter_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
     const int64_t nstate = R * C * a.S;
     if (zi && zf && nstate > 0 && ranges_meet(zi, nstate, zf, nstate)) return GFX_EINVAL;
+    if (zf && history_tail_blocks(R, C, a.S) > MAX_GRID_X) return GFX_EINVAL;   // (past 2^30 state rows: refused before any launch)
     a.ymap = ymap;
     a.pwords = a.T + a.N - 1 + a.M - 1;
     const size_t lds = sizeof(float) * ((size_t)a.N + 2 * (size_t)a.pwords);
@@ -417,10 +407,7 @@ int gfx_limiter_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     hipLaunchKernelGGL(lim_fwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, y, log_ceiling, w, zi, gain,
                        a);
     if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    if (zf && a.S > 0) {
-        hipLaunchKernelGGL(lim_state_kernel, dim3((unsigned)(R * C)), dim3(256), 0, st, x, xmap, zi, zf, (int)C, L, a.S);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (zf && a.S > 0) return launch_history_tail(x, xmap, zi, zf, R, C, L, a.S, nullptr, nullptr, st);
     return GFX_OK;
 }
 

@@ -199,23 +199,6 @@ __global__ __launch_bounds__(MD_THREADS) void md_fwd_kernel(const float* __restr
     }
 }
 
-// zf = the last S samples of zi || x per row-channel (a copy: exact, also when L < S and the old history shifts), and the
-// row's position moved on by L
-__global__ __launch_bounds__(256) void md_state_kernel(const float* __restrict__ x, gfx_rowmap_t xmap,
-                                                       const float* __restrict__ zi, float* __restrict__ zf,
-                                                       const int64_t* __restrict__ pos_in, int64_t* __restrict__ pos_out, int C,
-                                                       int64_t L, int S) {
-    const int64_t rc = blockIdx.x;
-    const int64_t r = rc / C;
-    const int c = (int)(rc - r * C);
-    const float* xrow = x + row_off(xmap, r, c);
-    for (int i = threadIdx.x; i < S; i += 256) {
-        const int64_t k = L - S + i;
-        zf[rc * S + i] = k >= 0 ? xrow[k] : zi ? zi[rc * S + S + k] : 0.0f;
-    }
-    if (c == 0 && threadIdx.x == 0) pos_out[r] = (pos_in ? pos_in[r] : 0) + L;
-}
-
 // gx for the samples k0 .. k0 + left - 1 of a row.  Per voice and channel, local index idx stands for the output sample
 // n = nlo + idx, nlo = k0 + J0 + imin the first n that can read the tile (imin, imax: floor(d) at the ends of the swing);
 // ms[idx] = (n - i(n)) - (k0 + J0) + Dmax = idx + imin - i(n) + Dmax > 0.  Sample k = k0 + tt is read through node j by
@@ -437,6 +420,7 @@ int gfx_moddelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t y
     if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
     const int64_t nstate = R * C * a.S;
     if (zi && zf && (ranges_meet(zi, nstate, zf, nstate) || (pos_in < pos_out + R && pos_out < pos_in + R))) return GFX_EINVAL;
+    if (zf && history_tail_blocks(R, C, a.S) > MAX_GRID_X) return GFX_EINVAL;   // (past 2^30 state rows: refused before any launch)
     a.ymap = ymap;
     const size_t lds = sizeof(float) * (size_t)(MD_TILE + a.S);
     auto fwd = interp ? md_fwd_kernel<1> : md_fwd_kernel<0>;
@@ -445,11 +429,7 @@ int gfx_moddelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t y
     hipLaunchKernelGGL(fwd, dim3((unsigned)(R * a.ntiles)), dim3(MD_THREADS), lds, st, x, y, delay, depth, rate, phase, gain, dry,
                        zi, pos_in, a);
     if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    if (zf) {
-        hipLaunchKernelGGL(md_state_kernel, dim3((unsigned)(R * C)), dim3(256), 0, st, x, xmap, zi, zf, pos_in, pos_out, (int)C, L,
-                           a.S);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (zf) return launch_history_tail(x, xmap, zi, zf, R, C, L, a.S, pos_in, pos_out, st);   // and the rows' positions, moved on by L
     return GFX_OK;
 }
 

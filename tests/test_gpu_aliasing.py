@@ -167,7 +167,7 @@ def test_a_call_that_shares_memory_is_refused_with_every_tensor_untouched(name, 
 # Lengths that cross a boundary of the kernel that runs (and the lengths the issue named, where they differ):
 #   dynamics: 1024-sample tiles (DTILE, csrc/dyn_common.hpp) and 2048 samples per workgroup of the one-shot tiles (OS_GTILE);
 #     the ballistics walk cuts a row into chunks from 512 samples on (csrc/ballistics.hip: chunks of at least 256)
-#   convolution: a tile of a 33-tap filter keeps 16384 - 512 = 15872 samples (conv_geom, csrc/fftconv.hip); the short FIR
+#   convolution: a tile of a 33-tap filter keeps 16384 - 512 = 15872 samples (conv_geom, csrc/fftconv_tile.hpp); the short FIR
 #     writes 4096 samples per workgroup (FM_SEG, csrc/fir_mfma.hip)
 #   cascade: 512 samples per tile (BQ_TILE = 64 lanes x BQ_E, csrc/biquad_kernel.hpp)
 #   the element-wise entries have no tile of their own: they ride along at the dynamics lengths

@@ -17,7 +17,7 @@ TILE_F = 16384
 
 
 def _overlap_of(N):
-    """The tile overlap O of an N-tap filter (csrc/fftconv.hip: conv_geom)."""
+    """The tile overlap O of an N-tap filter (csrc/fftconv_tile.hpp: conv_geom)."""
     return (N - 1 + 511) // 512 * 512 if N <= 8193 else 8192
 
 
@@ -204,6 +204,34 @@ def test_only_the_last_N_minus_1_samples_are_read(N):
     assert torch.equal(ys[0][1], ys[1][1])
     assert torch.equal(ys[0][0], ys[1][0]), "samples older than N - 1 reached the output"
     assert_close(ys[0][0].cpu(), _lin64(x.cpu(), h.cpu(), past1[..., M - (N - 1) :]), 1e-5, f"N={N}")
+
+
+def test_state_of_two_chunks_from_strided_blocks():
+    """The state copy runs on one workgroup per 1024 state samples (launch_history_tail, csrc/common.hip): N = 1501 leaves
+    1500 of them, two chunks, the second partial and no multiple of 256.  Blocks of 700 (shorter than the history, entering
+    without one), 700 (shorter, entering with one: the old history shifts) and 2600 (longer), read as strided (B, n, C, L)
+    views of a wider buffer: after every block the state is the one-call state over the samples so far, bit for bit."""
+    from grafx_amd import ops
+
+    N, B, n, C = 1501, 1, 3, 2
+    cuts = [700, 700, 2600]
+    T = sum(cuts)
+    g = torch.Generator().manual_seed(N)
+    x = torch.randn(B * n, C, T, generator=g)
+    h = torch.randn(B * n, C, N, generator=g) / N**0.5
+    xbuf = torch.full((B, n + 1, C, T + 3), 7.0, device="cuda")
+    xbuf[:, :n, :, :T] = x.view(B, n, C, T).cuda()
+    Hs = ops.fir_spectrum(h.cuda().reshape(B * n * C, N))
+    ys, state, at = [], None, 0
+    for L in cuts:
+        y, state = ops.fftconv_state(xbuf[:, :n, :, at : at + L], Hs, N, C, zi=state)
+        at += L
+        _, whole = ops.fftconv_state(xbuf[:, :n, :, :at], Hs, N, C)
+        assert torch.equal(state, whole), f"state after {at} samples != the one-call state"
+        assert torch.equal(state, _tail(x[..., :at].cuda(), N - 1))
+        ys.append(y.reshape(B * n, C, L))
+    assert_close(torch.cat(ys, -1).cpu(), _lin64(x, h), 1e-5, "strided blocks, N=1501")
+    assert (xbuf[:, n] == 7).all() and (xbuf[..., T:] == 7).all()
 
 
 # ------------------------------------------------------------------------------------------------- rows

@@ -320,6 +320,32 @@ def test_blocks_equal_one_call_in_bits(D, H, N):
     assert torch.equal(first, whole[..., :50])          # zeros mean "nothing came before"
 
 
+def test_blocks_with_a_two_chunk_state_from_strided_views():
+    """The state copy runs on one workgroup per 1024 state samples (launch_history_tail, csrc/common.hip): D, H, N = 1023,
+    500, 64 keep S = 1586 of them, two chunks, the second partial and no multiple of 256.  Blocks of 300 (shorter than S,
+    entering without a state), 300 (shorter, entering with one: the old state shifts) and 3000 (longer), read as strided
+    (B, n, C, L) views of a wider buffer: outputs and every state equal the one-call results bit for bit."""
+    from grafx_amd import ops
+
+    D, H, N = 1023, 500, 64
+    S, B, n, C = D + H + N - 1, 1, 3, 2
+    cuts = [300, 300, 3000]
+    L = sum(cuts)
+    x = l64.burst_rows(B * n, C, L, 29).cuda()
+    lc, w = _ceilings(B * n).cuda(), l64.window(D, N).cuda()
+    xin = torch.zeros(B, n + 2, C, L + 8, device="cuda")[:, 1:1 + n, :, 3:3 + L]
+    xin.copy_(x.view(B, n, C, L))
+    whole, zw = ops.limiter(x, lc, w, D, H, return_state=True)
+    assert zw.shape == (B * n, C, S) and torch.equal(zw, x[..., L - S:])
+    ys, state, at = [], None, 0
+    for m in cuts:
+        y, state = ops.limiter(xin[..., at:at + m], lc, w, D, H, state=state, return_state=True)
+        at += m
+        assert torch.equal(state, ops.limiter(x[..., :at], lc, w, D, H, return_state=True)[1]), at
+        ys.append(y.reshape(B * n, C, m))
+    assert torch.equal(torch.cat(ys, -1), whole) and torch.equal(state, zw)
+
+
 def test_streaming_refusals_and_the_memoryless_module():
     import grafx_amd.processors as P
 

@@ -274,6 +274,33 @@ def test_blocks_equal_one_call_in_bits(V, Dmax, interp):
     assert torch.equal(first, whole[..., :50])          # zeros mean "nothing came before"
 
 
+def test_blocks_with_a_two_chunk_history_from_strided_views():
+    """The history copy runs on one workgroup per 1024 state samples (launch_history_tail, csrc/common.hip): max_delay =
+    1500 keeps S = 1502 of them, two chunks, the second partial and no multiple of 256.  Blocks of 400 (shorter than S,
+    entering without a state), 400 (shorter, entering with one: the old history shifts) and 2500 (longer), read as strided
+    (B, n, C, L) views of a wider buffer: outputs and every history equal the one-call results bit for bit, and the
+    position is the number of samples rendered."""
+    from grafx_amd import ops
+
+    V, Dmax, interp = 3, 1500, "cubic"
+    B, n, C, S = 1, 3, 2, Dmax + 2
+    cuts = [400, 400, 2500]
+    L = sum(cuts)
+    x = m64.bright_rows(B * n, C, L, 31).cuda()
+    params = _cuda(m64.draw_parameters(B * n, V, C, Dmax, 32))
+    whole, (zw, pw) = ops.moddelay(x, *params, Dmax, interp, return_state=True)
+    assert zw.shape == (B * n, C, S) and torch.equal(zw, x[..., L - S:]) and pw.tolist() == [L] * (B * n)
+    xin = _strided(x, B, n)
+    ys, state, at = [], None, 0
+    for m in cuts:
+        y, state = ops.moddelay(xin[..., at:at + m], *params, Dmax, interp, state=state, return_state=True)
+        at += m
+        zs, ps = ops.moddelay(x[..., :at], *params, Dmax, interp, return_state=True)[1]
+        assert torch.equal(state[0], zs) and state[1].tolist() == ps.tolist() == [at] * (B * n)
+        ys.append(y.reshape(B * n, C, m))
+    assert torch.equal(torch.cat(ys, -1), whole) and torch.equal(state[0], zw) and torch.equal(state[1], pw)
+
+
 def test_module_and_node_agree_with_the_op():
     """ModulatedDelay(...)(x, **z) is ops.moddelay on physical(**z); under requires_grad it runs ModulatedDelayFn, whose
     gradients in x and the z parameters match float64 autograd of torch_forward under the policy of this file."""
