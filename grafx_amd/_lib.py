@@ -135,6 +135,12 @@ SIGNATURES = {
     "gfx_moddelay_bwd_ws_bytes": (sz, [i64, i64, i64, i64]),
     "gfx_moddelay_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, i64, i64, i64, f32p, f32p, f32p, f32p, f32p,
                                             f32p, f32p, RowMap, f32p, f32p, f32p, f32p, f32p, f32p, vp, sz, vp]),
+    "gfx_fbdelay_ws_bytes": (sz, [i64, i64, i64]),
+    "gfx_fbdelay_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, i64, i64, i64, i64, f32p, f32p, f32p, f32p, f32p, f32p, f32p,
+                                       f32p, f32p, f32p, vp, sz, vp]),
+    "gfx_fbdelay_bwd_ws_bytes": (sz, [i64, i64, i64]),
+    "gfx_fbdelay_bwd_f32": (ctypes.c_int, [f32p, RowMap, f32p, RowMap, f32p, f32p, i64, i64, i64, i64, f32p, f32p, f32p, f32p,
+                                           f32p, f32p, RowMap, f32p, f32p, f32p, f32p, f32p, vp, sz, vp]),
     "gfx_gather_sum_f32": (ctypes.c_int, [f32p, i64, i64, i64, vp, vp, f32p, i64, i64, i64, i64, i64, i64, i64, vp]),
     "gfx_gather_sum_fanout_f32": (ctypes.c_int, [f32p, i64, i64, i64, vp, vp, i64, f32p, i64, i64, i64, i64, i64, i64, i64, vp]),
     "gfx_istft_basis_bytes": (sz, [i64]),

@@ -763,6 +763,35 @@ class ModulatedDelayFn(torch.autograd.Function):
                 None, None)
 
 
+class FeedbackDelayFn(torch.autograd.Function):
+    """The feedback delay (ops.fbdelay, without a state) as one autograd node: forward is the recursive chunk walk, backward
+    one gfx_fbdelay_bwd_f32 call (the same walk backwards in time, then tile sums) that asks only for what
+    ``needs_input_grad`` wants -- instead of one launch chain per ``delay`` samples with the whole line on autograd's tape.
+    Saved: x, the five parameter arrays (the physical ones of ops.fbdelay) and the two signals q and w the forward writes.
+    There is no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, delay, damping, feedback, dry, wet, max_delay):
+        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
+        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
+            x = x.contiguous()
+        y, (q, w) = ops.fbdelay(x, delay, damping, feedback, dry, wet, max_delay, tape=True)   # (q and w are read: no tape_only)
+        ctx.save_for_backward(x, delay, damping, feedback, dry, wet, q, w)
+        ctx.max_delay = max_delay
+        return y.view(x.shape) if four else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, *params, q, w = ctx.saved_tensors
+        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
+            gy = gy.contiguous()
+        want = [name for name, need in zip(ops.FBDELAY_GRADS, ctx.needs_input_grad) if need]
+        gx, *gp = ops.fbdelay_bwd(x, gy, q, w, *params, ctx.max_delay, out=_sink_for(x) if "x" in want else None, want=want)
+        return (None if gx is None else gx.view(x.shape), *(None if g is None else g.reshape(p.shape) for g, p in zip(gp, params)),
+                None)
+
+
 class StftReverbIrFn(torch.autograd.Function):
     """The taps of STFTMaskedNoiseReverb (reverb.py:161-200, ms_to_lr, normalize_impulse) for n_fft = 384, hop = 192 as one
     autograd node: forward is the inference kernel (``ops.stft_reverb_ir``, "fft" schedule; times ``row_gain`` when

@@ -1577,6 +1577,118 @@ def moddelay_bwd(x, gy, delay, depth, rate, phase, gain, dry, max_delay, interp=
     return (gx, *grads)
 
 
+# ----------------------------------------------------------------------------------------- feedback delay
+FBDELAY_MIN_DELAY = 64
+FBDELAY_MAX_DELAY = 65536
+FBDELAY_CHUNK = 1024           # FB_CHUNK of csrc/fbdelay.hip: the longest run of samples one step of the walk produces
+FBDELAY_GRADS = ("x", "delay", "damping", "feedback", "dry", "wet")
+
+
+def _fbdelay_args(what, x, delay, damping, feedback, dry, wet, max_delay):
+    """The configuration and the parameter shapes of the feedback-delay pair, checked before anything is allocated ->
+    (the signal's row map, R, C, L, the five parameter arrays in the entries' shapes)."""
+    _int_in(what, "max_delay", max_delay, FBDELAY_MIN_DELAY, FBDELAY_MAX_DELAY)
+    xmap, R, C, L = rowmap(x)
+    if C not in (1, 2):
+        raise ValueError(f"{what}: {C} channels, the loop takes 1 or 2")
+    for name, p, shape in (("delay", delay, (R, C)), ("damping", damping, (R, C)), ("feedback", feedback, (R, C, C))):
+        _expect(p, shape, f"{what}: {name}")
+    for name, p in (("dry", dry), ("wet", wet)):
+        if p.numel() != R:
+            raise ValueError(f"{what}: {p.numel()} {name} gains for {R} rows")
+    return xmap, R, C, L, (delay, damping, feedback, dry.reshape(R), wet.reshape(R))
+
+
+@_on_device
+def fbdelay(x, delay, damping, feedback, dry, wet, max_delay, out=None, state=None, return_state=False, tape=False):
+    """Feedback delay (echo, ping-pong) on the recursive chunk walk (gfx_fbdelay_f32).  Per row r and channels c, c':
+
+        i_c = floor(delay[r,c]), f_c = delay[r,c] - i_c                 64 <= delay <= max_delay <= 65536, in samples
+        s_c[n] = (1 - f_c) w_c[n - i_c] + f_c w_c[n - i_c - 1]
+        q_c[n] = (1 - a[r,c]) s_c[n] + a[r,c] q_c[n - 1]                a = damping, 0 <= a < 1
+        w_c[n] = x_c[n] + sum_c' F[r,c,c'] q_c'[n]                      F = feedback
+        y_c[n] = dry[r] x_c[n] + wet[r] q_c[n]
+
+    ``delay``, ``damping``: (R, C) with C = 1 or 2; ``feedback``: (R, C, C); ``dry``, ``wet``: (R,) or (R, 1); float32 on
+    the GPU.  The caller's contract, which cannot be checked without reading the parameters back: every row sum of
+    |F| < 1, 0 <= a < 1 and the delay's range -- outside it nothing is read or written out of place, and the values are
+    unspecified.
+
+    ``x`` / ``out``: (R,C,L) tensors or strided (B,n,C,L) views; ``out`` may never share memory with ``x``.  ``state``:
+    the pair (history, q_last) -- the last max_delay + 1 samples of w, contiguous float32 (R, C, max_delay + 1), oldest
+    first, and the loop filter's last value, (R, C) (None: silence); with ``state`` or ``return_state`` the new pair comes
+    back too.  The walk restarts at each call: blocks agree with the one call to rounding, and the same sequence of calls
+    gives the same bits.  ``tape``: also return the (R,C,L) signals (q, w) that :func:`fbdelay_bwd` reads.
+    -> y, or (y, state), with ``tape`` y, [state,] (q, w).  Equal bits from call to call; a row's result does not depend
+    on the other rows."""
+    what = "fbdelay"
+    _require_gpu(x, delay, damping, feedback, dry, wet, out)
+    xmap, R, C, L, params = _fbdelay_args(what, x, delay, damping, feedback, dry, wet, max_delay)
+    S = max_delay + 1
+    zi = q_in = None
+    if state is not None:
+        if not isinstance(state, (tuple, list)) or len(state) != 2:
+            raise ValueError(f"{what}: state must be the pair (history, q_last)")
+        zi = _state(state[0], (R, C, S), what, "the state's history")
+        q_in = _state(state[1], (R, C), what, "the state's q_last")
+        if zi is None or q_in is None:
+            raise ValueError(f"{what}: state must be the pair (history, q_last)")
+    stateful = state is not None or return_state
+    out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, zi, q_in, *params))
+    zf = torch.empty((R, C, S), dtype=torch.float32, device=x.device) if stateful else None
+    q_out = torch.empty((R, C), dtype=torch.float32, device=x.device) if stateful else None
+    q = torch.empty((R, C, L), dtype=torch.float32, device=x.device) if tape else None
+    w = torch.empty((R, C, L), dtype=torch.float32, device=x.device)        # the line: the entry's workspace
+    pin = _Pin()
+    with _timed("fbdelay_kernel", 12 * R * C * L):
+        check(lib().gfx_fbdelay_f32(_ptr(x), xmap, _ptr(out), ymap, R, C, L, max_delay, *(pin(p) for p in params), _ptr(zi),
+                                    _ptr(q_in), _ptr(zf), _ptr(q_out), _ptr(q), _ptr(w), 4 * w.numel(), _stream()),
+              "gfx_fbdelay_f32")
+    res = (out, (zf, q_out)) if stateful else (out,)
+    if tape:
+        res = (*res, (q, w))
+    return res if len(res) > 1 else out
+
+
+@_on_device
+def fbdelay_bwd(x, gy, q, w, delay, damping, feedback, dry, wet, max_delay, out=None, want=FBDELAY_GRADS, ws=None):
+    """Backward of :func:`fbdelay` (a call without a state) in one call (gfx_fbdelay_bwd_f32) -> (gx, g_delay, g_damping,
+    g_feedback, g_dry, g_wet), each shaped like its parameter (g_dry, g_wet (R,)), None for what ``want`` (any of
+    FBDELAY_GRADS) leaves out.  ``q``, ``w``: the contiguous (R,C,L) signals the forward returned with ``tape=True``.
+
+    ``x``, ``gy``: (R,C,L) or strided (B,n,C,L) views; ``gx`` is ``out`` (any view of the signal's shape, apart from x and
+    gy) or a new (R,C,L) tensor.  ``ws``: a uint8 workspace of at least gfx_fbdelay_bwd_ws_bytes(R, C, L) bytes to reuse,
+    8-byte aligned (the adjoint's line and the tile sums).  Equal bits from call to call."""
+    what = "fbdelay_bwd"
+    _require_gpu(x, gy, q, w, delay, damping, feedback, dry, wet, out)
+    xmap, R, C, L, params = _fbdelay_args(what, x, delay, damping, feedback, dry, wet, max_delay)
+    gmap, Rg, Cg, Lg = rowmap(gy)
+    if (Rg, Cg, Lg) != (R, C, L):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    q = _state(q, (R, C, L), what, "q")
+    w = _state(w, (R, C, L), what, "w")
+    if q is None or w is None:
+        raise ValueError(f"{what}: q and w, the signals of fbdelay(tape=True), are needed")
+    _want(what, want, FBDELAY_GRADS)
+    if not want:
+        raise ValueError(f"{what}: no gradient asked for")
+    reads = (x, gy, q, w, *params)
+    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
+    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
+        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
+        if "x" in want:
+            gx, gxmap = dest
+    shapes = {"delay": (R, C), "damping": (R, C), "feedback": (R, C, C), "dry": (R,), "wet": (R,)}
+    grads = [torch.empty(shape, dtype=torch.float32, device=x.device) if name in want else None for name, shape in shapes.items()]
+    pin = _Pin()
+    wsarg = _workspace(what, ws, lib().gfx_fbdelay_bwd_ws_bytes(R, C, L), x.device, pin, reads, align=8)
+    with _timed("fbdelay_bwd_kernel", 24 * R * C * L):
+        check(lib().gfx_fbdelay_bwd_f32(_ptr(x), xmap, _ptr(gy), gmap, _ptr(q), _ptr(w), R, C, L, max_delay,
+                                        *(pin(p) for p in params), _ptr(gx), gxmap, *(_ptr(g) for g in grads), *wsarg, _stream()),
+              "gfx_fbdelay_bwd_f32")
+    return (gx, *grads)
+
+
 # ----------------------------------------------------------------------------------------- reverb IR
 @_on_device
 def istft_basis(window):

@@ -16,6 +16,7 @@ from .dynamics import (
     NoiseGate,
 )
 from .eq import GraphicEqualizer, NewZeroPhaseFIREqualizer, ParametricEqualizer, ZeroPhaseFIREqualizer
+from .fbdelay import FeedbackDelay
 from .filter import (
     AllPassFilter,
     BandPassFilter,

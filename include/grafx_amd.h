@@ -791,6 +791,50 @@ int gfx_moddelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx
                          float* g_depth, float* g_rate, float* g_phase, float* g_gain, float* g_dry, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* ---- feedback delay (echo, ping-pong): a delay line inside a damped feedback loop ----------
+ * For every row r of C channels (C = 1 or 2), c, c' < C:
+ *   i_c = floor(delay[r,c]),  f_c = delay[r,c] - i_c                     float32; 64 <= delay <= max_delay <= 65536
+ *   s_c[n] = (1 - f_c) w_c[n - i_c] + f_c w_c[n - i_c - 1]               the line's output, linear interpolation
+ *   q_c[n] = (1 - a[r,c]) s_c[n] + a[r,c] q_c[n - 1]                     the loop's one-pole damping, 0 <= a < 1
+ *   w_c[n] = x_c[n] + sum_c' F[r,c,c'] q_c'[n]                           what enters the line
+ *   y_c[n] = dry[r] x_c[n] + wet[r] q_c[n]                               0 <= n < L
+ * delay and damping (a) are (R, C), feedback (F) is (R, C, C), dry and wet (R), all contiguous.  w and q are zero, or the
+ * carried state, below the row's start.  The contract: max_c sum_c' |F[c,c']| < 1, 0 <= a < 1 and the delay's range.
+ * Outside it (NaNs included) the delay is clamped to 64 .. max_delay before it is split, every access stays inside its
+ * buffer, and the values are unspecified.
+ * One workgroup walks a row, all channels together, in chunks of min(min_c i_c, 1024) samples; the rows ride on grid.x.
+ * The line w lives in ws, (R, C, L) floats:  gfx_fbdelay_ws_bytes = 4 R C L,  0 for a bad argument.  After a call ws
+ * holds w; q (nullable) receives the (R, C, L) contiguous signal q -- the two signals the backward reads.
+ * A state is the history zi / zf, the last S = max_delay + 1 samples of w, (R, C, S) contiguous, oldest first, and q_in /
+ * q_out, (R, C), the loop filter's last value.  zi and q_in are given together or both null (silence), so are zf and
+ * q_out (null: not wanted).  The system is time-invariant: a state carries no position.  The chunk grid restarts at each
+ * call, so blocks agree with the one call to rounding, not to the bit; the same sequence of calls gives the same bits.
+ * y is addressed through its own row map and may not share memory with x.
+ * gfx_fbdelay_bwd_f32 is the adjoint for a call without a state, from x, gy and the forward's q and w: n descending,
+ *   lambda_c[n] = (1 - f_c) mu_c[n + i_c] + f_c mu_c[n + i_c + 1],  zeta_c[n] = wet gy_c[n] + sum_c' F[c',c] lambda_c'[n],
+ *   mu_c[n] = (1 - a_c) zeta_c[n] + a_c mu_c[n + 1],                gx_c[n] = dry gy_c[n] + lambda_c[n],
+ *   g_dry = sum_c sum_n gy x,  g_wet = sum_c sum_n gy q,  g_feedback[c,c'] = sum_n lambda_c q_c',
+ *   g_delay[c] = sum_n mu_c (w_c[n - i_c - 1] - w_c[n - i_c]),  g_damping[c] = sum_n mu_c (q_c[n - 1] - s_c[n]) / (1 - a_c).
+ * Each of gx and the five parameter gradients (shaped like their parameters) may be null, not all.  ws holds the tile
+ * sums of the parameter gradients in double and the line mu:
+ *   gfx_fbdelay_bwd_ws_bytes = 8 R ceil(L / 2048) (2 + 2 C + C C) + 4 R C L,   0 for a bad argument,
+ * 8-byte aligned, always needed.  No atomics in either entry: equal bits from run to run, and a row's result does not
+ * depend on the other rows of the call.
+ * GFX_EINVAL before any launch: a null x, y / gy, q / w (backward) or parameter array; R, C or L <= 0; C > 2; max_delay
+ * outside 64 .. 65536; a zi without q_in or the reverse, a zf without q_out or the reverse; zf overlapping zi; an empty
+ * row map or one with a negative stride; an output that overlaps an input; more than 2^31 - 1 rows; nothing asked for; a
+ * missing or misaligned workspace.  A workspace that is too small is GFX_ENOSPC. */
+size_t gfx_fbdelay_ws_bytes(int64_t R, int64_t C, int64_t L);
+int gfx_fbdelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, int64_t R, int64_t C, int64_t L,
+                    int64_t max_delay, const float* delay, const float* damping, const float* feedback, const float* dry,
+                    const float* wet, const float* zi, const float* q_in, float* zf, float* q_out, float* q, void* ws,
+                    size_t ws_bytes, void* stream);
+size_t gfx_fbdelay_bwd_ws_bytes(int64_t R, int64_t C, int64_t L);
+int gfx_fbdelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_rowmap_t gmap, const float* q, const float* w,
+                        int64_t R, int64_t C, int64_t L, int64_t max_delay, const float* delay, const float* damping,
+                        const float* feedback, const float* dry, const float* wet, float* gx, gfx_rowmap_t gxmap, float* g_delay,
+                        float* g_damping, float* g_feedback, float* g_dry, float* g_wet, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- multi-resolution STFT magnitude loss, one resolution per call ------------------------
  * replaces the call site of a training step's loss: torch.stft of the prediction and of the target, their magnitudes
  * and logs, and autograd through all of them.  For rows p = pred[r], t = target[r] of L samples,
