@@ -3,7 +3,9 @@ per-launch timing hook, and the checks of the tensors whose pointers are passed.
 RowMap carries strides only, so a destination, a carried state or a workspace is checked or made here, once, and
 nowhere else: :func:`_output`, :func:`_state` and :func:`_workspace`, all on the aliasing rule of :func:`_apart`.  The
 small checks more than one wrapper needs are here too: :func:`_expect` (a shape), :func:`_int_in` (an integer in a range),
-:func:`_taps` (shared filter taps) and :func:`_want` (the gradients asked of a backward entry)."""
+:func:`_taps` (shared filter taps) and :func:`_pair_state` (a state of two parts).  So is the frame of a backward entry:
+:func:`_want` (the gradients asked of it), :func:`_cotangent` (the shape of dL/dy), :func:`_signal_grad` (where the signal
+gradient goes, and what it must be apart from) and :func:`_param_grads` (the wanted parameter gradients)."""
 import contextvars
 import functools
 
@@ -284,11 +286,51 @@ def _taps(what, name, h, max_taps):
         raise ValueError(f"{what}: {name} must hold 1..{max_taps} taps in one dimension, got {tuple(h.shape)}")
 
 
-def _want(what, want, known):
-    """The gradients a backward entry is asked for are some of the ones it knows."""
+def _want(what, want, known, some=False):
+    """The gradients a backward entry is asked for are some of the ones it knows (``some``: and at least one)."""
     unknown = set(want) - set(known)
     if unknown:
         raise ValueError(f"{what}: unknown gradients {sorted(unknown)} (known: {known})")
+    if some and not want:
+        raise ValueError(f"{what}: no gradient asked for")
+
+
+def _cotangent(what, gy, x, shape):
+    """The cotangent ``gy`` of a backward entry has the (R, C, L) = ``shape`` of the signal ``x`` -> its RowMap."""
+    gmap, *got = rowmap(gy)
+    if tuple(got) != tuple(shape):
+        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    return gmap
+
+
+def _signal_grad(what, want, out, shape, xmap, device, apart):
+    """Where a backward entry writes the signal gradient -> (gx, its RowMap).  Without "x" in ``want`` the entry writes no
+    signal gradient (and takes any row map): (None, ``xmap``, the input's).  Else ``out`` or a new tensor, as
+    :func:`_output` makes it.  A given ``out`` is checked whether or not it is used; ``apart``: everything the call reads
+    and its ``ws``."""
+    if "x" not in want and out is None:
+        return None, xmap
+    dest = _output(out, shape, device, what, apart=apart)
+    return dest if "x" in want else (None, xmap)
+
+
+def _param_grads(want, shapes, device):
+    """The parameter gradients of a backward entry, in the order of ``shapes`` = {name: shape}: a new float32 tensor for a
+    name in ``want``, None for the others (the entry takes a null pointer for a gradient nobody asked for)."""
+    return [torch.empty(shape, dtype=torch.float32, device=device) if name in want else None for name, shape in shapes.items()]
+
+
+def _pair_state(what, state, shape, second, read_second):
+    """The two parts of a stateful entry's ``state`` = (history, ``second``) -> (history, second part), both None without
+    a state.  The history is a :func:`_state` of ``shape``; ``read_second`` checks the other part and returns it."""
+    if state is None:
+        return None, None
+    if not isinstance(state, (tuple, list)) or len(state) != 2:
+        raise ValueError(f"{what}: state must be the pair (history, {second})")
+    zi, other = _state(state[0], shape, what, "the state's history"), read_second(state[1])
+    if zi is None or other is None:
+        raise ValueError(f"{what}: state must be the pair (history, {second})")
+    return zi, other
 
 
 def _row_chunks(rows, limit):

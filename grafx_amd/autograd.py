@@ -145,6 +145,44 @@ def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
+# ----------------------------------------------------------------------------------------- the frame of a node on a fused op
+def _in_place(t):
+    """A signal or a cotangent as the kernels take it: a strided (B,n,C,L) view of the signal buffer is read in place
+    through its row map, and so is anything contiguous; whatever else (a last stride that is not 1, a 3-D view with gaps)
+    is copied."""
+    if t.stride(-1) != 1 or not (t.ndim == 4 or t.is_contiguous()):
+        t = t.contiguous()
+    return t
+
+
+def _signal(x):
+    """How a node takes its signal -> (x as :func:`_in_place` leaves it, whether it is a (B,n,C,L) view, its rows).  The
+    output of a node on a 4-D view comes back as (B,n,C,L) too, so that a strided 4-D gradient can be fed in without a
+    copy."""
+    x = _in_place(x)
+    if x.ndim == 4:
+        return x, True, x.shape[0] * x.shape[1]
+    return x, False, x.shape[0]
+
+
+def _tape_only_output(x, rows):
+    """The output of a node whose output is the processor's output, while `tape_only` is active: its values are not read,
+    so the node skips its forward kernel and hands back the placeholder.  None otherwise: the node runs its op."""
+    return tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device) if tape_only_active() else None
+
+
+def _wanted(names, ctx):
+    """The gradients a node asks of its backward entry: the ``names`` of the inputs that need one, in order."""
+    return [name for name, need in zip(names, ctx.needs_input_grad) if need]
+
+
+def _shaped_like(gx, x, grads, params):
+    """What a backward entry returned, as autograd wants it: the signal gradient viewed like ``x`` (it may be the
+    registered sink, a view already), every parameter gradient in its parameter's shape, None where there is none."""
+    return (None if gx is None else gx.view(x.shape),
+            *(None if g is None else g.reshape(p.shape) for g, p in zip(grads, params)))
+
+
 class LinearConvFn(torch.autograd.Function):
     """y[r,c,n] = sum_k h[r % Rh,cf,k] x[r,cx,n+off-k], n in [0,Lout); channels broadcast 1<->2.
 
@@ -154,14 +192,9 @@ class LinearConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, Lout, off, final=False):
-        # x: (R,C,L), or a strided (B,n,C,L) view of the signal buffer, read in place through its row map; the
-        # output then comes back as (B,n,C,Lout) so that a strided 4-D gradient can be fed in without a copy
-        four = x.ndim == 4
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
+        x, four, rows = _signal(x)     # (R,C,L) or a strided (B,n,C,L) view; the output then comes back as (B,n,C,Lout)
         h = h.contiguous()
         Rh, Cf, N = h.shape
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
         if rows % Rh != 0:
             raise ValueError(f"{rows} signal rows cannot share {Rh} filters")
         ctx.save_for_backward(x, h)
@@ -177,8 +210,7 @@ class LinearConvFn(torch.autograd.Function):
         x, h = ctx.saved_tensors
         off = ctx.off
         four = x.ndim == 4
-        if g.stride(-1) != 1 or not (g.ndim == 4 or g.is_contiguous()):
-            g = g.contiguous()
+        g = _in_place(g)
         Cin, L = x.shape[-2], x.shape[-1]
         R = x.shape[0] * x.shape[1] if four else x.shape[0]
         Rh, Cf, N = h.shape
@@ -571,20 +603,15 @@ class DynamicsFn(torch.autograd.Function):
     def forward(ctx, x, log_threshold, log_ratio, log_knee, z_alpha, smoother, iir_len, knee, gate, u1=None):
         # u1: the smoother's un-truncated scan of this very input, kept by an earlier forward pass (the stage-wise
         # backward of render_grafx hands over what the inference render stored); None: produced / recomputed here
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
-        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
-        else:
-            if smoother and u1 is None:
-                u1 = torch.empty((rows, x.shape[-1]), dtype=torch.float32, device=x.device)
-                y = ops.dynamics_fused(x, log_threshold, log_ratio, log_knee if knee != "hard" else None, z_alpha,
-                                       smoother=1, iir_len=iir_len, knee=knee, gate=gate, u1_out=u1)
-            else:
-                y = ops.dynamics_fused(x, log_threshold, log_ratio, log_knee if knee != "hard" else None, z_alpha,
-                                       smoother=int(smoother), iir_len=iir_len, knee=knee, gate=gate)
+        x, four, rows = _signal(x)
+        y = _tape_only_output(x, rows)
+        if y is None and smoother and u1 is None:
+            u1 = torch.empty((rows, x.shape[-1]), dtype=torch.float32, device=x.device)
+            y = ops.dynamics_fused(x, log_threshold, log_ratio, log_knee if knee != "hard" else None, z_alpha,
+                                   smoother=1, iir_len=iir_len, knee=knee, gate=gate, u1_out=u1)
+        elif y is None:
+            y = ops.dynamics_fused(x, log_threshold, log_ratio, log_knee if knee != "hard" else None, z_alpha,
+                                   smoother=int(smoother), iir_len=iir_len, knee=knee, gate=gate)
         ctx.save_for_backward(x, log_threshold, log_ratio, log_knee, z_alpha)
         ctx.cfg = (smoother, iir_len, knee, gate)
         ctx.u1 = u1 if smoother else None
@@ -597,8 +624,7 @@ class DynamicsFn(torch.autograd.Function):
         src = _source_for(x, x.shape[0] * x.shape[1] if x.ndim == 4 else x.shape[0])
         if src is not None:     # the real gradient, in a layout only the row map expresses (see grad_source)
             gy = src
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
+        gy = _in_place(gy)
         lk = log_knee if knee != "hard" else None
         if smoother:  # two fused passes over the rows (forward, then backward in time) + the pole-gradient reduction
             sink = _sink_for(x)
@@ -624,13 +650,10 @@ def _waveshaper_forward(ctx, x, log_pre_gain, log_post_gain, p0, p1, mode, use_t
                         filters=None):
     """Forward of WaveshaperFn and, with ``factor`` and ``filters`` = (h_up, offset_up, h_dn, offset_dn), of
     OversampledWaveshaperFn."""
-    four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-    if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-        x = x.contiguous()
-    rows = x.shape[0] * x.shape[1] if four else x.shape[0]
+    x, four, rows = _signal(x)
     flags = dict(use_tanh=use_tanh, inverse_post_gain=inverse_post_gain, remove_dc=remove_dc)
-    if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-        y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
+    y = _tape_only_output(x, rows)
+    if y is not None:
         dc = ops.row_mean(x) if remove_dc else None
     elif filters is None:
         y, dc = ops.waveshaper(x, mode, log_pre_gain, log_post_gain, p0=p0, p1=p1, return_dc=True, **flags)
@@ -646,9 +669,7 @@ def _waveshaper_backward(ctx, gy):
     """Backward of the same two nodes -> the gradients of x and the four parameters."""
     x, log_pre_gain, log_post_gain, p0, p1, dc, *taps = ctx.saved_tensors
     mode, flags, oversampling = ctx.cfg
-    if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-        gy = gy.contiguous()
-    want = [name for name, need in zip(ops.WS_GRADS, ctx.needs_input_grad) if need]
+    gy, want = _in_place(gy), _wanted(ops.WS_GRADS, ctx)
     shaper = dict(flags, p0=p0, p1=p1, dc=dc, out=_sink_for(x) if "x" in want else None, want=want)
     if oversampling is None:
         gx, grads = ops.waveshaper_bwd(x, gy, mode, log_pre_gain, log_post_gain, **shaper)
@@ -656,9 +677,7 @@ def _waveshaper_backward(ctx, gy):
         (h_up, h_dn), (factor, offset_up, offset_dn) = taps, oversampling
         gx, grads = ops.oversampled_waveshaper_bwd(x, gy, mode, factor, h_up, offset_up, h_dn, offset_dn, log_pre_gain,
                                                    log_post_gain, **shaper)
-    like = lambda name, t: None if name not in grads else grads[name].reshape(t.shape)  # noqa: E731
-    return (None if gx is None else gx.view(x.shape), like("log_pre_gain", log_pre_gain), like("log_post_gain", log_post_gain),
-            like("p0", p0), like("p1", p1))
+    return _shaped_like(gx, x, (grads.get(name) for name in ops.WS_GRADS[1:]), (log_pre_gain, log_post_gain, p0, p1))
 
 
 class WaveshaperFn(torch.autograd.Function):
@@ -707,13 +726,9 @@ class LimiterFn(torch.autograd.Function):
     def forward(ctx, x, log_ceiling, taps, lookahead, hold, compensate):
         if taps.requires_grad:
             raise ValueError("LimiterFn: the taps get no gradient (detach them)")
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
-        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
-        else:
+        x, four, rows = _signal(x)
+        y = _tape_only_output(x, rows)
+        if y is None:
             y = ops.limiter(x, log_ceiling, taps, lookahead, hold, compensate)
         ctx.save_for_backward(x, log_ceiling, taps)
         ctx.cfg = (lookahead, hold, compensate)
@@ -723,12 +738,9 @@ class LimiterFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, log_ceiling, taps = ctx.saved_tensors
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
-        want = [name for name, need in zip(ops.LIMITER_GRADS, ctx.needs_input_grad) if need]
+        gy, want = _in_place(gy), _wanted(ops.LIMITER_GRADS, ctx)
         gx, gc = ops.limiter_bwd(x, gy, log_ceiling, taps, *ctx.cfg, out=_sink_for(x) if "x" in want else None, want=want)
-        return (None if gx is None else gx.view(x.shape), None if gc is None else gc.reshape(log_ceiling.shape), None, None,
-                None, None)
+        return (*_shaped_like(gx, x, (gc,), (log_ceiling,)), None, None, None, None)
 
 
 class ModulatedDelayFn(torch.autograd.Function):
@@ -739,13 +751,9 @@ class ModulatedDelayFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, delay, depth, rate, phase, gain, dry, max_delay, interp):
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
-        rows = x.shape[0] * x.shape[1] if four else x.shape[0]
-        if tape_only_active():  # the output of this node is the processor's output: its values are not read (see tape_only)
-            y = tape_placeholder((rows, x.shape[-2], x.shape[-1]), x.device)
-        else:
+        x, four, rows = _signal(x)
+        y = _tape_only_output(x, rows)
+        if y is None:
             y = ops.moddelay(x, delay, depth, rate, phase, gain, dry, max_delay, interp)
         ctx.save_for_backward(x, delay, depth, rate, phase, gain, dry)
         ctx.cfg = (max_delay, interp)
@@ -755,12 +763,9 @@ class ModulatedDelayFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, *params = ctx.saved_tensors
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
-        want = [name for name, need in zip(ops.MODDELAY_GRADS, ctx.needs_input_grad) if need]
+        gy, want = _in_place(gy), _wanted(ops.MODDELAY_GRADS, ctx)
         gx, *gp = ops.moddelay_bwd(x, gy, *params, *ctx.cfg, out=_sink_for(x) if "x" in want else None, want=want)
-        return (None if gx is None else gx.view(x.shape), *(None if g is None else g.reshape(p.shape) for g, p in zip(gp, params)),
-                None, None)
+        return (*_shaped_like(gx, x, gp, params), None, None)
 
 
 class FeedbackDelayFn(torch.autograd.Function):
@@ -772,9 +777,7 @@ class FeedbackDelayFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, delay, damping, feedback, dry, wet, max_delay):
-        four = x.ndim == 4  # a strided (B,n,C,L) view of the signal buffer is read in place
-        if x.stride(-1) != 1 or not (four or x.is_contiguous()):
-            x = x.contiguous()
+        x, four, _ = _signal(x)
         y, (q, w) = ops.fbdelay(x, delay, damping, feedback, dry, wet, max_delay, tape=True)   # (q and w are read: no tape_only)
         ctx.save_for_backward(x, delay, damping, feedback, dry, wet, q, w)
         ctx.max_delay = max_delay
@@ -784,12 +787,9 @@ class FeedbackDelayFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, *params, q, w = ctx.saved_tensors
-        if gy.stride(-1) != 1 or not (gy.ndim == 4 or gy.is_contiguous()):
-            gy = gy.contiguous()
-        want = [name for name, need in zip(ops.FBDELAY_GRADS, ctx.needs_input_grad) if need]
+        gy, want = _in_place(gy), _wanted(ops.FBDELAY_GRADS, ctx)
         gx, *gp = ops.fbdelay_bwd(x, gy, q, w, *params, ctx.max_delay, out=_sink_for(x) if "x" in want else None, want=want)
-        return (None if gx is None else gx.view(x.shape), *(None if g is None else g.reshape(p.shape) for g, p in zip(gp, params)),
-                None)
+        return (*_shaped_like(gx, x, gp, params), None)
 
 
 class StftReverbIrFn(torch.autograd.Function):
@@ -852,9 +852,9 @@ class NoiseShapingIrFn(torch.autograd.Function):
     def backward(ctx, gh):
         log_decay, log_gain, log_fade_in, z_fade_in_gain, noise, ir, gain = ctx.saved_tensors
         min_decay, max_decay, normalise = ctx.cfg
-        want = [name for name, need in zip(ops.NS_GRADS, ctx.needs_input_grad) if need]
         grads = ops.noise_shaping_ir_bwd(gh, noise, log_decay, log_gain, log_fade_in, z_fade_in_gain, min_decay, max_decay,
-                                         ir=ir if normalise else None, row_gain=gain if normalise else None, want=want)
+                                         ir=ir if normalise else None, row_gain=gain if normalise else None,
+                                         want=_wanted(ops.NS_GRADS, ctx))
         return (*(grads.get(name) for name in ops.NS_GRADS), None, None, None, None, None)
 
 
@@ -954,8 +954,7 @@ class BiquadCascadeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, Bs, As = ctx.saved_tensors
-        want = tuple(n for n, need in zip(("x", "Bs", "As"), ctx.needs_input_grad) if need)
-        gx, gB, gA, _ = ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, want=want)
+        gx, gB, gA, _ = ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, want=_wanted(ops.BIQUAD_GRADS, ctx))  # (no zi here)
         return gx, gB, gA
 
 
@@ -987,9 +986,8 @@ class BiquadCascadeStateFn(torch.autograd.Function):
         x, Bs, As, zi = ctx.saved_tensors
         if gy is None:
             gy = torch.zeros((*zi.shape[:2], x.shape[-1]), dtype=x.dtype, device=x.device)
-        want = tuple(n for n, need in zip(ops.BIQUAD_GRADS, ctx.needs_input_grad) if need)
         return ops.biquad_cascade_bwd(x, gy.contiguous(), Bs, As, zi=zi, gzf=None if gzf is None else gzf.contiguous(),
-                                      want=want)
+                                      want=_wanted(ops.BIQUAD_GRADS, ctx))
 
 
 def _loss_calls(hops, banked, tensors):

@@ -12,8 +12,9 @@ from collections import namedtuple
 import torch
 
 from ._lib import RowMap, check, lib
-from ._plumbing import (_apart, _expect, _int_in, _on_device, _output, _overlap, _Pin, _ptr, _require_gpu, _row_chunks,  # noqa: F401
-                        _state, _stream, _taps, _timed, _want, _workspace, profiling, rowmap)
+from ._plumbing import (_apart, _cotangent, _expect, _int_in, _on_device, _output, _overlap, _pair_state, _param_grads,  # noqa: F401
+                        _Pin, _ptr, _require_gpu, _row_chunks, _signal_grad, _state, _stream, _taps, _timed, _want, _workspace,
+                        profiling, rowmap)
 
 
 # The aliasing rule (include/grafx_amd.h): no tensor a call writes shares an element with one it reads, with another it
@@ -714,9 +715,7 @@ def dyn_gain_bwd(x, gy, env, log_threshold, log_ratio, log_knee, knee, gate):
     """-> (gain (R,L), denv (R,L), gparams (R,3) = d/d(log_threshold, log_ratio, log_knee)); see the header."""
     _require_gpu(x, gy, env)
     xmap, R, C, L = rowmap(x)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"dyn_gain_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gmap = _cotangent("dyn_gain_bwd", gy, x, (R, C, L))
     _expect(env, (R, L), "dyn_gain_bwd: env")
     env = env.contiguous()
     gain, denv = torch.empty_like(env), torch.empty_like(env)
@@ -740,9 +739,7 @@ def dynamics_bwd(x, gy, log_threshold, log_ratio, log_knee, z_alpha, iir_len, kn
     ``schedule`` (with ``u1``): "oneshot" (default, see DYN_SCHEDULE) or "rows"."""
     _require_gpu(x, gy, out)
     xmap, R, C, L = rowmap(x)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"dynamics_bwd: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gmap = _cotangent("dynamics_bwd", gy, x, (R, C, L))
     kept = u1 is not None
     if kept:
         _require_gpu(u1)
@@ -784,13 +781,12 @@ def onepole_dz(g, U, D, coef, N):
 def dyn_dx(x, gy, gain, de):
     _require_gpu(x, gy, gain, de)
     xmap, R, C, L = rowmap(x)
-    if rowmap(gy)[1:] != (R, C, L):
-        raise ValueError(f"dyn_dx: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gmap = _cotangent("dyn_dx", gy, x, (R, C, L))
     _expect(gain, (R, L), "dyn_dx: gain")
     _expect(de, (R, L), "dyn_dx: de")
     gx = torch.empty((R, C, L), dtype=torch.float32, device=x.device)
     pin = _Pin()
-    check(lib().gfx_dyn_dx_f32(_ptr(x), xmap, _ptr(gy), rowmap(gy)[0], pin(gain), pin(de),
+    check(lib().gfx_dyn_dx_f32(_ptr(x), xmap, _ptr(gy), gmap, pin(gain), pin(de),
                                _ptr(gx), R, C, L, _stream()), "gfx_dyn_dx_f32")
     return gx
 
@@ -1080,11 +1076,7 @@ def biquad_cascade_bwd(x, gy, Bs, As, zi=None, gzf=None, want=BIQUAD_GRADS, out=
     zi = _state(zi, (R, Cout, K, 2), what, "zi")
     gzf = _state(gzf, (R, Cout, K, 2), what, "gzf")
     reads = (x, gy, Bs, As, zi, gzf)
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, Cin, L), x.device, what, apart=(*reads, ws))
-        if "x" in want:
-            gx, gxmap = dest
+    gx, gxmap = _signal_grad(what, want, out, (R, Cin, L), xmap, x.device, (*reads, ws))
     # More than two channels with a broadcast side: the kernel sums a broadcast inside a pair of row-channels, which is a
     # row's channels only when there are two.  The broadcast side goes in expanded instead -- the coefficients copied
     # (parameter-sized), x through a row map with a zero channel stride -- and the channels of the result are added here.
@@ -1266,15 +1258,9 @@ def _shape_bwd(what, x, gy, mode, log_pre_gain, log_post_gain, p0, p1, use_tanh,
         kernel, factor = "oversampled_waveshaper_bwd_kernel", oversampling[:1]
         taps, extra = _oversampling_args(what, *oversampling)
     xmap, R, C, L = rowmap(x)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gmap = _cotangent(what, gy, x, (R, C, L))
     _want(what, want, WS_GRADS)
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, what, apart=(x, gy, dc, *taps))
-        if "x" in want:
-            gx, gxmap = dest
+    gx, gxmap = _signal_grad(what, want, out, (R, C, L), xmap, x.device, (x, gy, dc, *taps))
     params, K, dc = _waveshaper_args(what, x, R, C, mode, log_pre_gain, log_post_gain, p0, p1, remove_dc, dc)
     grads = {k: torch.empty_like(v) for k, v in params.items() if k in want and v is not None}
     pin = _Pin()
@@ -1429,18 +1415,10 @@ def limiter_bwd(x, gy, log_ceiling, h, lookahead, hold=0, compensate=False, out=
     what = "limiter_bwd"
     _require_gpu(x, gy, log_ceiling, out)
     xmap, R, C, L, log_ceiling, sigma, _ = _limiter_args(what, x, log_ceiling, h, lookahead, hold, compensate)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
-    _want(what, want, LIMITER_GRADS)
-    if not want:
-        raise ValueError(f"{what}: no gradient asked for")
+    gmap = _cotangent(what, gy, x, (R, C, L))
+    _want(what, want, LIMITER_GRADS, some=True)
     reads = (x, gy, h)
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
-        if "x" in want:
-            gx, gxmap = dest
+    gx, gxmap = _signal_grad(what, want, out, (R, C, L), xmap, x.device, (*reads, ws))
     gc = torch.empty(R, dtype=torch.float32, device=x.device) if "log_ceiling" in want else None
     pin = _Pin()
     wsarg = (0, 0)
@@ -1520,14 +1498,7 @@ def moddelay(x, delay, depth, rate, phase, gain, dry, max_delay, interp="cubic",
     _require_gpu(x, delay, depth, rate, phase, gain, dry, out)
     xmap, R, C, L, V, mode, params = _moddelay_args(what, x, delay, depth, rate, phase, gain, dry, max_delay, interp)
     S = max_delay + 2
-    zi = pos = None
-    if state is not None:
-        if not isinstance(state, (tuple, list)) or len(state) != 2:
-            raise ValueError(f"{what}: state must be the pair (history, position)")
-        zi = _state(state[0], (R, C, S), what, "the state's history")
-        pos = _moddelay_position(state[1], R, x.device, what)
-        if zi is None:
-            raise ValueError(f"{what}: state must be the pair (history, position)")
+    zi, pos = _pair_state(what, state, (R, C, S), "position", lambda pos: _moddelay_position(pos, R, x.device, what))
     stateful = state is not None or return_state
     out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, zi, pos, *params))
     zf = torch.empty((R, C, S), dtype=torch.float32, device=x.device) if stateful else None
@@ -1553,20 +1524,12 @@ def moddelay_bwd(x, gy, delay, depth, rate, phase, gain, dry, max_delay, interp=
     what = "moddelay_bwd"
     _require_gpu(x, gy, delay, depth, rate, phase, gain, dry, out)
     xmap, R, C, L, V, mode, params = _moddelay_args(what, x, delay, depth, rate, phase, gain, dry, max_delay, interp)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
-    _want(what, want, MODDELAY_GRADS)
-    if not want:
-        raise ValueError(f"{what}: no gradient asked for")
+    gmap = _cotangent(what, gy, x, (R, C, L))
+    _want(what, want, MODDELAY_GRADS, some=True)
     reads = (x, gy, *params)
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
-        if "x" in want:
-            gx, gxmap = dest
+    gx, gxmap = _signal_grad(what, want, out, (R, C, L), xmap, x.device, (*reads, ws))
     shapes = {"delay": (R, V), "depth": (R, V), "rate": (R, V), "phase": (R, V, C), "gain": (R, V, C), "dry": (R,)}
-    grads = [torch.empty(shape, dtype=torch.float32, device=x.device) if name in want else None for name, shape in shapes.items()]
+    grads = _param_grads(want, shapes, x.device)
     pin = _Pin()
     wsarg = (0, 0)
     if any(g is not None for g in grads):
@@ -1625,14 +1588,7 @@ def fbdelay(x, delay, damping, feedback, dry, wet, max_delay, out=None, state=No
     _require_gpu(x, delay, damping, feedback, dry, wet, out)
     xmap, R, C, L, params = _fbdelay_args(what, x, delay, damping, feedback, dry, wet, max_delay)
     S = max_delay + 1
-    zi = q_in = None
-    if state is not None:
-        if not isinstance(state, (tuple, list)) or len(state) != 2:
-            raise ValueError(f"{what}: state must be the pair (history, q_last)")
-        zi = _state(state[0], (R, C, S), what, "the state's history")
-        q_in = _state(state[1], (R, C), what, "the state's q_last")
-        if zi is None or q_in is None:
-            raise ValueError(f"{what}: state must be the pair (history, q_last)")
+    zi, q_in = _pair_state(what, state, (R, C, S), "q_last", lambda q: _state(q, (R, C), what, "the state's q_last"))
     stateful = state is not None or return_state
     out, ymap = _output(out, (R, C, L), x.device, what, apart=(x, zi, q_in, *params))
     zf = torch.empty((R, C, S), dtype=torch.float32, device=x.device) if stateful else None
@@ -1662,24 +1618,16 @@ def fbdelay_bwd(x, gy, q, w, delay, damping, feedback, dry, wet, max_delay, out=
     what = "fbdelay_bwd"
     _require_gpu(x, gy, q, w, delay, damping, feedback, dry, wet, out)
     xmap, R, C, L, params = _fbdelay_args(what, x, delay, damping, feedback, dry, wet, max_delay)
-    gmap, Rg, Cg, Lg = rowmap(gy)
-    if (Rg, Cg, Lg) != (R, C, L):
-        raise ValueError(f"{what}: gradient {tuple(gy.shape)} does not match the input {tuple(x.shape)}")
+    gmap = _cotangent(what, gy, x, (R, C, L))
     q = _state(q, (R, C, L), what, "q")
     w = _state(w, (R, C, L), what, "w")
     if q is None or w is None:
         raise ValueError(f"{what}: q and w, the signals of fbdelay(tape=True), are needed")
-    _want(what, want, FBDELAY_GRADS)
-    if not want:
-        raise ValueError(f"{what}: no gradient asked for")
+    _want(what, want, FBDELAY_GRADS, some=True)
     reads = (x, gy, q, w, *params)
-    gx, gxmap = None, xmap                       # without "x" the entry writes no signal gradient (and takes any row map)
-    if "x" in want or out is not None:           # a given ``out`` is checked whether or not it is used
-        dest = _output(out, (R, C, L), x.device, what, apart=(*reads, ws))
-        if "x" in want:
-            gx, gxmap = dest
+    gx, gxmap = _signal_grad(what, want, out, (R, C, L), xmap, x.device, (*reads, ws))
     shapes = {"delay": (R, C), "damping": (R, C), "feedback": (R, C, C), "dry": (R,), "wet": (R,)}
-    grads = [torch.empty(shape, dtype=torch.float32, device=x.device) if name in want else None for name, shape in shapes.items()]
+    grads = _param_grads(want, shapes, x.device)
     pin = _Pin()
     wsarg = _workspace(what, ws, lib().gfx_fbdelay_bwd_ws_bytes(R, C, L), x.device, pin, reads, align=8)
     with _timed("fbdelay_bwd_kernel", 24 * R * C * L):

@@ -19,6 +19,9 @@ asks every stage before it launches the first.
 shapes, the carry that means "nothing came before": what a first block's None stands for, materialised, so that a stream
 can start on the kernels every later block runs (render.silent_state, render.CapturedStream)."""
 import torch
+import torch.nn.functional as F
+
+from ...autograd import needs_grad
 
 
 class Prepared:
@@ -89,6 +92,37 @@ class BufferIO(StreamIO):
         y = self.forward(x4.reshape(-1, *x4.shape[2:]), **params)
         out4.copy_(y.view(out4.shape))
         return out4
+
+
+class FusedIO(BufferIO):
+    """A module on one fused op whose ``forward`` takes the strided views themselves and a destination ``_out``: the op
+    writes the buffer in place.  Under grad the autograd node makes its own output, and the rows are written from it."""
+
+    def render_into(self, x4, out4, **params):
+        if needs_grad(x4, *params.values()):
+            return write_rows(out4, self.forward(x4, **params))
+        return self.forward(x4, _out=out4, **params)
+
+
+class FusedStateIO(FusedIO):
+    """A FusedIO module with memory in every configuration: the carry is the state of ``forward(state=)``."""
+
+    def stream_block(self, x4, out4, carry, **params):
+        return self.forward(x4, _out=out4, state=carry, return_state=True, **params)[1]
+
+
+def history_after(x, S):
+    """The input history a first block leaves: the last ``S`` samples of ``x`` behind zeros -> contiguous (R, C, S), off
+    the tape."""
+    C, L = x.shape[-2:]
+    xr = x.detach().reshape(-1, C, L)
+    return F.pad(xr[..., max(0, L - S):], (max(0, S - L), 0)).contiguous()
+
+
+def refuse_state_under_grad(name, state):
+    """The fused ops' backward entries start from silence: a block that enters with a state cannot be trained through."""
+    if state is not None:
+        raise ValueError(f"{name}: a block that enters with a state has no native backward; train on whole signals")
 
 
 def shared_reps(x, shared_rows):

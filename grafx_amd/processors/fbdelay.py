@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..autograd import FeedbackDelayFn, needs_grad
-from .core._buffer_io import BufferIO, write_rows
+from .core._buffer_io import FusedStateIO, refuse_state_under_grad, write_rows
 
 
 def _onepole_matrix(a, K):
@@ -70,7 +70,7 @@ def fbdelay_torch(x, delay, damping, feedback, dry, wet, max_delay, state=None, 
     return y.reshape(shape), (after, q_last.detach().contiguous())
 
 
-class FeedbackDelay(BufferIO, nn.Module):
+class FeedbackDelay(FusedStateIO, nn.Module):
     """A delay of ``min_delay`` .. ``max_delay`` samples per channel (64 <= min_delay < max_delay <= 65536) inside a
     feedback loop of gain up to ``max_feedback`` with a one-pole low-pass of coefficient up to ``max_damping``;
     ``processor_channel``: "mono" (C = 1) or "stereo" (C = 2: each channel its own delay and damping, and ``z_cross``
@@ -153,9 +153,7 @@ class FeedbackDelay(BufferIO, nn.Module):
                              f"{self.processor_channel!r}")
         z = self._z(z_delay, z_feedback, z_cross, z_damping, log_wet, log_dry)
         if needs_grad(input_signals, *z):
-            if state is not None:
-                raise ValueError("FeedbackDelay: a block that enters with a state has no native backward; train on whole "
-                                 "signals")
+            refuse_state_under_grad("FeedbackDelay", state)
             params = self.physical(*z)
             y = FeedbackDelayFn.apply(input_signals, *params, self.max_delay)
             y = y if _out is None else write_rows(_out, y)
@@ -175,12 +173,3 @@ class FeedbackDelay(BufferIO, nn.Module):
         params = self.physical(*self._z(z_delay, z_feedback, z_cross, z_damping, log_wet, log_dry))
         y, after = fbdelay_torch(input_signals, *params, self.max_delay, state, chunk=ops.FBDELAY_CHUNK)
         return (y, after) if return_state or state is not None else y
-
-    def render_into(self, x4, out4, **params):
-        if needs_grad(x4, *params.values()):
-            return write_rows(out4, self.forward(x4, **params))
-        return self.forward(x4, _out=out4, **params)
-
-    def stream_block(self, x4, out4, carry, **params):
-        """The carry is the state of forward(state=): the pair (the line's last samples, the loop filter's last value)."""
-        return self.forward(x4, _out=out4, state=carry, return_state=True, **params)[1]

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..autograd import LimiterFn, needs_grad
-from .core._buffer_io import BufferIO, write_rows
+from .core._buffer_io import FusedIO, history_after, refuse_state_under_grad, write_rows
 
 
 def limiter_window(lookahead):
@@ -34,7 +34,7 @@ def limiter_window(lookahead):
     return w / w.sum()
 
 
-class Limiter(BufferIO, nn.Module):
+class Limiter(FusedIO, nn.Module):
     """``lookahead`` = D >= 0 and ``hold`` = H >= 0 samples with D + 1 + H <= 4096; ``window``: 1 .. min(D + 1, 1024)
     non-negative taps that sum to one within 1e-6 (None: ``limiter_window(lookahead)``), kept as a float32 buffer;
     ``compensate_delay``: the output is aligned with the input (x taken as zero beyond its end) instead of D samples
@@ -92,8 +92,7 @@ class Limiter(BufferIO, nn.Module):
             if self.state_samples == 0 and state is not None:
                 raise ValueError("Limiter: lookahead = hold = 0 has no memory: there is no state to carry")
         if needs_grad(input_signals, log_ceiling):
-            if state is not None:
-                raise ValueError("Limiter: a block that enters with a state has no native backward; train on whole signals")
+            refuse_state_under_grad("Limiter", state)
             y = LimiterFn.apply(input_signals, log_ceiling, self.window, *cfg)
             y = y if _out is None else write_rows(_out, y)
             return (y, self._state_after(input_signals)) if return_state else y
@@ -104,11 +103,7 @@ class Limiter(BufferIO, nn.Module):
 
     def _state_after(self, x):
         """The state a first block leaves: its last samples behind zeros."""
-        S, (C, L) = self.state_samples, x.shape[-2:]
-        if S == 0:
-            return None
-        xr = x.detach().reshape(-1, C, L)
-        return F.pad(xr[..., max(0, L - S):], (max(0, S - L), 0)).contiguous()
+        return history_after(x, self.state_samples) if self.state_samples else None
 
     def torch_forward(self, input_signals, log_ceiling, state=None, return_state=False):
         """forward() as torch ops."""
@@ -133,11 +128,6 @@ class Limiter(BufferIO, nn.Module):
         if return_state:
             return y, (xx[..., L:L + S].contiguous() if S else None)
         return y
-
-    def render_into(self, x4, out4, **params):
-        if needs_grad(x4, *params.values()):
-            return write_rows(out4, self.forward(x4, **params))
-        return self.forward(x4, _out=out4, **params)
 
     def stream_block(self, x4, out4, carry, **params):
         """The carry is the state of forward(state=): the input's last samples; None for a module without memory."""

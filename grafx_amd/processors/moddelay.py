@@ -16,11 +16,10 @@ import math
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
 from ..autograd import ModulatedDelayFn, needs_grad
-from .core._buffer_io import BufferIO, write_rows
+from .core._buffer_io import FusedStateIO, history_after, refuse_state_under_grad, write_rows
 
 # the part of the kernel's slope contract 2 pi rate depth <= 1/2 that the mapping uses: float32 rounding stays inside it
 _SLOPE = 0.45
@@ -61,7 +60,7 @@ def moddelay_torch(x, delay, depth, rate, phase, gain, dry, max_delay, interp="c
     return y.reshape(shape), (xx[..., L:L + S].detach().contiguous(), pos + L)
 
 
-class ModulatedDelay(BufferIO, nn.Module):
+class ModulatedDelay(FusedStateIO, nn.Module):
     """``num_voices`` = V (1 .. 8) delay taps per channel, each swinging under its own sine oscillator between
     ``min_delay`` and ``max_delay`` samples (max_delay <= 8192) at up to ``max_rate`` Hz; ``interpolation``: "linear" or
     "cubic"; ``processor_channel``: "mono" (C = 1) or "stereo" (C = 2, every voice with its own phase and gain per channel).
@@ -136,9 +135,7 @@ class ModulatedDelay(BufferIO, nn.Module):
         z = (z_delay, z_depth, z_rate, phase, log_gain, log_dry)
         cfg = (self.max_delay, self.interpolation)
         if needs_grad(input_signals, *z):
-            if state is not None:
-                raise ValueError("ModulatedDelay: a block that enters with a state has no native backward; train on whole "
-                                 "signals")
+            refuse_state_under_grad("ModulatedDelay", state)
             y = ModulatedDelayFn.apply(input_signals, *self.physical(*z), *cfg)
             y = y if _out is None else write_rows(_out, y)
             return (y, self._state_after(input_signals)) if return_state else y
@@ -150,22 +147,11 @@ class ModulatedDelay(BufferIO, nn.Module):
 
     def _state_after(self, x):
         """The state a first block leaves: its last samples behind zeros, and its length."""
-        S, (C, L) = self.state_samples, x.shape[-2:]
-        xr = x.detach().reshape(-1, C, L)
-        history = F.pad(xr[..., max(0, L - S):], (max(0, S - L), 0)).contiguous()
-        return history, torch.full((xr.shape[0],), L, dtype=torch.int64, device=x.device)
+        history = history_after(x, self.state_samples)
+        return history, torch.full((history.shape[0],), x.shape[-1], dtype=torch.int64, device=x.device)
 
     def torch_forward(self, input_signals, z_delay, z_depth, z_rate, phase, log_gain, log_dry, state=None, return_state=False):
         """forward() as torch ops: the same definition on any device and dtype, the delay evaluated in float64."""
         params = self.physical(z_delay, z_depth, z_rate, phase, log_gain, log_dry)
         y, after = moddelay_torch(input_signals, *params, self.max_delay, self.interpolation, state)
         return (y, after) if return_state or state is not None else y
-
-    def render_into(self, x4, out4, **params):
-        if needs_grad(x4, *params.values()):
-            return write_rows(out4, self.forward(x4, **params))
-        return self.forward(x4, _out=out4, **params)
-
-    def stream_block(self, x4, out4, carry, **params):
-        """The carry is the state of forward(state=): the pair (the input's last samples, the samples rendered so far)."""
-        return self.forward(x4, _out=out4, state=carry, return_state=True, **params)[1]

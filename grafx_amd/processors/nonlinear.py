@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..autograd import OversampledWaveshaperFn, WaveshaperFn, needs_grad
 from ..resample import sinc_kernel
-from .core._buffer_io import BufferIO, write_rows
+from .core._buffer_io import FusedIO
 
 
 def _center(x, remove_dc):
@@ -52,7 +52,7 @@ def _decimate(v, h, factor, offset):
     return F.conv1d(padded, h.flip(0).view(1, 1, N), stride=factor)[..., :L].reshape(*v.shape[:-1], L)
 
 
-class _Waveshaper(BufferIO, nn.Module):
+class _Waveshaper(FusedIO, nn.Module):
     accepts_strided_rows = True   # forward() also takes a strided (B, n, C, L) view (under grad it then returns (B, n, C, L))
 
     def _set_oversample(self, oversample):
@@ -93,11 +93,6 @@ class _Waveshaper(BufferIO, nn.Module):
         if self.remove_dc:
             raise ValueError(f"{type(self).__name__}: remove_dc=True subtracts the mean of the whole signal, which a block "
                              "does not know; a chain of blocks is not a stream")
-
-    def render_into(self, x4, out4, **params):
-        if needs_grad(x4, *params.values()):
-            return write_rows(out4, self.forward(x4, **params))
-        return self.forward(x4, _out=out4, **params)
 
 
 class TanhDistortion(_Waveshaper):

@@ -51,22 +51,16 @@ def test_workspace_is_a_small_part_of_one_signal_tensor_at_the_training_shape():
 
 
 def test_entry_refuses_inconsistent_arguments_before_any_launch():
-    """Every check of the entry comes before its first launch, so the refusals need no GPU: the pointers below are never
-    followed.  (The consistent call is made on the GPU, tests/test_gpu_biquad_bwd.py.)  Where a GPU is visible the pointer
-    is a real 16 MB device buffer instead, larger than anything these shapes index: should a check ever slip behind a
-    launch there, the test fails on the return code and no kernel has been sent to an address nobody owns."""
-    import torch
+    """Every check of the entry comes before its first launch, so the refusals need no GPU (abi_checks.device_pointer).
+    (The consistent call is made on the GPU, tests/test_gpu_biquad_bwd.py.)"""
+    from abi_checks import device_pointer, refused
 
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, Cin, Cf, K, L = 3, 2, 1, 3, 1000
     need = lib.gfx_biquad_cascade_bwd_ws_bytes(R, 2, K, L)
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x1000      # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     rm = _lib.RowMap(R, 0, 2 * L, L)
     good = dict(x=p, xmap=rm, g=p, gmap=rm, gx=p, gxmap=rm, Bs=p, As=p, zi=p, gzf=p, gB=p, gA=p, gzi=p, ws=p, ws_bytes=need,
                 R=R, C_in=Cin, C_f=Cf, K=K, L=L, stream=None)
@@ -87,5 +81,4 @@ def test_entry_refuses_inconsistent_arguments_before_any_launch():
         "a shared input over four channels, its gradient asked": dict(C_in=1, C_f=4, ws_bytes=1 << 20),
         "an empty row map": dict(xmap=_lib.RowMap(0, 0, 2 * L, L)),
     }
-    for what, change in bad.items():
-        assert lib.gfx_biquad_cascade_bwd_f32(*{**good, **change}.values()) == -1, what   # GFX_EINVAL
+    refused(lib.gfx_biquad_cascade_bwd_f32, good, bad)

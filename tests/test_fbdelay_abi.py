@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import fbdelay_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ENTRIES = ("gfx_fbdelay_ws_bytes", "gfx_fbdelay_f32", "gfx_fbdelay_bwd_ws_bytes", "gfx_fbdelay_bwd_f32")
 # R, C, Dmax, L of the small float64 checks: the loop goes round several times
@@ -16,24 +17,12 @@ SMALL = ((4, 2, 128, 420), (3, 1, 100, 400), (4, 2, 77, 300))
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib
-
-    protos = header_prototypes()
     cf, f = "const float*", "float*"
     fwd = [cf, "gfx_rowmap_t", f, "gfx_rowmap_t"] + ["int64_t"] * 4 + [cf] * 5 + [cf, cf, f, f, f, "void*", "size_t", "void*"]
     bwd = ([cf, "gfx_rowmap_t", cf, "gfx_rowmap_t", cf, cf] + ["int64_t"] * 4 + [cf] * 5 + [f, "gfx_rowmap_t"] + [f] * 5
            + ["void*", "size_t", "void*"])
-    want = dict(zip(ENTRIES, (("size_t", ["int64_t"] * 3), ("int", fwd), ("size_t", ["int64_t"] * 3), ("int", bwd))))
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        assert protos[name] == want[name], name
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES, dict(zip(ENTRIES, (("size_t", ["int64_t"] * 3), ("int", fwd), ("size_t", ["int64_t"] * 3),
+                                              ("int", bwd)))))
 
 
 def test_constants_and_workspace_queries():
@@ -51,19 +40,14 @@ def test_constants_and_workspace_queries():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check comes before the first launch, so the refusals need no GPU: the device pointers below are never
-    followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than these shapes index."""
+    """Every check comes before the first launch, so the refusals need no GPU (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, C, L, Dmax = 3, 2, 5000, 441
     S = Dmax + 1
     need, need_bwd = lib.gfx_fbdelay_ws_bytes(R, C, L), lib.gfx_fbdelay_bwd_ws_bytes(R, C, L)
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x100000     # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     sig = 4 * R * C * L
     far, third, qs, wsig, wsp = (p + k * sig for k in range(1, 6))            # signals that do not overlap, then the workspace
     z0 = wsp + need_bwd + 64
@@ -96,12 +80,10 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                 "no w": dict(w=None), "nothing asked for": dict(gx=None, **{"g_" + name: None for name in five}),
                 "gx is x": dict(gx=p), "gx is gy": dict(gx=far), "gx overlaps x a sample later": dict(gx=p + 4),
                 "an empty gx row map": dict(gxmap=empty), "a workspace that is not 8-byte aligned": dict(ws=wsp + 4)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_fbdelay_f32(*{**fwd, **change}.values()) == -1, what             # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_fbdelay_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    assert lib.gfx_fbdelay_f32(*{**fwd, "ws_bytes": need - 1}.values()) == -2           # GFX_ENOSPC
-    assert lib.gfx_fbdelay_bwd_f32(*{**bwd, "ws_bytes": need_bwd - 1}.values()) == -2
+    refused(lib.gfx_fbdelay_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_fbdelay_bwd_f32, bwd, {**bad, **only_bwd})
+    refused(lib.gfx_fbdelay_f32, fwd, {"a workspace one byte short": dict(ws_bytes=need - 1)}, code=-2)
+    refused(lib.gfx_fbdelay_bwd_f32, bwd, {"a workspace one byte short": dict(ws_bytes=need_bwd - 1)}, code=-2)
 
 
 def test_constructor_and_parameter_size():

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import limiter_float64 as l64
+from abi_checks import device_pointer, entries_match, refused
 
 ENTRIES = ("gfx_limiter_f32", "gfx_limiter_bwd_ws_bytes", "gfx_limiter_bwd_f32")
 # D, H, N of the small float64 checks
@@ -15,25 +16,12 @@ SMALL = ((4, 3, 4), (0, 0, 1), (7, 0, 3), (5, 9, 6))
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib
-
-    protos = header_prototypes()
     fwd = ["const float*", "gfx_rowmap_t", "float*", "gfx_rowmap_t", "int64_t", "int64_t", "int64_t", "const float*",
            "const float*", "int64_t", "int64_t", "int64_t", "int64_t", "const float*", "float*", "float*", "void*"]
     bwd = ["const float*", "gfx_rowmap_t", "const float*", "gfx_rowmap_t", "int64_t", "int64_t", "int64_t", "const float*",
            "const float*", "int64_t", "int64_t", "int64_t", "int64_t", "float*", "gfx_rowmap_t", "float*", "void*", "size_t",
            "void*"]
-    want = dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 4), ("int", bwd))))
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        assert protos[name] == want[name], name
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES, dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 4), ("int", bwd)))))
 
 
 def test_tile_and_workspace_query():
@@ -56,19 +44,14 @@ def test_tile_and_workspace_query():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check comes before the first launch, so the refusals need no GPU: the device pointers below are never
-    followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than these shapes index."""
+    """Every check comes before the first launch, so the refusals need no GPU (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, C, L, D, H, N = 3, 2, 2000, 63, 100, 64
     S = D + H + N - 1
     need = lib.gfx_limiter_bwd_ws_bytes(R, L, D, H)
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x100000     # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     far = p + 4 * R * C * L      # a second signal that does not overlap the first, then a third, then two states
     third = far + 4 * R * C * L
     z0, z1 = third + 4 * R * C * L, third + 4 * R * C * L + 4 * R * C * S
@@ -95,11 +78,9 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                 "nothing asked for": dict(gx=None, g_log_ceiling=None), "gx is x": dict(gx=p), "gx is gy": dict(gx=far),
                 "gx overlaps x a sample later": dict(gx=p + 4), "an empty gx row map": dict(omap=empty),
                 "a ceiling gradient without a workspace": dict(ws=None), "a workspace that is not 8-byte aligned": dict(ws=p + 4)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_limiter_f32(*{**fwd, **change}.values()) == -1, what            # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_limiter_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    assert lib.gfx_limiter_bwd_f32(*{**bwd, "ws_bytes": need - 1}.values()) == -2      # GFX_ENOSPC
+    refused(lib.gfx_limiter_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_limiter_bwd_f32, bwd, {**bad, **only_bwd})
+    refused(lib.gfx_limiter_bwd_f32, bwd, {"a workspace one byte short": dict(ws_bytes=need - 1)}, code=-2)
 
 
 def _case(D, H, N, seed, R=2, C=2, L=60):

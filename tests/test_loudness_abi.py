@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import loudness_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gfx_kweight_energy_ws_bytes", "gfx_kweight_energy_f32", "gfx_kweight_energy_bwd_f32")
@@ -17,20 +18,9 @@ TABLE_A = ((1.0, -1.69065929318241, 0.73248077421585), (1.0, -1.99004745483398, 
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib
-
     header = open(os.path.join(ROOT, "include", "grafx_amd.h")).read()
     assert "gfx_kweight_energy_ws_bytes = R * C * ceil(L / 1024) * 64 bytes" in header
-    protos = header_prototypes()
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES)
 
 
 def test_workspace_query_returns_the_documented_size():
@@ -45,9 +35,8 @@ def test_workspace_query_returns_the_documented_size():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check of the two entries comes before their first launch, so the refusals need no GPU: the device pointers
-    below are never followed (the coefficients are host memory and are read).  Where a GPU is visible the pointer is a real
-    16 MB device buffer instead, larger than anything these shapes index."""
+    """Every check of the two entries comes before their first launch, so the refusals need no GPU
+    (abi_checks.device_pointer; the coefficients are host memory and are read)."""
     import ctypes
 
     from grafx_amd import _lib
@@ -56,11 +45,7 @@ def test_entries_refuse_bad_arguments_before_any_launch():
     R, C, L, hop = 3, 2, 2000, 100
     need = lib.gfx_kweight_energy_ws_bytes(R, C, L)
     assert need == R * C * 2 * 64
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x1000      # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
 
     def doubles(values):
         return (ctypes.c_double * 10)(*values)
@@ -91,13 +76,11 @@ def test_entries_refuse_bad_arguments_before_any_launch():
     only_fwd = {"no energies": dict(energy=None), "energies off the 8-byte grid": dict(energy=p + 4)}
     only_bwd = {"no cotangent": dict(genergy=None), "no gradient": dict(gx=None), "an empty gradient row map": dict(gmap=empty),
                 "a cotangent off the 8-byte grid": dict(genergy=p + 4)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_kweight_energy_f32(*{**fwd, **change}.values()) == -1, what        # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_kweight_energy_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    # a workspace one byte short
-    assert lib.gfx_kweight_energy_f32(*{**fwd, "ws_bytes": need - 1}.values()) == -2        # GFX_ENOSPC
-    assert lib.gfx_kweight_energy_bwd_f32(*{**bwd, "ws_bytes": need - 1}.values()) == -2
+    refused(lib.gfx_kweight_energy_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_kweight_energy_bwd_f32, bwd, {**bad, **only_bwd})
+    short = {"a workspace one byte short": dict(ws_bytes=need - 1)}
+    refused(lib.gfx_kweight_energy_f32, fwd, short, code=-2)
+    refused(lib.gfx_kweight_energy_bwd_f32, bwd, short, code=-2)
 
 
 def test_k_weighting_is_the_table_of_the_standard_at_48_khz():

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import moddelay_float64 as m64
+from abi_checks import device_pointer, entries_match, refused
 
 ENTRIES = ("gfx_moddelay_f32", "gfx_moddelay_bwd_ws_bytes", "gfx_moddelay_bwd_f32")
 # V, Dmax, interp of the small float64 checks
@@ -18,24 +19,11 @@ SMALL = ((1, 2, "linear"), (2, 8, "cubic"), (3, 21, "cubic"), (2, 13, "linear"))
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib
-
-    protos = header_prototypes()
     cf, f = "const float*", "float*"
     head = [cf, "gfx_rowmap_t", "{second}", "gfx_rowmap_t"] + ["int64_t"] * 6 + [cf] * 6
     fwd = [t.format(second=f) for t in head] + [cf, "const int64_t*", f, "int64_t*", "void*"]
     bwd = [t.format(second=cf) for t in head] + [f, "gfx_rowmap_t"] + [f] * 6 + ["void*", "size_t", "void*"]
-    want = dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 4), ("int", bwd))))
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        assert protos[name] == want[name], name
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES, dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 4), ("int", bwd)))))
 
 
 def test_tile_and_workspace_query():
@@ -58,19 +46,14 @@ def test_tile_and_workspace_query():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check comes before the first launch, so the refusals need no GPU: the device pointers below are never
-    followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than these shapes index."""
+    """Every check comes before the first launch, so the refusals need no GPU (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, C, L, V, Dmax = 3, 2, 5000, 2, 441
     S = Dmax + 2
     need = lib.gfx_moddelay_bwd_ws_bytes(R, C, L, V)
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x100000     # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     far = p + 4 * R * C * L      # a second signal that does not overlap the first, then a third, then two states
     third = far + 4 * R * C * L
     z0 = third + 4 * R * C * L
@@ -103,11 +86,9 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                 "nothing asked for": dict(gx=None, **{"g_" + name: None for name in six}), "gx is x": dict(gx=p),
                 "gx is gy": dict(gx=far), "gx overlaps x a sample later": dict(gx=p + 4), "an empty gx row map": dict(gxmap=empty),
                 "a parameter gradient without a workspace": dict(ws=None), "a workspace that is not 8-byte aligned": dict(ws=p + 4)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_moddelay_f32(*{**fwd, **change}.values()) == -1, what            # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_moddelay_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    assert lib.gfx_moddelay_bwd_f32(*{**bwd, "ws_bytes": need - 1}.values()) == -2      # GFX_ENOSPC
+    refused(lib.gfx_moddelay_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_moddelay_bwd_f32, bwd, {**bad, **only_bwd})
+    refused(lib.gfx_moddelay_bwd_f32, bwd, {"a workspace one byte short": dict(ws_bytes=need - 1)}, code=-2)
 
 
 def test_constructor_and_parameter_size():

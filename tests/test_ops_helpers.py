@@ -4,8 +4,8 @@ import pytest
 import torch
 
 from grafx_amd import ops
-from grafx_amd.ops import (_apart, _int_in, _output, _Pin, _read_mix, _row_chunks, _state, _taps, _want, _workspace,
-                           rowmap)
+from grafx_amd.ops import (_apart, _cotangent, _int_in, _output, _pair_state, _param_grads, _Pin, _read_mix, _row_chunks,
+                           _signal_grad, _state, _taps, _want, _workspace, rowmap)
 
 SHAPE = (2, 2, 64)
 CPU = torch.device("cpu")
@@ -158,6 +158,77 @@ def test_want():
     _want("t", ["p0", "x"], ("x", "p0"))
     with pytest.raises(ValueError, match=r"t: unknown gradients \['h_up'\] \(known: \('x', 'p0'\)\)"):
         _want("t", ("x", "h_up"), ("x", "p0"))
+    _want("t", ["p0"], ("x", "p0"), some=True)
+    for nothing in ((), []):
+        with pytest.raises(ValueError, match=r"^t: no gradient asked for$"):
+            _want("t", nothing, ("x", "p0"), some=True)
+    with pytest.raises(ValueError, match="unknown gradients"):                          # the unknown name comes first
+        _want("t", ("h_up",), ("x", "p0"), some=True)
+
+
+def test_cotangent():
+    x, buf = torch.zeros(SHAPE), torch.zeros(1, 6, 2, 64)
+    for gy in (torch.zeros(SHAPE), buf[:, 2:4]):
+        assert _same_map(_cotangent("t", gy, x, SHAPE), rowmap(gy)[0])
+    for bad in (torch.zeros(2, 2, 63), torch.zeros(2, 1, 64), torch.zeros(3, 2, 64), buf[:, 2:5]):
+        with pytest.raises(ValueError, match=r"t: gradient \(.*\) does not match the input \(2, 2, 64\)"):
+            _cotangent("t", bad, x, SHAPE)
+    with pytest.raises(ValueError, match="last dimension must be contiguous"):
+        _cotangent("t", torch.zeros(2, 2, 128)[..., ::2], x, SHAPE)
+
+
+def test_signal_grad():
+    buf = torch.zeros(1, 8, 2, 64)
+    x, gy, free = buf[:, 0:2], buf[:, 2:4], buf[:, 4:6]
+    ws = buf[:, 6:8].reshape(-1).view(torch.uint8)
+    xmap = rowmap(x)[0]
+    gx, gxmap = _signal_grad("t", ("x", "p0"), None, SHAPE, xmap, CPU, (x, gy, ws))      # wanted, no out: a new tensor
+    assert gx.shape == SHAPE and gx.dtype == torch.float32 and _same_map(gxmap, rowmap(gx)[0])
+    gx, gxmap = _signal_grad("t", ("x",), free, SHAPE, xmap, CPU, (x, gy, ws))           # wanted, into out
+    assert gx is free and _same_map(gxmap, rowmap(free)[0])
+    assert _signal_grad("t", ("p0",), None, SHAPE, xmap, CPU, (x, gy, ws)) == (None, xmap)   # not wanted: the input's row map
+    assert _signal_grad("t", ("p0",), free, SHAPE, xmap, CPU, (x, gy, ws)) == (None, xmap)   # ... whatever out is
+    for want in (("x", "p0"), ("p0",)):                          # out is checked whether or not "x" is wanted
+        for bad in (x, gy, buf[:, 1:3], buf[:, 6:8]):            # the input, the cotangent, half of each, the workspace
+            with pytest.raises(ValueError, match="t: out must not share memory"):
+                _signal_grad("t", want, bad, SHAPE, xmap, CPU, (x, gy, ws))
+        with pytest.raises(ValueError, match="t: out .* does not match rows=2, channels=2, length=64"):
+            _signal_grad("t", want, torch.zeros(2, 2, 63), SHAPE, xmap, CPU, (x, gy, ws))
+
+
+def test_param_grads():
+    shapes = {"delay": (3, 2), "phase": (3, 2, 2), "dry": (3,)}
+    grads = _param_grads(("x", "phase", "dry"), shapes, CPU)
+    assert grads[0] is None and [tuple(g.shape) for g in grads[1:]] == [(3, 2, 2), (3,)]
+    assert all(g.dtype == torch.float32 and g.is_contiguous() for g in grads[1:])
+    assert _param_grads(("x",), shapes, CPU) == [None, None, None] == _param_grads((), shapes, CPU)
+    assert [tuple(g.shape) for g in _param_grads(["dry", "delay", "phase"], shapes, CPU)] == list(shapes.values())   # shapes' order
+
+
+def test_pair_state():
+    on_gpu = lambda t: t.as_subclass(_SaysGpu)  # noqa: E731
+    shape, seen = (2, 2, 8), []
+
+    def position(pos):
+        seen.append(pos)
+        if pos == "bad":
+            raise ValueError("t: the state's position must be right")
+        return pos
+
+    assert _pair_state("t", None, shape, "position", position) == (None, None) and not seen
+    hist = on_gpu(torch.zeros(shape))
+    for state in ((hist, 7), [hist, 7]):
+        zi, pos = _pair_state("t", state, shape, "position", position)
+        assert zi is hist and pos == 7
+    for bad in (hist, (hist,), (hist, 7, 7), "ab", {0: hist, 1: 7}, (None, 7), (hist, None), (None, None)):
+        with pytest.raises(ValueError, match=r"^t: state must be the pair \(history, position\)$"):
+            _pair_state("t", bad, shape, "position", position)
+    with pytest.raises(ValueError, match=r"^t: state must be the pair \(history, q_last\)$"):
+        _pair_state("t", (hist,), shape, "q_last", position)
+    with pytest.raises(ValueError, match=r"t: the state's history must be .*\(2, 2, 8\).*got \(2, 2, 7\)"):
+        _pair_state("t", (on_gpu(torch.zeros(2, 2, 7)), 7), shape, "position", position)
+    with pytest.raises(ValueError, match="t: the state's position must be right"):      # the second part's own message
+        _pair_state("t", (hist, "bad"), shape, "position", position)
 
 
 @pytest.mark.parametrize("limit", [1, 3, ops.GRID_ROWS_I16_MAX, ops.GRID_YZ_MAX])

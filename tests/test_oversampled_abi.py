@@ -8,6 +8,7 @@ import torch
 
 import oversampled_float64 as o64
 import upfirdn_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ENTRIES = ("gfx_oversampled_waveshaper_f32", "gfx_oversampled_waveshaper_bwd_ws_bytes", "gfx_oversampled_waveshaper_bwd_f32")
 # the issue's table: factor -> alias share of tanh(e^3 x) / e^3 on the tone, float64
@@ -16,11 +17,6 @@ CLASSES = ("TanhDistortion", "PiecewiseTanhDistortion", "PowerDistortion", "Cheb
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib
-
-    protos = header_prototypes()
     fwd = ["const float*", "gfx_rowmap_t", "float*", "gfx_rowmap_t", "int64_t", "int64_t", "int64_t", "int64_t", "const float*",
            "int64_t", "int64_t", "const float*", "int64_t", "int64_t", "int", "int", "int", "const float*", "const float*",
            "const float*", "const float*", "int64_t", "const float*", "void*"]
@@ -28,15 +24,7 @@ def test_the_entries_are_declared_bound_and_exported():
            "const float*", "int64_t", "int64_t", "const float*", "int64_t", "int64_t", "int", "int", "int", "const float*",
            "const float*", "const float*", "const float*", "int64_t", "const float*", "float*", "gfx_rowmap_t", "float*", "float*",
            "float*", "float*", "void*", "size_t", "void*"]
-    want = dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 5), ("int", bwd))))
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        assert protos[name] == want[name], name
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES, dict(zip(ENTRIES, (("int", fwd), ("size_t", ["int64_t"] * 5), ("int", bwd)))))
 
 
 def test_tile_and_workspace_query():
@@ -56,18 +44,13 @@ def test_tile_and_workspace_query():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check comes before the first launch, so the refusals need no GPU: the device pointers below are never
-    followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than these shapes index."""
+    """Every check comes before the first launch, so the refusals need no GPU (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, C, L, N = 3, 2, 2000, 49
     need = lib.gfx_oversampled_waveshaper_bwd_ws_bytes(R, C, L, 0, 4)
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x100000     # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     far = p + 4 * R * C * L      # a second signal that does not overlap the first, a third
     rm, empty, neg = _lib.RowMap(R, 0, C * L, L), _lib.RowMap(0, 0, C * L, L), _lib.RowMap(R, 0, -C * L, L)
     fwd = dict(x=p, xmap=rm, y=far, ymap=rm, R=R, C=C, L=L, factor=4, h_up=p, N_up=N, o_up=24, h_dn=p, N_dn=N, o_dn=24, mode=0,
@@ -101,11 +84,9 @@ def test_entries_refuse_bad_arguments_before_any_launch():
                 "the post gain unused under inverse_post_gain": dict(inverse=1, post=p, g_post=p),
                 "gx is x": dict(gx=p), "gx is gy": dict(gx=far), "gx overlaps x a sample later": dict(gx=p + 4),
                 "an empty gx row map": dict(omap=empty), "no workspace": dict(ws=None)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_oversampled_waveshaper_f32(*{**fwd, **change}.values()) == -1, what            # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_oversampled_waveshaper_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    assert lib.gfx_oversampled_waveshaper_bwd_f32(*{**bwd, "ws_bytes": need - 1}.values()) == -2      # GFX_ENOSPC
+    refused(lib.gfx_oversampled_waveshaper_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_oversampled_waveshaper_bwd_f32, bwd, {**bad, **only_bwd})
+    refused(lib.gfx_oversampled_waveshaper_bwd_f32, bwd, {"a workspace one byte short": dict(ws_bytes=need - 1)}, code=-2)
 
 
 @pytest.mark.parametrize("factor", [1, 2, 3, 4, 8, 16])

@@ -12,6 +12,7 @@ from conftest import assert_close
 
 import stft_band_loss_float64 as b64
 import stft_loss_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gfx_stft_band_loss_sums_f32", "gfx_stft_band_loss_bwd_f32")
@@ -19,32 +20,22 @@ TABLE = ([("mel", n) for n in b64.MEL_BANDS] + [(name, n) for name in b64.ANY fo
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from grafx_amd import _lib
-
     header = open(os.path.join(ROOT, "include", "grafx_amd.h")).read()
-    for name in ENTRIES:
-        assert name + "(" in header and name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name)
     for said in ("Staircase contract", "caller's to guarantee", "n_bins outside"):
         assert said in header
-    assert _lib.lib().gfx_abi_version() == 2 and _lib.ABI_VERSION == 2
+    entries_match(ENTRIES)
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """As for the plain entries (tests/test_stft_loss_abi.py): every check comes before the first launch, so the pointers
-    below are never followed; where a GPU is visible they are a real 16 MB device buffer, larger than anything these shapes
-    index."""
+    """As for the plain entries (tests/test_stft_loss_abi.py): every check comes before the first launch, so the refusals
+    need no GPU (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, L, n_fft, hop, n_bins = 3, 1000, 128, 32, 8
     need = lib.gfx_stft_loss_ws_bytes(R, L, n_fft, hop)
     assert need > 0
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x1000      # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     rm = _lib.RowMap(R, 0, L, 0)
     empty = _lib.RowMap(0, 0, L, 0)
     sums = dict(pred=p, pmap=rm, target=p, tmap=rm, window=p, fb=p, row_lo=p, row_hi=p, n_bins=n_bins, sums=p, R=R, L=L,
@@ -81,14 +72,12 @@ def test_entries_refuse_bad_arguments_before_any_launch():
     only_sums = {"no sums": dict(sums=None)}
     only_bwd = {"no col_lo": dict(col_lo=None), "no col_hi": dict(col_hi=None), "no coefficients": dict(coef=None),
                 "no gradient": dict(gpred=None), "an empty gradient row map": dict(gmap=empty)}
-    for what, change in {**bad, **only_sums}.items():
-        assert lib.gfx_stft_band_loss_sums_f32(*{**sums, **change}.values()) == -1, what       # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_stft_band_loss_bwd_f32(*{**bwd, **change}.values()) == -1, what
+    refused(lib.gfx_stft_band_loss_sums_f32, sums, {**bad, **only_sums})
+    refused(lib.gfx_stft_band_loss_bwd_f32, bwd, {**bad, **only_bwd})
     # the widest filterbank is accepted as far as the checks go: a workspace one byte short is the next refusal
-    for n in (n_bins, n_fft // 2 + 1):
-        assert lib.gfx_stft_band_loss_sums_f32(*{**sums, "n_bins": n, "ws_bytes": need - 1}.values()) == -2       # GFX_ENOSPC
-        assert lib.gfx_stft_band_loss_bwd_f32(*{**bwd, "n_bins": n, "ws_bytes": need - 1}.values()) == -2
+    short = {f"a workspace one byte short, n_bins = {n}": dict(n_bins=n, ws_bytes=need - 1) for n in (n_bins, n_fft // 2 + 1)}
+    refused(lib.gfx_stft_band_loss_sums_f32, sums, short, code=-2)
+    refused(lib.gfx_stft_band_loss_bwd_f32, bwd, short, code=-2)
 
 
 # ------------------------------------------------------------------------------------------------ the formulas

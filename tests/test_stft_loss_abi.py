@@ -8,6 +8,7 @@ import torch
 from conftest import assert_close
 
 import stft_loss_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gfx_stft_loss_ws_bytes", "gfx_stft_loss_sums_f32", "gfx_stft_loss_bwd_f32")
@@ -19,14 +20,9 @@ def documented(R, L, n_fft, hop):
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from grafx_amd import _lib
-
     header = open(os.path.join(ROOT, "include", "grafx_amd.h")).read()
     assert "gfx_stft_loss_ws_bytes = R * ceil((1 + L / hop) * n_fft / 16384) * 16 bytes" in header
-    for name in ENTRIES:
-        assert name + "(" in header and name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name)
-    assert _lib.lib().gfx_abi_version() == 2
+    entries_match(ENTRIES)
 
 
 def test_workspace_query_returns_the_documented_size():
@@ -49,21 +45,15 @@ def test_workspace_query_returns_zero_for_a_bad_argument():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check of the two entries comes before their first launch, so the refusals need no GPU: the pointers below are
-    never followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than anything these
-    shapes index: should a check ever slip behind a launch there, the test fails on the return code and no kernel has been
-    sent to an address nobody owns."""
+    """Every check of the two entries comes before their first launch, so the refusals need no GPU
+    (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, L, n_fft, hop = 3, 1000, 128, 32
     need = lib.gfx_stft_loss_ws_bytes(R, L, n_fft, hop)
     assert need == documented(R, L, n_fft, hop) > 0
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x1000      # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     rm = _lib.RowMap(R, 0, L, 0)
     empty = _lib.RowMap(0, 0, L, 0)
     sums = dict(pred=p, pmap=rm, target=p, tmap=rm, window=p, sums=p, R=R, L=L, n_fft=n_fft, hop=hop, eps=1e-8, ws=p,
@@ -91,13 +81,11 @@ def test_entries_refuse_bad_arguments_before_any_launch():
     }
     only_sums = {"no sums": dict(sums=None)}
     only_bwd = {"no coefficients": dict(coef=None), "no gradient": dict(gpred=None), "an empty gradient row map": dict(gmap=empty)}
-    for what, change in {**bad, **only_sums}.items():
-        assert lib.gfx_stft_loss_sums_f32(*{**sums, **change}.values()) == -1, what       # GFX_EINVAL
-    for what, change in {**bad, **only_bwd}.items():
-        assert lib.gfx_stft_loss_bwd_f32(*{**bwd, **change}.values()) == -1, what
-    # a workspace one byte short
-    assert lib.gfx_stft_loss_sums_f32(*{**sums, "ws_bytes": need - 1}.values()) == -2       # GFX_ENOSPC
-    assert lib.gfx_stft_loss_bwd_f32(*{**bwd, "ws_bytes": need - 1}.values()) == -2
+    refused(lib.gfx_stft_loss_sums_f32, sums, {**bad, **only_sums})
+    refused(lib.gfx_stft_loss_bwd_f32, bwd, {**bad, **only_bwd})
+    short = {"a workspace one byte short": dict(ws_bytes=need - 1)}
+    refused(lib.gfx_stft_loss_sums_f32, sums, short, code=-2)
+    refused(lib.gfx_stft_loss_bwd_f32, bwd, short, code=-2)
 
 
 def test_the_inputs_keep_clear_of_the_jumps_of_the_gradient():

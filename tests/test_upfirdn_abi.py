@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import upfirdn_float64 as f64
+from abi_checks import device_pointer, entries_match, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gfx_upfirdn_f32", "gfx_upfirdn_absmax_ws_bytes", "gfx_upfirdn_absmax_f32")
@@ -22,21 +23,12 @@ IDENTITIES = ((160, 147, 1939, 969, 300), (1, 2, 25, 12, 101), (4, 1, 49, 24, 50
 
 
 def test_the_entries_are_declared_bound_and_exported():
-    from test_abi import ctypes_matches, header_prototypes
-
-    from grafx_amd import _lib, ops
+    from grafx_amd import ops
 
     header = open(os.path.join(ROOT, "include", "grafx_amd.h")).read()
     assert "gfx_upfirdn_absmax_ws_bytes = R * C * ceil(M / GFX_UPFIRDN_TILE) * 16 bytes" in header
     assert int(re.search(r"#define GFX_UPFIRDN_TILE (\d+)", header).group(1)) == ops.UPFIRDN_TILE
-    protos = header_prototypes()
-    for name in ENTRIES:
-        assert name in protos and name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-        ret, params = protos[name]
-        res, args = _lib.SIGNATURES[name]
-        assert ctypes_matches(ret, res, _lib.RowMap) and len(params) == len(args)
-        assert all(ctypes_matches(c, a, _lib.RowMap) for c, a in zip(params, args)), name
-    assert _lib.lib().gfx_abi_version() == 2 == _lib.ABI_VERSION
+    entries_match(ENTRIES)
 
 
 def test_workspace_query_returns_the_documented_size():
@@ -50,20 +42,15 @@ def test_workspace_query_returns_the_documented_size():
 
 
 def test_entries_refuse_bad_arguments_before_any_launch():
-    """Every check of the two entries comes before their first launch, so the refusals need no GPU: the device pointers
-    below are never followed.  Where a GPU is visible the pointer is a real 16 MB device buffer instead, larger than
-    anything these shapes index."""
+    """Every check of the two entries comes before their first launch, so the refusals need no GPU
+    (abi_checks.device_pointer)."""
     from grafx_amd import _lib
 
     lib = _lib.lib()
     R, C, L, M, N = 3, 2, 2000, 2177, 1939
     need = lib.gfx_upfirdn_absmax_ws_bytes(R, C, M)
     assert need == R * C * 3 * 16
-    if torch.cuda.is_available():
-        held = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        p = held.data_ptr()
-    else:
-        p = 0x1000      # stands for any non-null, 16-byte aligned device pointer
+    p, _held = device_pointer()
     rm, ym, empty = _lib.RowMap(R, 0, C * L, L), _lib.RowMap(R, 0, C * M, M), _lib.RowMap(0, 0, C * L, L)
     fwd = dict(x=p, xmap=rm, h=p, N=N, up=160, down=147, offset=969, y=p, ymap=ym, R=R, C=C, L=L, M=M, accumulate=0, stream=None)
     peak = dict(x=p, xmap=rm, h=p, N=N, up=160, down=147, offset=969, peak=p, index=p, R=R, C=C, L=L, M=M, ws=p, ws_bytes=need,
@@ -80,11 +67,9 @@ def test_entries_refuse_bad_arguments_before_any_launch():
     only_fwd = {"no output": dict(y=None), "an empty output row map": dict(ymap=empty)}
     only_peak = {"no peaks": dict(peak=None), "no indices": dict(index=None), "no workspace": dict(ws=None),
                  "a workspace off the 16-byte grid": dict(ws=p + 8), "indices off the 8-byte grid": dict(index=p + 4)}
-    for what, change in {**bad, **only_fwd}.items():
-        assert lib.gfx_upfirdn_f32(*{**fwd, **change}.values()) == -1, what                 # GFX_EINVAL
-    for what, change in {**bad, **only_peak}.items():
-        assert lib.gfx_upfirdn_absmax_f32(*{**peak, **change}.values()) == -1, what
-    assert lib.gfx_upfirdn_absmax_f32(*{**peak, "ws_bytes": need - 1}.values()) == -2        # GFX_ENOSPC
+    refused(lib.gfx_upfirdn_f32, fwd, {**bad, **only_fwd})
+    refused(lib.gfx_upfirdn_absmax_f32, peak, {**bad, **only_peak})
+    refused(lib.gfx_upfirdn_absmax_f32, peak, {"a workspace one byte short": dict(ws_bytes=need - 1)}, code=-2)
 
 
 @pytest.mark.parametrize("orig,new,taps,up,down", DESIGNS)
