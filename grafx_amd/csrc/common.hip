@@ -33,9 +33,9 @@ const float2* tile_twiddle_table(hipStream_t stream) {
     if (!tables[dev]) {
         float2* p = nullptr;
         if (hipMalloc(&p, sizeof(float2) * TW_TABLE_F2) != hipSuccess) return nullptr;
-        hipLaunchKernelGGL(tile_twiddle_table_kernel, dim3(TW_ROWS), dim3(TILE_T), 0, stream, p);
         // make the table visible to every stream before anyone else can use it
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        if (launch(tile_twiddle_table_kernel, dim3(TW_ROWS), dim3(TILE_T), 0, stream, p) != GFX_OK ||
+            hipStreamSynchronize(stream) != hipSuccess) {
             hipFree(p);
             return nullptr;
         }
@@ -69,9 +69,8 @@ int launch_history_tail(const float* x, gfx_rowmap_t xmap, const float* zi, floa
                         int64_t S, const int64_t* pos_in, int64_t* pos_out, hipStream_t stream) {
     const int64_t blocks = history_tail_blocks(R, C, S);
     if (blocks <= 0 || blocks > MAX_GRID_X) return GFX_EINVAL;
-    hipLaunchKernelGGL(history_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, xmap, zi, zf, (int)C, L, S,
-                       (unsigned)((S + HISTORY_CHUNK - 1) / HISTORY_CHUNK), pos_in, pos_out);
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return launch(history_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, xmap, zi, zf, (int)C, L, S,
+                  (unsigned)((S + HISTORY_CHUNK - 1) / HISTORY_CHUNK), pos_in, pos_out);
 }
 
 }  // namespace gfx

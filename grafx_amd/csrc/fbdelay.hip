@@ -22,10 +22,10 @@
 //     gx_c[n]     = dry gy_c[n] + lambda_c[n]
 // mu is stored in the workspace the way w is.  The parameter gradients are plain sums over n once mu exists
 // (fb_bwd_par_kernel: tiles of FB_TILE samples, double accumulators, a fixed-order workgroup reduction, per-tile partials
-// in the workspace; fb_bwd_finish_kernel adds them per row in a fixed order).  No atomics anywhere: equal bits from run
-// to run, and a row's result does not depend on the other rows.  Outside the contract (max_c sum_c' |F[c,c']| < 1,
-// 0 <= a < 1, the delay's range; NaNs included) the delay is clamped before it is split, so every access stays inside
-// its buffer; the values are unspecified.
+// in the workspace; tile_sums_finish_kernel of common.hpp, with FbSlots, adds them per row in a fixed order).  No atomics
+// anywhere: equal bits from run to run, and a row's result does not depend on the other rows.  Outside the contract
+// (max_c sum_c' |F[c,c']| < 1, 0 <= a < 1, the delay's range; NaNs included) the delay is clamped before it is split, so
+// every access stays inside its buffer; the values are unspecified.
 #include "common.hpp"
 
 namespace gfx {
@@ -373,43 +373,26 @@ __global__ __launch_bounds__(FB_THREADS) void fb_bwd_par_kernel(const float* __r
 #pragma unroll
             for (int d = 0; d < C; ++d) s[2 + 2 * C + c * C + d] += (double)lam[c] * (double)qv[d];
     }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        s[k] = wave_sum(s[k]);
-        if (lane == 0) red[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (t < P) {
-        double sum = 0.0;
-        for (int wv = 0; wv < FB_WAVES; ++wv) sum += red[wv][t];
-        part[item * P + t] = sum;
-    }
+    block_sums<P, FB_WAVES>(s, red, lane, wave, [&](double sum) { part[item * P + t] = sum; });
 }
 
-// a row's tile sums -> its parameter gradients: in double, in a fixed order; a null destination is skipped
-__global__ __launch_bounds__(256) void fb_bwd_finish_kernel(const double* __restrict__ part, int64_t R, int64_t ntiles, int C,
-                                                            const float* __restrict__ damping, float* __restrict__ g_delay,
-                                                            float* __restrict__ g_damping, float* __restrict__ g_feedback,
-                                                            float* __restrict__ g_dry, float* __restrict__ g_wet) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int64_t P = 2 + 2 * C + C * C;
-    for (int64_t e = tid; e < R * P; e += nthr) {
-        const int64_t r = e / P, slot = e - r * P;
-        float* dst;
-        double scale = 1.0;
-        if (slot == 0) dst = g_dry ? g_dry + r : nullptr;
-        else if (slot == 1) dst = g_wet ? g_wet + r : nullptr;
-        else if (slot < 2 + C) dst = g_delay ? g_delay + r * C + (slot - 2) : nullptr;
-        else if (slot < 2 + 2 * C) {
-            dst = g_damping ? g_damping + r * C + (slot - 2 - C) : nullptr;
+// a row's tile sums -> its parameter gradients (tile_sums_finish_kernel): dry, wet, delay[C], damping[C] with its
+// 1 / (1 - a), feedback[C, C]; a null destination is skipped
+struct FbSlots {
+    const float* damping;
+    float *g_delay, *g_damping, *g_feedback, *g_dry, *g_wet;
+    int C;
+    __device__ float* dest(int64_t r, int64_t slot, double& scale) const {
+        if (slot == 0) return g_dry ? g_dry + r : nullptr;
+        if (slot == 1) return g_wet ? g_wet + r : nullptr;
+        if (slot < 2 + C) return g_delay ? g_delay + r * C + (slot - 2) : nullptr;
+        if (slot < 2 + 2 * C) {
             scale = 1.0 / (1.0 - (double)damping[r * C + (slot - 2 - C)]);
-        } else dst = g_feedback ? g_feedback + r * C * C + (slot - 2 - 2 * C) : nullptr;
-        if (!dst) continue;
-        double s = 0.0;
-        for (int64_t b = 0; b < ntiles; ++b) s += part[(r * ntiles + b) * P + slot];
-        *dst = (float)(s * scale);
+            return g_damping ? g_damping + r * C + (slot - 2 - C) : nullptr;
+        }
+        return g_feedback ? g_feedback + r * C * C + (slot - 2 - 2 * C) : nullptr;
     }
-}
+};
 
 // the checks both entries share
 static int fb_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, int64_t max_delay, const float* delay,
@@ -456,11 +439,11 @@ int gfx_fbdelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     if (rc != GFX_OK) return rc;
     if (!zi != !q_in || !zf != !q_out) return GFX_EINVAL;              // a state is its history and the loop filter's last value
     if (map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
-    const int64_t nstate = R * C * a.S, nsig = R * C * L;
-    if (zi && zf && (ranges_meet(zi, nstate, zf, nstate) || ranges_meet(q_in, R * C, q_out, R * C))) return GFX_EINVAL;
-    if (zf && history_tail_blocks(R, C, a.S) > MAX_GRID_X) return GFX_EINVAL;
-    if (!ws || reinterpret_cast<uintptr_t>(ws) % alignof(float)) return GFX_EINVAL;
-    if (ws_bytes < gfx_fbdelay_ws_bytes(R, C, L)) return GFX_ENOSPC;
+    const int64_t nsig = R * C * L;
+    if (!history_pair_ok(zi, zf, R, C, a.S)) return GFX_EINVAL;
+    if (zi && zf && ranges_meet(q_in, R * C, q_out, R * C)) return GFX_EINVAL;
+    const int wrc = workspace_ok(ws, ws_bytes, gfx_fbdelay_ws_bytes(R, C, L), alignof(float));
+    if (wrc != GFX_OK) return wrc;
     float* w = static_cast<float*>(ws);
     // the line and the q signal are written while x is read and next to y
     if (fb_meets(w, nsig, x, xmap, R, C, L) || fb_meets(w, nsig, y, ymap, R, C, L)) return GFX_EINVAL;
@@ -469,9 +452,9 @@ int gfx_fbdelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     a.ymap = ymap;
     hipStream_t st = (hipStream_t)stream;
     auto fwd = C == 1 ? fb_fwd_kernel<1> : fb_fwd_kernel<2>;
-    hipLaunchKernelGGL(fwd, dim3((unsigned)R), dim3(FB_THREADS), 0, st, x, y, w, q, delay, damping, feedback, dry, wet, zi, q_in,
-                       q_out, a);
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    if (launch(fwd, dim3((unsigned)R), dim3(FB_THREADS), 0, st, x, y, w, q, delay, damping, feedback, dry, wet, zi, q_in, q_out,
+               a) != GFX_OK)
+        return GFX_ELAUNCH;
     if (zf) {
         const gfx_rowmap_t wmap = {R, 0, C * L, L};
         return launch_history_tail(w, wmap, zi, zf, R, C, L, a.S, nullptr, nullptr, st);
@@ -496,13 +479,10 @@ int gfx_fbdelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     if (!gx && !params) return GFX_EINVAL;
     if (map_negative(gmap)) return GFX_EINVAL;
     const int64_t nsig = R * C * L;
-    if (gx) {
-        if (gxmap.inner <= 0 || map_negative(gxmap)) return GFX_EINVAL;
-        if (signals_overlap(gx, gxmap, x, xmap, R, C, L) || signals_overlap(gx, gxmap, gy, gmap, R, C, L)) return GFX_EINVAL;
-        if (fb_meets(q, nsig, gx, gxmap, R, C, L) || fb_meets(w, nsig, gx, gxmap, R, C, L)) return GFX_EINVAL;
-    }
-    if (!ws || reinterpret_cast<uintptr_t>(ws) % alignof(double)) return GFX_EINVAL;
-    if (ws_bytes < gfx_fbdelay_bwd_ws_bytes(R, C, L)) return GFX_ENOSPC;
+    if (!grad_out_ok(gx, gxmap, x, xmap, gy, gmap, R, C, L)) return GFX_EINVAL;
+    if (gx && (fb_meets(q, nsig, gx, gxmap, R, C, L) || fb_meets(w, nsig, gx, gxmap, R, C, L))) return GFX_EINVAL;
+    const int wrc = workspace_ok(ws, ws_bytes, gfx_fbdelay_bwd_ws_bytes(R, C, L), alignof(double));
+    if (wrc != GFX_OK) return wrc;
     if (params && a.ntiles > MAX_GRID_X / R) return GFX_EINVAL;         // grid.x of the sum kernel
     double* part = static_cast<double*>(ws);
     float* mu = reinterpret_cast<float*>(static_cast<char*>(ws) + fb_par_bytes(R, C, L));
@@ -512,19 +492,17 @@ int gfx_fbdelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     hipStream_t st = (hipStream_t)stream;
     if (gx || g_delay || g_damping || g_feedback) {                     // (dry and wet need no adjoint line)
         auto walk = C == 1 ? fb_bwd_walk_kernel<1> : fb_bwd_walk_kernel<2>;
-        hipLaunchKernelGGL(walk, dim3((unsigned)R), dim3(FB_THREADS), 0, st, gy, gx, mu, delay, damping, feedback, dry, wet, a);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+        if (launch(walk, dim3((unsigned)R), dim3(FB_THREADS), 0, st, gy, gx, mu, delay, damping, feedback, dry, wet, a) != GFX_OK)
+            return GFX_ELAUNCH;
     }
     if (params) {
         if (!(g_delay || g_damping || g_feedback) && hipMemsetAsync(mu, 0, sizeof(float) * (size_t)nsig, st) != hipSuccess)
             return GFX_ELAUNCH;
         auto par = C == 1 ? fb_bwd_par_kernel<1> : fb_bwd_par_kernel<2>;
-        hipLaunchKernelGGL(par, dim3((unsigned)(R * a.ntiles)), dim3(FB_THREADS), 0, st, x, gy, q, w, mu, delay, part, a);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-        const int64_t nb = (R * (2 + 2 * C + C * C) + 255) / 256;
-        hipLaunchKernelGGL(fb_bwd_finish_kernel, dim3((unsigned)(nb > 65535 ? 65535 : nb)), dim3(256), 0, st, part, R, a.ntiles,
-                           (int)C, damping, g_delay, g_damping, g_feedback, g_dry, g_wet);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+        if (launch(par, dim3((unsigned)(R * a.ntiles)), dim3(FB_THREADS), 0, st, x, gy, q, w, mu, delay, part, a) != GFX_OK)
+            return GFX_ELAUNCH;
+        return finish_tile_sums(FbSlots{damping, g_delay, g_damping, g_feedback, g_dry, g_wet, (int)C}, part, R,
+                                2 + 2 * C + C * C, a.ntiles, st);
     }
     return GFX_OK;
 }

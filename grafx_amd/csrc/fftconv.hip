@@ -359,14 +359,12 @@ __global__ __launch_bounds__(TILE_T, 2) void corr1_kernel(const float* __restric
 
 static thread_local const char* t_last_kernel = "";   // see gfx_fftconv_last_kernel
 
-// One launch of fftconv_sched on pad8(nblocks) workgroups: the LDS opt-in of the kernel it launches, the launch and its
-// check.  On success `name` (unless null) is what gfx_fftconv_last_kernel returns.  Every launch of this file's kernels goes through
-// here, so none runs without its opt-in.
+// One launch of fftconv_sched on pad8(nblocks) workgroups, through launch() of common.hpp (the LDS opt-in, the launch, its
+// check).  On success `name` (unless null) is what gfx_fftconv_last_kernel returns.  Every launch of this file's kernels goes
+// through here, so none runs without its opt-in.
 template <typename K, typename... Args>
 static int launch_tile(K kernel, const char* name, int64_t nblocks, unsigned threads, size_t lds, hipStream_t st, Args... args) {
-    if (allow_lds(kernel, lds)) return GFX_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3(pad8(nblocks)), dim3(threads), lds, st, args...);
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    if (launch(kernel, dim3(pad8(nblocks)), dim3(threads), lds, st, args...) != GFX_OK) return GFX_ELAUNCH;
     if (name) t_last_kernel = name;
     return GFX_OK;
 }

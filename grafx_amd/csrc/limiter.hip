@@ -347,16 +347,11 @@ __global__ __launch_bounds__(LIM_THREADS) void lim_bwd_kernel(const float* __res
     }
 }
 
-// a row's tile sums -> its ceiling gradient: in double, in a fixed order
-__global__ __launch_bounds__(256) void lim_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ g_log_ceiling,
-                                                             int64_t R, int64_t ntiles) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t r = tid; r < R; r += nthr) {
-        double s = 0.0;
-        for (int64_t b = 0; b < ntiles; ++b) s += part[r * ntiles + b];
-        g_log_ceiling[r] = (float)s;
-    }
-}
+// a row's tile sums -> its ceiling gradient (tile_sums_finish_kernel): the one slot of a row
+struct LimSlots {
+    float* g_log_ceiling;
+    __device__ float* dest(int64_t r, int64_t, double&) const { return g_log_ceiling + r; }
+};
 
 // the checks both entries share, then the tile geometry
 static int lim_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, const float* log_ceiling,
@@ -396,17 +391,14 @@ int gfx_limiter_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ym
     if ((zi || zf) && sigma > 0) return GFX_EINVAL;    // the compensated output needs samples the next block brings
     // tiles read each other's halos of x: never in place
     if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
-    const int64_t nstate = R * C * a.S;
-    if (zi && zf && nstate > 0 && ranges_meet(zi, nstate, zf, nstate)) return GFX_EINVAL;
-    if (zf && history_tail_blocks(R, C, a.S) > MAX_GRID_X) return GFX_EINVAL;   // (past 2^30 state rows: refused before any launch)
+    if (!history_pair_ok(zi, zf, R, C, a.S)) return GFX_EINVAL;        // (past 2^30 state rows: refused before any launch)
     a.ymap = ymap;
     a.pwords = a.T + a.N - 1 + a.M - 1;
     const size_t lds = sizeof(float) * ((size_t)a.N + 2 * (size_t)a.pwords);
-    if (allow_lds(lim_fwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(lim_fwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, y, log_ceiling, w, zi, gain,
-                       a);
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    if (launch(lim_fwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, y, log_ceiling, w, zi, gain, a) !=
+        GFX_OK)
+        return GFX_ELAUNCH;
     if (zf && a.S > 0) return launch_history_tail(x, xmap, zi, zf, R, C, L, a.S, nullptr, nullptr, st);
     return GFX_OK;
 }
@@ -426,14 +418,11 @@ int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     if (rc != GFX_OK) return rc;
     if (!gx && !g_log_ceiling) return GFX_EINVAL;
     if (map_negative(xmap) || map_negative(gmap)) return GFX_EINVAL;
-    if (gx) {
-        if (omap.inner <= 0 || map_negative(omap)) return GFX_EINVAL;
-        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
-    }
+    if (!grad_out_ok(gx, omap, x, xmap, gy, gmap, R, C, L)) return GFX_EINVAL;
     double* part = nullptr;
     if (g_log_ceiling) {
-        if (!ws || reinterpret_cast<uintptr_t>(ws) % alignof(double)) return GFX_EINVAL;
-        if (ws_bytes < gfx_limiter_bwd_ws_bytes(R, L, D, H)) return GFX_ENOSPC;
+        const int wrc = workspace_ok(ws, ws_bytes, gfx_limiter_bwd_ws_bytes(R, L, D, H), alignof(double));
+        if (wrc != GFX_OK) return wrc;
         part = static_cast<double*>(ws);
     }
     a.gmap = gmap;
@@ -442,17 +431,11 @@ int gfx_limiter_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx_
     a.pwords += a.pwords & 1;                            // (the 16-bit indices behind the floats stay 4-byte aligned)
     a.qwords = a.T + a.M - 1;
     const size_t lds = sizeof(float) * ((size_t)a.N + 2 * (size_t)a.pwords + (size_t)a.qwords) + 2 * sizeof(uint16_t) * (size_t)a.pwords;
-    if (allow_lds(lim_bwd_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(lim_bwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, gy, gx, log_ceiling, w, part,
-                       a);
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    if (part) {
-        const int64_t nb = (R + 255) / 256;
-        hipLaunchKernelGGL(lim_bwd_finish_kernel, dim3((unsigned)(nb > 65535 ? 65535 : nb)), dim3(256), 0, st, part,
-                           g_log_ceiling, R, a.ntiles);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (launch(lim_bwd_kernel, dim3((unsigned)(R * a.ntiles)), dim3(LIM_THREADS), lds, st, x, gy, gx, log_ceiling, w, part, a) !=
+        GFX_OK)
+        return GFX_ELAUNCH;
+    if (part) return finish_tile_sums(LimSlots{g_log_ceiling}, part, R, 1, a.ntiles, st);
     return GFX_OK;
 }
 

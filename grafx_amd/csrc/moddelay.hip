@@ -21,7 +21,7 @@
 //     ascending n.
 //   - md_bwd_par_kernel, the six parameter gradients: the forward's gather again, with the derivative weights l'_j, summed
 //     over the tile in double (g_rate carries the factor p, and the terms change sign).  The tile sums go to the
-//     workspace, md_bwd_finish_kernel adds them per row in a fixed order.
+//     workspace, tile_sums_finish_kernel (common.hpp, with MdSlots) adds them per row in a fixed order.
 // No atomics anywhere: equal bits from run to run, and a row's result does not depend on the other rows.  Outside the
 // contract every index is still inside its buffer (d is clamped before it is split, the run walk is bounded); the values
 // are unspecified.  Base offsets are 64-bit, everything inside the tile 32-bit.
@@ -338,20 +338,12 @@ __global__ __launch_bounds__(MD_THREADS) void md_bwd_par_kernel(const float* __r
                 s[4] += gg * (double)u;
                 if (v == 0) s[5] += gg * (double)xs[H + tt];
             }
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                s[k] = wave_sum(s[k]);
-                if (lane == 0) red[wave][k] = s[k];
-            }
-            __syncthreads();
-            if (t < K) {
-                double sum = 0.0;
-                for (int w = 0; w < MD_WAVES; ++w) sum += red[w][t];
+            block_sums<K, MD_WAVES>(s, red, lane, wave, [&](double sum) {
                 if (t < 3) tot[t * MD_MAX_VOICES + v] += sum;
                 else if (t == 3) out[1 + 3 * V + v * C + c] = sum;
                 else if (t == 4) out[1 + 3 * V + V * C + v * C + c] = sum;
                 else if (v == 0) tot[3 * MD_MAX_VOICES] += sum;
-            }
+            });
             __syncthreads();
         }
     }
@@ -359,31 +351,23 @@ __global__ __launch_bounds__(MD_THREADS) void md_bwd_par_kernel(const float* __r
     if (t == 0) out[0] = tot[3 * MD_MAX_VOICES];
 }
 
-// a row's tile sums -> its parameter gradients: in double, in a fixed order; a null destination is skipped
-__global__ __launch_bounds__(256) void md_bwd_finish_kernel(const double* __restrict__ part, int64_t R, int64_t ntiles, int V, int C,
-                                                            float* __restrict__ g_delay, float* __restrict__ g_depth,
-                                                            float* __restrict__ g_rate, float* __restrict__ g_phase,
-                                                            float* __restrict__ g_gain, float* __restrict__ g_dry) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int64_t P = 1 + 3 * V + 2 * V * C, VC = (int64_t)V * C;
-    for (int64_t e = tid; e < R * P; e += nthr) {
-        const int64_t r = e / P, slot = e - r * P;
-        float* dst;
-        if (slot == 0) dst = g_dry ? g_dry + r : nullptr;
-        else if (slot <= 3 * V) {
+// a row's tile sums -> its parameter gradients (tile_sums_finish_kernel): dry, three blocks of V, two blocks of V C; a null
+// destination is skipped
+struct MdSlots {
+    float *g_delay, *g_depth, *g_rate, *g_phase, *g_gain, *g_dry;
+    int V, C;
+    __device__ float* dest(int64_t r, int64_t slot, double&) const {
+        const int64_t VC = (int64_t)V * C;
+        if (slot == 0) return g_dry ? g_dry + r : nullptr;
+        if (slot <= 3 * V) {
             const int64_t which = (slot - 1) / V, v = (slot - 1) - which * V;
             float* base = which == 0 ? g_delay : which == 1 ? g_depth : g_rate;
-            dst = base ? base + r * V + v : nullptr;
-        } else {
-            const int64_t q = slot - 1 - 3 * V;
-            dst = q < VC ? (g_phase ? g_phase + r * VC + q : nullptr) : (g_gain ? g_gain + r * VC + (q - VC) : nullptr);
+            return base ? base + r * V + v : nullptr;
         }
-        if (!dst) continue;
-        double s = 0.0;
-        for (int64_t b = 0; b < ntiles; ++b) s += part[(r * ntiles + b) * P + slot];
-        *dst = (float)s;
+        const int64_t q = slot - 1 - 3 * V;
+        return q < VC ? (g_phase ? g_phase + r * VC + q : nullptr) : (g_gain ? g_gain + r * VC + (q - VC) : nullptr);
     }
-}
+};
 
 // the checks both entries share, then the tile geometry
 static int md_prepare(const float* x, gfx_rowmap_t xmap, int64_t R, int64_t C, int64_t L, int64_t V, int64_t interp,
@@ -418,17 +402,15 @@ int gfx_moddelay_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t y
     if (!zi != !pos_in || !zf != !pos_out) return GFX_EINVAL;          // a state is its history and its position
     // tiles read each other's halos of x: never in place
     if (map_negative(xmap) || map_negative(ymap) || signals_overlap(y, ymap, x, xmap, R, C, L)) return GFX_EINVAL;
-    const int64_t nstate = R * C * a.S;
-    if (zi && zf && (ranges_meet(zi, nstate, zf, nstate) || (pos_in < pos_out + R && pos_out < pos_in + R))) return GFX_EINVAL;
-    if (zf && history_tail_blocks(R, C, a.S) > MAX_GRID_X) return GFX_EINVAL;   // (past 2^30 state rows: refused before any launch)
+    if (!history_pair_ok(zi, zf, R, C, a.S)) return GFX_EINVAL;        // (past 2^30 state rows: refused before any launch)
+    if (zi && zf && pos_in < pos_out + R && pos_out < pos_in + R) return GFX_EINVAL;
     a.ymap = ymap;
     const size_t lds = sizeof(float) * (size_t)(MD_TILE + a.S);
     auto fwd = interp ? md_fwd_kernel<1> : md_fwd_kernel<0>;
-    if (allow_lds(fwd, lds) != GFX_OK) return GFX_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(fwd, dim3((unsigned)(R * a.ntiles)), dim3(MD_THREADS), lds, st, x, y, delay, depth, rate, phase, gain, dry,
-                       zi, pos_in, a);
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    if (launch(fwd, dim3((unsigned)(R * a.ntiles)), dim3(MD_THREADS), lds, st, x, y, delay, depth, rate, phase, gain, dry, zi,
+               pos_in, a) != GFX_OK)
+        return GFX_ELAUNCH;
     if (zf) return launch_history_tail(x, xmap, zi, zf, R, C, L, a.S, pos_in, pos_out, st);   // and the rows' positions, moved on by L
     return GFX_OK;
 }
@@ -450,13 +432,10 @@ int gfx_moddelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx
     const bool params = g_delay || g_depth || g_rate || g_phase || g_gain || g_dry;
     if (!gx && !params) return GFX_EINVAL;
     if (map_negative(xmap) || map_negative(gmap)) return GFX_EINVAL;
-    if (gx) {
-        if (gxmap.inner <= 0 || map_negative(gxmap)) return GFX_EINVAL;
-        if (signals_overlap(gx, gxmap, x, xmap, R, C, L) || signals_overlap(gx, gxmap, gy, gmap, R, C, L)) return GFX_EINVAL;
-    }
+    if (!grad_out_ok(gx, gxmap, x, xmap, gy, gmap, R, C, L)) return GFX_EINVAL;
     if (params) {
-        if (!ws || reinterpret_cast<uintptr_t>(ws) % alignof(double)) return GFX_EINVAL;
-        if (ws_bytes < gfx_moddelay_bwd_ws_bytes(R, C, L, V)) return GFX_ENOSPC;
+        const int wrc = workspace_ok(ws, ws_bytes, gfx_moddelay_bwd_ws_bytes(R, C, L, V), alignof(double));
+        if (wrc != GFX_OK) return wrc;
     }
     a.gmap = gmap;
     a.ymap = gx ? gxmap : xmap;
@@ -466,21 +445,17 @@ int gfx_moddelay_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, gfx
         const int cap = MD_TILE + a.Dmax + 4;            // even: the 16-bit positions behind the floats stay aligned
         const size_t lds = (sizeof(float) + sizeof(uint16_t)) * (size_t)cap;
         auto bx = interp ? md_bwd_x_kernel<1> : md_bwd_x_kernel<0>;
-        if (allow_lds(bx, lds) != GFX_OK) return GFX_ELAUNCH;
-        hipLaunchKernelGGL(bx, grid, dim3(MD_THREADS), lds, st, gy, gx, delay, depth, rate, phase, gain, dry, a, cap);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+        if (launch(bx, grid, dim3(MD_THREADS), lds, st, gy, gx, delay, depth, rate, phase, gain, dry, a, cap) != GFX_OK)
+            return GFX_ELAUNCH;
     }
     if (params) {
         double* part = static_cast<double*>(ws);
         const size_t lds = sizeof(float) * (size_t)(MD_TILE + a.S);
         auto bp = interp ? md_bwd_par_kernel<1> : md_bwd_par_kernel<0>;
-        if (allow_lds(bp, lds) != GFX_OK) return GFX_ELAUNCH;
-        hipLaunchKernelGGL(bp, grid, dim3(MD_THREADS), lds, st, x, gy, delay, depth, rate, phase, gain, part, a);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-        const int64_t nb = (R * (1 + 3 * V + 2 * V * C) + 255) / 256;
-        hipLaunchKernelGGL(md_bwd_finish_kernel, dim3((unsigned)(nb > 65535 ? 65535 : nb)), dim3(256), 0, st, part, R, a.ntiles,
-                           (int)V, (int)C, g_delay, g_depth, g_rate, g_phase, g_gain, g_dry);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+        if (launch(bp, grid, dim3(MD_THREADS), lds, st, x, gy, delay, depth, rate, phase, gain, part, a) != GFX_OK)
+            return GFX_ELAUNCH;
+        return finish_tile_sums(MdSlots{g_delay, g_depth, g_rate, g_phase, g_gain, g_dry, (int)V, (int)C}, part, R,
+                                1 + 3 * V + 2 * V * C, a.ntiles, st);
     }
     return GFX_OK;
 }

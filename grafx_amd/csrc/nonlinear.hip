@@ -80,9 +80,8 @@ extern "C" {
 int gfx_row_mean_f32(const float* x, gfx_rowmap_t xmap, float* mean, int64_t R, int64_t C, int64_t L, void* stream) {
     if (!x || !mean || R <= 0 || C <= 0 || L <= 0 || xmap.inner <= 0 || R > 0x7fffffffLL) return GFX_EINVAL;
     const int64_t n = R * C;
-    hipLaunchKernelGGL(row_mean_kernel, dim3((unsigned)(n > 65535 * 16 ? 65535 * 16 : n)), dim3(256), 0,
-                       (hipStream_t)stream, x, xmap, mean, R, (int)C, L);
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return launch(row_mean_kernel, dim3((unsigned)(n > 65535 * 16 ? 65535 * 16 : n)), dim3(256), 0, (hipStream_t)stream, x, xmap,
+                  mean, R, (int)C, L);
 }
 
 int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t ymap, int64_t R, int64_t C, int64_t L,
@@ -100,21 +99,10 @@ int gfx_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, gfx_rowmap_t
     if (bx < 1) bx = 1;
     const dim3 grid((unsigned)bx, (unsigned)(R > 65535 ? 65535 : R));
     hipStream_t st = (hipStream_t)stream;
-    switch (mode) {
-        case GFX_WS_TANH:
-            hipLaunchKernelGGL(waveshaper_kernel<GFX_WS_TANH>, grid, dim3(256), 0, st, x, y, log_pre_gain, log_post_gain, p0, p1, dc, a, vec);
-            break;
-        case GFX_WS_PIECEWISE:
-            hipLaunchKernelGGL(waveshaper_kernel<GFX_WS_PIECEWISE>, grid, dim3(256), 0, st, x, y, log_pre_gain, log_post_gain, p0, p1, dc, a, vec);
-            break;
-        case GFX_WS_POWER:
-            hipLaunchKernelGGL(waveshaper_kernel<GFX_WS_POWER>, grid, dim3(256), 0, st, x, y, log_pre_gain, log_post_gain, p0, p1, dc, a, vec);
-            break;
-        default:
-            hipLaunchKernelGGL(waveshaper_kernel<GFX_WS_CHEBYSHEV>, grid, dim3(256), 0, st, x, y, log_pre_gain, log_post_gain, p0, p1, dc, a, vec);
-            break;
-    }
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return with_ws_mode(mode, [&](auto m) {
+        return launch(waveshaper_kernel<decltype(m)::value>, grid, dim3(256), 0, st, x, y, log_pre_gain, log_post_gain, p0, p1, dc,
+                      a, vec);
+    });
 }
 
 }  // extern "C"
@@ -293,9 +281,8 @@ int ws_bwd_finish(const WsBwdSpace& s, const WsGrads& g, int64_t R, int64_t C, i
     const int NS = ws_nsums(K);
     const int64_t items = R * (NS > (int)C ? NS : (int)C);
     const int64_t nb = (items + 255) / 256;
-    hipLaunchKernelGGL(ws_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, stream, s.part,
-                       s.dcpart, s.gmean, g.pre, g.post, g.p0, g.p1, R, (int)C, L, NS, npart, ndc, mode, (int)K);
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return launch(ws_bwd_finish_kernel, dim3((unsigned)(nb > 65535 * 16 ? 65535 * 16 : nb)), dim3(256), 0, stream, s.part,
+                  s.dcpart, s.gmean, g.pre, g.post, g.p0, g.p1, R, (int)C, L, NS, npart, ndc, mode, (int)K);
 }
 
 // the adjoint of the centring x - mean(x): gx -= mean(gx) per row-channel
@@ -338,10 +325,8 @@ int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, g
     const WsGrads grads{g_log_pre_gain, g_log_post_gain, g_p0, g_p1};
     if (ws_check_grads(grads, gx, mode, inverse_post_gain, log_pre_gain, log_post_gain, p0) != GFX_OK) return GFX_EINVAL;
     const bool want_par = grads.any();
-    if (gx) {
-        if (omap.inner <= 0 || map_negative(xmap) || map_negative(gmap) || map_negative(omap)) return GFX_EINVAL;
-        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
-    }
+    if (gx && (map_negative(xmap) || map_negative(gmap))) return GFX_EINVAL;
+    if (!grad_out_ok(gx, omap, x, xmap, gy, gmap, R, C, L)) return GFX_EINVAL;
     const bool center = dc && gx;
     const int64_t bx = ws_blocks(L);
     WsBwdSpace sp;
@@ -353,27 +338,15 @@ int gfx_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const float* gy, g
     const int vec = aligned16(x) && aligned16(gy) && map_vec(xmap) && map_vec(gmap) && (!gx || (aligned16(gx) && map_vec(omap)));
     const dim3 grid((unsigned)bx, (unsigned)(R > 65535 ? 65535 : R));
     hipStream_t st = (hipStream_t)stream;
-    switch (mode) {
-        case GFX_WS_TANH:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_TANH>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
-            break;
-        case GFX_WS_PIECEWISE:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_PIECEWISE>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
-            break;
-        case GFX_WS_POWER:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_POWER>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
-            break;
-        default:
-            hipLaunchKernelGGL(waveshaper_bwd_kernel<GFX_WS_CHEBYSHEV>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a, vec);
-            break;
-    }
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    const int lrc = with_ws_mode(mode, [&](auto m) {
+        return launch(waveshaper_bwd_kernel<decltype(m)::value>, grid, dim3(256), 0, st, x, gy, gx, log_pre_gain, log_post_gain, p0,
+                      p1, dc, sp.part, sp.dcpart, a, vec);
+    });
+    if (lrc != GFX_OK) return GFX_ELAUNCH;
     if (ws_bwd_finish(sp, grads, R, C, L, K, bx, bx, mode, st) != GFX_OK) return GFX_ELAUNCH;
-    if (center) {
-        hipLaunchKernelGGL(ws_sub_mean_kernel, grid, dim3(256), 0, st, gx, omap, sp.gmean, R, (int)C, L,
-                           (int)(aligned16(gx) && map_vec(omap)));
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (center)
+        return launch(ws_sub_mean_kernel, grid, dim3(256), 0, st, gx, omap, sp.gmean, R, (int)C, L,
+                      (int)(aligned16(gx) && map_vec(omap)));
     return GFX_OK;
 }
 
@@ -471,10 +444,8 @@ __global__ __launch_bounds__(256) void rdft_kernel(const float* __restrict__ x, 
 extern "C" int gfx_rdft_f32(const float* x, float* X, int64_t rows, int64_t K, int64_t n, void* stream) {
     if (!x || !X || rows <= 0 || rows > 65535 || n < 1 || n > 8192 || K != n / 2 + 1) return GFX_EINVAL;
     const size_t lds = (size_t)n * (sizeof(float2) + sizeof(float));
-    if (gfx::allow_lds(gfx::rdft_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
-    hipLaunchKernelGGL(gfx::rdft_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)rows), dim3(256), lds, (hipStream_t)stream, x, X,
+    return gfx::launch(gfx::rdft_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)rows), dim3(256), lds, (hipStream_t)stream, x, X,
                        (int)K, (int)n);
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
 }
 
 extern "C" int gfx_irdft_f32(const float* X, int is_real, float* y, int64_t rows, int64_t K, int64_t n, int64_t roll,
@@ -482,8 +453,6 @@ extern "C" int gfx_irdft_f32(const float* X, int is_real, float* y, int64_t rows
     if (!X || !y || rows <= 0 || rows > 0x7fffffffLL || n < 1 || n > 8192 || K != n / 2 + 1 || roll < 0 || roll >= n)
         return GFX_EINVAL;
     const size_t lds = (size_t)(n + K) * sizeof(float2);
-    if (gfx::allow_lds(gfx::irdft_kernel, lds) != GFX_OK) return GFX_ELAUNCH;
-    hipLaunchKernelGGL(gfx::irdft_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, X, is_real, y, (int)K,
-                       (int)n, (int)roll, window);
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return gfx::launch(gfx::irdft_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, X, is_real, y, (int)K, (int)n,
+                       (int)roll, window);
 }

@@ -440,18 +440,10 @@ int gfx_oversampled_waveshaper_f32(const float* x, gfx_rowmap_t xmap, float* y, 
     const size_t lds = os_layout(a, (int)N_dn, (int)(N_dn - 1 - offset_dn), false);
     const dim3 grid((unsigned)(R * C * a.ntiles));
     hipStream_t st = (hipStream_t)stream;
-#define GFX_OS_FWD(M)                                                                                                          \
-    if (allow_lds(os_fwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                        \
-    hipLaunchKernelGGL(os_fwd_kernel<M>, grid, dim3(OS_THREADS), lds, st, x, y, h_up, h_dn, log_pre_gain, log_post_gain, p0, p1, \
-                       dc, a)
-    switch (mode) {
-        case GFX_WS_TANH: GFX_OS_FWD(GFX_WS_TANH); break;
-        case GFX_WS_PIECEWISE: GFX_OS_FWD(GFX_WS_PIECEWISE); break;
-        case GFX_WS_POWER: GFX_OS_FWD(GFX_WS_POWER); break;
-        default: GFX_OS_FWD(GFX_WS_CHEBYSHEV); break;
-    }
-#undef GFX_OS_FWD
-    return hipGetLastError() == hipSuccess ? GFX_OK : GFX_ELAUNCH;
+    return with_ws_mode(mode, [&](auto m) {
+        return launch(os_fwd_kernel<decltype(m)::value>, grid, dim3(OS_THREADS), lds, st, x, y, h_up, h_dn, log_pre_gain,
+                      log_post_gain, p0, p1, dc, a);
+    });
 }
 
 size_t gfx_oversampled_waveshaper_bwd_ws_bytes(int64_t R, int64_t C, int64_t L, int64_t K, int64_t factor) {
@@ -476,10 +468,8 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
     const WsGrads grads{g_log_pre_gain, g_log_post_gain, g_p0, g_p1};
     if (ws_check_grads(grads, gx, mode, inverse_post_gain, log_pre_gain, log_post_gain, p0) != GFX_OK) return GFX_EINVAL;
     const bool want_par = grads.any();
-    if (gx) {
-        if (omap.inner <= 0 || map_negative(xmap) || map_negative(gmap) || map_negative(omap)) return GFX_EINVAL;
-        if (signals_overlap(gx, omap, x, xmap, R, C, L) || signals_overlap(gx, omap, gy, gmap, R, C, L)) return GFX_EINVAL;
-    }
+    if (gx && (map_negative(xmap) || map_negative(gmap))) return GFX_EINVAL;
+    if (!grad_out_ok(gx, omap, x, xmap, gy, gmap, R, C, L)) return GFX_EINVAL;
     const bool center = dc && gx;
     const int64_t npart = C * a.ntiles;              // partials of a row's sum, of a row-channel's: a.ntiles
     WsBwdSpace sp;
@@ -491,23 +481,13 @@ int gfx_oversampled_waveshaper_bwd_f32(const float* x, gfx_rowmap_t xmap, const 
     const size_t lds = os_layout(a, (int)N_up, (int)offset_up, true);
     const dim3 grid((unsigned)(R * C * a.ntiles));
     hipStream_t st = (hipStream_t)stream;
-#define GFX_OS_BWD(M)                                                                                                          \
-    if (allow_lds(os_bwd_kernel<M>, lds) != GFX_OK) return GFX_ELAUNCH;                                                        \
-    hipLaunchKernelGGL(os_bwd_kernel<M>, grid, dim3(OS_THREADS), lds, st, x, gy, gx, h_up, h_dn, log_pre_gain, log_post_gain, \
-                       p0, p1, dc, sp.part, sp.dcpart, a)
-    switch (mode) {
-        case GFX_WS_TANH: GFX_OS_BWD(GFX_WS_TANH); break;
-        case GFX_WS_PIECEWISE: GFX_OS_BWD(GFX_WS_PIECEWISE); break;
-        case GFX_WS_POWER: GFX_OS_BWD(GFX_WS_POWER); break;
-        default: GFX_OS_BWD(GFX_WS_CHEBYSHEV); break;
-    }
-#undef GFX_OS_BWD
-    if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
+    const int lrc = with_ws_mode(mode, [&](auto m) {
+        return launch(os_bwd_kernel<decltype(m)::value>, grid, dim3(OS_THREADS), lds, st, x, gy, gx, h_up, h_dn, log_pre_gain,
+                      log_post_gain, p0, p1, dc, sp.part, sp.dcpart, a);
+    });
+    if (lrc != GFX_OK) return GFX_ELAUNCH;
     if (ws_bwd_finish(sp, grads, R, C, L, K, npart, a.ntiles, mode, st) != GFX_OK) return GFX_ELAUNCH;
-    if (center) {
-        hipLaunchKernelGGL(os_sub_mean_kernel, grid, dim3(OS_THREADS), 0, st, gx, omap, sp.gmean, (int)C, L, a.T, a.ntiles);
-        if (hipGetLastError() != hipSuccess) return GFX_ELAUNCH;
-    }
+    if (center) return launch(os_sub_mean_kernel, grid, dim3(OS_THREADS), 0, st, gx, omap, sp.gmean, (int)C, L, a.T, a.ntiles);
     return GFX_OK;
 }
 

@@ -3,6 +3,8 @@
 // terms of every parameter sum, and on the host the argument checks and the workspace layout that the entries of both
 // files share.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace gfx {
@@ -208,6 +210,18 @@ static inline int ws_check_shaper(int mode, int inverse_post_gain, const float* 
     return GFX_OK;
 }
 
+// f(std::integral_constant<int, MODE>{}) for the shaper `mode` (checked by ws_check_shaper), and what it returns: how an
+// entry picks the instance of a kernel template, `kernel<decltype(m)::value>`
+template <typename F>
+static inline int with_ws_mode(int mode, F&& f) {
+    switch (mode) {
+        case GFX_WS_TANH: return f(std::integral_constant<int, GFX_WS_TANH>{});
+        case GFX_WS_PIECEWISE: return f(std::integral_constant<int, GFX_WS_PIECEWISE>{});
+        case GFX_WS_POWER: return f(std::integral_constant<int, GFX_WS_POWER>{});
+        default: return f(std::integral_constant<int, GFX_WS_CHEBYSHEV>{});
+    }
+}
+
 struct WsGrads {                 // the parameter gradients a backward entry may be asked for
     float *pre, *post, *p0, *p1;
     bool any() const { return pre || post || p0 || p1; }
@@ -237,8 +251,9 @@ static inline int ws_bwd_carve(void* ws, size_t ws_bytes, int64_t R, int64_t C, 
                                bool want_par, bool center, WsBwdSpace& s) {
     s.part = s.dcpart = s.gmean = nullptr;
     if (!want_par && !center) return GFX_OK;
-    if (!ws) return GFX_EINVAL;
-    if (ws_bytes < sizeof(float) * ws_bwd_floats(R, C, K, npart, ndc)) return GFX_ENOSPC;
+    // (alignment 1: these entries have never refused a misaligned workspace)
+    const int rc = workspace_ok(ws, ws_bytes, sizeof(float) * ws_bwd_floats(R, C, K, npart, ndc), 1);
+    if (rc != GFX_OK) return rc;
     float* w = static_cast<float*>(ws);
     if (want_par) s.part = w;
     if (center) {

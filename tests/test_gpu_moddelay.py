@@ -173,6 +173,24 @@ def test_gradients_against_the_yardstick(V, Dmax, interp):
                     assert (a is None) if name not in subset else torch.equal(a, b), f"{what}: want={subset}: {name}"
 
 
+def test_a_single_gradient_over_three_tiles_has_the_bits_of_all_seven():
+    """Every gradient asked for alone, on rows of two tiles and 17 samples: None for the other six and the bits of the call
+    that asks for all.  Alone, every other slot of the rows' tile sums has no destination when they are added up."""
+    from grafx_amd import ops
+
+    V, Dmax, R, C = 2, 441, 3, 2
+    L = 2 * _tile(Dmax, C) + 17
+    x = m64.bright_rows(R, C, L, 21).cuda()
+    params = _cuda(m64.draw_parameters(R, V, C, Dmax, 22))
+    g = torch.randn(R, C, L, generator=torch.Generator().manual_seed(23)).cuda()
+    for interp in ("linear", "cubic"):
+        every = ops.moddelay_bwd(x, g, *params, Dmax, interp)
+        for only in NAMES:
+            part = ops.moddelay_bwd(x, g, *params, Dmax, interp, want=(only,))
+            for name, a, b in zip(NAMES, part, every):
+                assert (a is None) if name != only else torch.equal(a, b), f"{interp}: want=({only},): {name}"
+
+
 def test_determinism_rows_and_layout():
     """Two runs give equal bits, forward and backward; a row's result does not depend on the other rows; strided
     (B, n, C, L) views in and out match contiguous ones; an ``out`` that overlaps an input is refused."""
